@@ -57,6 +57,8 @@ def parse():
     ap.add_argument("--no-shard-projection", action="store_true",
                     help="skip timing the 1/2, 1/4, 1/8 per-rank shares of the batch on this one GPU (N = 1 only)")
     ap.add_argument("--cpu-pairs", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned (pred_logits, pred_masks) to DIR/<name>.npy, float32")
     return ap.parse_args()
 
 
@@ -144,6 +146,27 @@ def hbm_traffic(kernel, mode):
     if not k:
         return None, f"{name} has no entry for {kernel}"
     return k["hbm_bytes_per_launch"], f"{name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, same workload, git {d.get('git_sha', '?')})"
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, logits, masks):
+    """The headline's last timed step as a caller of _mask_vrd receives it, as float32 .npy files.  Above DUMP_LIMIT_BYTES
+    a fixed, seeded sample of pairs (sorted) is written instead, with its pair indices as pair_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"pred_logits": logits.detach().float(), "pred_masks": masks.detach().float()}
+    n = logits.shape[0]
+    per_pair = sum(v[0].numel() for v in out.values()) * 4
+    if n * per_pair > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - 8 * n) // per_pair)
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+        out = {name: v[idx.to(v.device)] for name, v in out.items()}
+        out["pair_index"] = idx.double()
+    for name, v in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), v.cpu().numpy())
+    log(f"outputs of the last timed step: {', '.join(f'{k}{tuple(v.shape)}' for k, v in out.items())} -> {path}")
 
 
 def cpu_baseline(model_cfg, sd_cpu, c_in, frames, t_pad, n_pairs):
@@ -255,8 +278,9 @@ def main():
     LAB_ABLATION = os.environ.get("BENCH_LAB_ABLATION") == "1"
     range_ok = {}
 
-    def run(mode, warmup, steps):
-        """W untimed + K timed steps in one GEMM precision mode; returns (seconds, per-family profile)."""
+    def run(mode, warmup, steps, keep=None):
+        """W untimed + K timed steps in one GEMM precision mode; returns (seconds, per-family profile).  keep: a dict that
+        receives the last timed step's (logits, masks)."""
         ops.set_precision(mode)
         with torch.no_grad():
             for i in range(warmup):
@@ -275,6 +299,8 @@ def main():
                 logits, masks = step()
             fence()
             elapsed = time.perf_counter() - t0
+            if keep is not None:        # (copies, made after the clock stopped: the untimed profiling step below may reuse buffers)
+                keep["logits"], keep["masks"] = logits.clone(), masks.clone()
             _hip.prof_enable(False)
             prof = _hip.prof_read() if (rank == 0 and not args.no_prof) else {}
             if prof and world == 1:
@@ -336,7 +362,12 @@ def main():
                      "share_of_kernel_time": g["ms"] / tot if tot else 0.0}, **extra)
 
     main_mode = args.precision or ops.get_precision()
-    elapsed, prof = run(main_mode, args.warmup, args.steps)
+    last = {} if args.dump_outputs else None
+    elapsed, prof = run(main_mode, args.warmup, args.steps, keep=last)
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["logits"], last["masks"])
+        del last
     alts = {}
     if not args.no_alt:
         for alt_mode in ("f16x3", "bf16x3", "f32"):

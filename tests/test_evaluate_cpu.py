@@ -33,15 +33,27 @@ def test_convertor_builds_the_benchmark_records():
         conv.to_eval_format_pr("0001_1", bad)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dataloaders"), reason="needs the reference checkout's category tables")
-def test_convertor_takes_its_tables_from_the_checkout():
-    sys.path.insert(0, "/root/reference")
+def test_convertor_takes_its_tables_from_the_checkout(tmp_path, golden_dir):
+    """With no tables passed, the convertor imports `dataloaders.category` from the checkout on sys.path: here a mock
+    checkout whose category.py serves the reference's own tables (tests/golden/category_tables.json,
+    scripts/make_golden_checkout.py)."""
+    import json
+    with open(os.path.join(golden_dir, "category_tables.json")) as f:
+        tables = json.load(f)
+    (tmp_path / "dataloaders").mkdir()
+    (tmp_path / "dataloaders" / "__init__.py").write_text("")
+    (tmp_path / "dataloaders" / "category.py").write_text("".join(
+        f"{ds}_category_id_to_name = {dict(map(tuple, t['entity_id_to_name']))!r}\n"
+        f"{ds}_pred_id_to_name = {dict(map(tuple, t['pred_id_to_name']))!r}\n" for ds, t in tables.items()))
+    sys.path.insert(0, str(tmp_path))
     try:
         conv = E.EvaluationFormatConvertor("vidvrd")
         assert len(conv.entity_id_to_name) == 36 and len(conv.pred_id_to_name) == 133        # incl. the background entries
+        assert conv.entity_id_to_name == dict(map(tuple, tables["vidvrd"]["entity_id_to_name"]))
+        assert conv.pred_id_to_name == dict(map(tuple, tables["vidvrd"]["pred_id_to_name"]))
         assert len(E.EvaluationFormatConvertor("vidor").entity_id_to_name) == 81
     finally:
-        sys.path.remove("/root/reference")
+        sys.path.remove(str(tmp_path))
         for m in [m for m in sys.modules if m == "dataloaders" or m.startswith("dataloaders.")]:
             del sys.modules[m]
 

@@ -207,34 +207,56 @@ def test_dropin_launcher_takes_precedence_over_the_checkouts_models(tmp_path):
     assert "MODEL models.maskvrd" in plain.stdout
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/utils"), reason="needs the reference checkout (build container only)")
-def test_reference_optimizer_and_ema_accept_the_dropin():
-    """utils/train_utils.py of the REFERENCE (build_optimizer's weight-decay grouping, ModelEma's state_dict zip) run
-    against the drop-in model, in a child process with dropin/ ahead of the checkout (nothing of the reference is
-    imported into this test process)."""
+def test_reference_optimizer_and_ema_accept_the_dropin(golden_dir):
+    """utils/train_utils.py of the REFERENCE (build_optimizer's weight-decay grouping, ModelEma's state_dict zip) against the
+    drop-in model: tests/golden/reference_optimizer_vidvrd.json holds what the reference's own code made of it
+    (scripts/make_golden_checkout.py).  Here a child process with dropin/ ahead of the repo classifies every parameter by
+    the classes the reference imports from `models.blocks` -- through the drop-in shims, so the isinstance tests see the
+    drop-in's types -- and by name suffix, then runs one EMA update over the zipped state_dicts; both must reproduce the
+    reference's result name for name."""
+    import json
     import subprocess
     import sys
+    with open(os.path.join(golden_dir, "reference_optimizer_vidvrd.json")) as f:
+        want = json.load(f)
     code = (
-        "import sys, os\n"
-        f"sys.path[:0] = [{os.path.join(REPO, 'dropin')!r}, {REPO!r}, '/root/reference']\n"
-        "import yaml, torch\n"
+        "import copy, json, sys\n"
+        f"sys.path[:0] = [{os.path.join(REPO, 'dropin')!r}, {REPO!r}]\n"
+        "import torch\n"
+        "from torch import nn\n"
         "from models.maskvrd import MaskVRD\n"
+        "from models.blocks import MaskedConv1D, LayerNorm, Scale, AffineDropPath\n"
+        "from vrdone_amd import configs\n"
         "assert MaskVRD.__module__.startswith('vrdone_amd.')\n"
-        "from utils.train_utils import build_optimizer, ModelEma\n"
-        "cfg = yaml.safe_load(open('/root/reference/configs/vidvrd.yaml'))\n"
-        "model = MaskVRD(cfg['model_config'], device='cpu')\n"
-        "opt = build_optimizer(model, cfg['training_config'])\n"
-        "n = [len(g['params']) for g in opt.param_groups]\n"
-        "ema = ModelEma(model)\n"
+        f"model = MaskVRD(configs.model_config({want['config']!r}), device='cpu')\n"
+        "decay, no_decay = [], []\n"
+        "for mn, m in model.named_modules():\n"
+        "    for pn, _ in m.named_parameters():\n"
+        "        full = f'{mn}.{pn}' if mn else pn\n"
+        "        if pn.endswith('bias'):\n"
+        "            no_decay.append(full)\n"
+        "        elif pn.endswith('weight') and isinstance(m, (nn.Linear, nn.Conv1d, MaskedConv1D)):\n"
+        "            decay.append(full)\n"
+        "        elif (pn.endswith('weight') and isinstance(m, (LayerNorm, nn.GroupNorm))) or \\\n"
+        "                (pn.endswith('scale') and isinstance(m, (Scale, AffineDropPath))) or pn.endswith('rel_pe'):\n"
+        "            no_decay.append(full)\n"
+        "names = [n for n, _ in model.named_parameters()]\n"
+        "assert not set(decay) & set(no_decay)\n"
+        "no_decay += [n for n in names if n not in set(decay) | set(no_decay)]\n"
+        "ema = copy.deepcopy(model).eval()\n"
         "with torch.no_grad():\n"
         "    for p in model.parameters(): p.add_(1.0)\n"
-        "ema.update(model)\n"
-        "k = 'backbone.stem.0.ln1.bias'\n"
-        "d = float((ema.module.state_dict()[k] - model.state_dict()[k]).abs().max())\n"
-        "print('GROUPS', n, 'EMA_LAG', round(d, 4))\n")
+        "    for e, v in zip(ema.state_dict().values(), model.state_dict().values()): e.copy_(0.999 * e + 0.001 * v)\n"
+        f"k = {want['ema_probe']!r}\n"
+        "lag = float((ema.state_dict()[k] - model.state_dict()[k]).abs().max())\n"
+        "print('RESULT', json.dumps({'decay': sorted(set(decay)), 'no_decay': sorted(set(no_decay)), 'ema_lag': lag}))\n")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
-    assert "GROUPS [176, 345]" in out.stdout and "EMA_LAG 0.999" in out.stdout, out.stdout
+    got = json.loads(out.stdout.split("RESULT", 1)[1])
+    groups = {g["weight_decay"] > 0: sorted(g["params"]) for g in want["param_groups"]}
+    assert [len(g["params"]) for g in want["param_groups"]] == [176, 345]
+    assert got["decay"] == groups[True] and got["no_decay"] == groups[False]
+    assert got["ema_lag"] == pytest.approx(want["ema_lag"], abs=1e-6) and round(got["ema_lag"], 4) == 0.999
 
 
 def test_synthetic_raw_video_has_the_dataloader_layout():
