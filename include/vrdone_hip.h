@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VRD_ABI_VERSION 34
+#define VRD_ABI_VERSION 35
 
 enum vrd_act { VRD_ACT_NONE = 0, VRD_ACT_RELU = 1, VRD_ACT_GELU = 2 };
 
@@ -125,7 +125,8 @@ int vrd_pack_pairs(const vrd_pack_args* a, void* stream);
  * frame t being row s_row[p] + t*stride of the subject's arrays and o_row[p] + t*stride of the object's (the dataloader's
  * feat[start_offset::feat_stride] slicing, :678-692).  Writes the same operand buffers as vrd_pack_pairs (zero rows for
  * t >= lens[p]); so_box = the 5 subject-object box features, ent = the 8 entity box features of subject then object rows
- * (boxes normalised by the frame size w x h, first differences along the sub-sampled frames).
+ * (boxes normalised by the frame size w x h -- or seq_wh[p] for sequence p, same arithmetic -- first differences along the
+ * sub-sampled frames).
  * out_vis == NULL: only the box features are written (the wide rows then come from vrd_assemble_pairs). */
 typedef struct {
     const float* vis;
@@ -141,6 +142,7 @@ typedef struct {
     float* out_so_box;
     float* out_ent;
     int32_t pair_wide;      /* enum vrd_pair_format of out_vis / out_clip */
+    const float* seq_wh;    /* (P, 2) w, h per gathered sequence (the pairs of several videos in one call), or NULL: w, h */
 } vrd_gather_args;
 int vrd_gather_pairs(const vrd_gather_args* a, void* stream);
 
@@ -379,6 +381,33 @@ int vrd_postprocess(const float* logits, const float* masks, const int32_t* vali
                     int P, int Q, int K1, int T, int topk,
                     float* top_score, int32_t* top_cat, int32_t* seg_first, int32_t* seg_last,
                     void* stream);
+
+/* ---- segmented triplet selection, models/maskvrd.py forward_test (reference maskvrd.py:247-300) -------------------------
+ * The candidate filter and top-n_max_pair selection of forward_test for n_videos videos in one launch (one workgroup per video).
+ * cand: (P_total, Q, 2k + 2) records of MaskVRD.pair_candidates [k top scores | k classes | first | last frame] (ints bit-cast),
+ * video v's pairs being rows video_pairs[v] .. video_pairs[v + 1] - 1 in that video's own pair order.  Per pair: s_score /
+ * o_score = the subject's / object's category score, so_offset, so_start / so_end = the pair's shared frames [start, end).
+ * Candidate i = (pair * Q + query) * k + rank of a video is kept when last >= 0 and (last - first) * feat_stride + 1 >=
+ * pred_min_frames; its score is mean(s_score, top score, o_score), bit for bit torch's GPU mean of the three.  Per video:
+ *   out_count[2v] = number selected (min(kept, n_max_pair)), out_count[2v + 1] = kept candidates whose frames fall outside
+ *   [0, so_end - so_start) (forward_test asserts there are none);
+ *   out_index[v, j] = the j-th selected candidate index (descending score, ties to the lower index), -1 behind the count;
+ *   out_score[v, j] = its score (out_score may be NULL).
+ * max_video_pairs: the most pairs of any one video (bounds the 32-bit candidate indices); n_max_pair <= 4096. */
+typedef struct {
+    const float* cand;
+    const float* s_score;
+    const float* o_score;
+    const int32_t* so_offset;
+    const int32_t* so_start;
+    const int32_t* so_end;
+    const int32_t* video_pairs;     /* (n_videos + 1) pair offsets, device */
+    int32_t n_videos, max_video_pairs, Q, k, feat_stride, pred_min_frames, n_max_pair;
+    int32_t* out_count;             /* (n_videos, 2) */
+    int32_t* out_index;             /* (n_videos, n_max_pair) */
+    float* out_score;               /* (n_videos, n_max_pair) or NULL */
+} vrd_select_args;
+int vrd_select_triplets(const vrd_select_args* a, void* stream);
 
 /* ====================================================================================================================
  * Backward kernels (training step: the reference differentiates its ATen graph with autograd, train.py:186;

@@ -126,7 +126,15 @@ class GatherArgs(C.Structure):
                 ("lens", C.c_void_p), ("P", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("Cc", C.c_int32),
                 ("stride", C.c_int32), ("w", C.c_float), ("h", C.c_float),
                 ("out_vis", c_f32p), ("out_clip", c_f32p), ("out_so_box", c_f32p), ("out_ent", c_f32p),
-                ("pair_wide", C.c_int32)]
+                ("pair_wide", C.c_int32), ("seq_wh", c_f32p)]
+
+
+class SelectArgs(C.Structure):                        # vrd_select_args
+    _fields_ = [("cand", c_f32p), ("s_score", c_f32p), ("o_score", c_f32p), ("so_offset", c_i32p), ("so_start", c_i32p),
+                ("so_end", c_i32p), ("video_pairs", c_i32p),
+                ("n_videos", C.c_int32), ("max_video_pairs", C.c_int32), ("Q", C.c_int32), ("k", C.c_int32),
+                ("feat_stride", C.c_int32), ("pred_min_frames", C.c_int32), ("n_max_pair", C.c_int32),
+                ("out_count", c_i32p), ("out_index", c_i32p), ("out_score", c_f32p)]
 
 
 class AssembleArgs(C.Structure):
@@ -175,6 +183,7 @@ _SIGNATURES = {
                                 C.c_float, c_f32p, C.c_void_p]),
     "vrd_postprocess": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_i32p,
                                   c_i32p, c_i32p, C.c_void_p]),
+    "vrd_select_triplets": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),
     # ---- backward kernels (training step)
     "vrd_gemm_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                  c_f32p, C.c_void_p]),
@@ -210,7 +219,7 @@ _SIGNATURES = {
                                   C.c_void_p]),
 }
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 
 class HipLibraryError(RuntimeError):

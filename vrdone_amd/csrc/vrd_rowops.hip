@@ -132,7 +132,9 @@ __global__ __launch_bounds__(256) void pack_pairs_kernel(vrd_pack_args a, unsign
 // backbone's channels-last operand buffers exactly like pack_pairs_kernel.  Frame t of pair p is row
 // s_row[p] + t * stride (o_row[p] + t * stride) of the concatenated arrays.
 // Box arithmetic is written operation by operation with the round-to-nearest intrinsics (no FMA contraction), in the
-// reference's order, so everything but the three logarithms is the reference's f32 value bit for bit.
+// reference's order, so everything but the three logarithms is the reference's f32 value bit for bit.  With a frame-size table
+// (seq_wh) sequence p normalises by its own video's w, h: the pairs of several videos gathered in one launch get the values
+// each would get gathered alone.
 // ------------------------------------------------------------------------------------------
 struct Box4 {
     float x0, y0, x1, y1;
@@ -216,7 +218,8 @@ __global__ __launch_bounds__(256) void gather_pairs_kernel(vrd_gather_args a, un
         so[4] = logf(__fdiv_rn(__fmul_rn(s_w, s_h), __fmul_rn(o_w, o_h)));
     } else if (lane == 1 || lane == 2) {
         float f[8];
-        entity_feats(a.boxes, lane == 1 ? a.s_row[p] : a.o_row[p], a.stride, t, n, a.w, a.h, f);
+        const float w = a.seq_wh ? a.seq_wh[2 * (int64_t)p] : a.w, h = a.seq_wh ? a.seq_wh[2 * (int64_t)p + 1] : a.h;
+        entity_feats(a.boxes, lane == 1 ? a.s_row[p] : a.o_row[p], a.stride, t, n, w, h, f);
         float* const dst = lane == 1 ? es : eo;
 #pragma unroll
         for (int i = 0; i < 8; ++i) dst[i] = f[i];

@@ -203,3 +203,33 @@ def eval_relation(dataset_type, prediction_results=None, json_results_path=None,
     result.update({f"RelDet_AR@{k}": v for k, v in rec_at_n.items()})
     result.update({f"RelTag_AP@{k}": v for k, v in mprec_at_n.items()})
     return result
+
+
+def batched_forward_test(model, proposals, max_videos=16, max_pairs=4096):
+    """The reference's eval loop (eval.py:136-150: one `model(proposal)` per video) over groups of videos: consecutive
+    proposals are grouped until `max_videos` videos or `max_pairs` pairs (a group holds at least one video) and evaluated with
+    ONE `model.forward_test_videos` call each.  Yields (proposal, result) in input order; result is what
+    `model(proposal)` returns (None for a video without triplets).  Empty proposals ({} / None, which eval.py skips) pass
+    through with a None result and take no place in a group."""
+    if max_videos < 1 or max_pairs < 1:
+        raise ValueError("batched_forward_test: max_videos and max_pairs must be >= 1")
+    group, n_pairs = [], 0
+
+    def pairs(p):
+        return len(p["sids"])
+
+    def flush():
+        results = model.forward_test_videos([p for p in group if p]) if any(group) else []
+        it = iter(results)
+        for p in group:
+            yield p, (next(it) if p else None)
+
+    for p in proposals:
+        if p and group and (sum(1 for q in group if q) >= max_videos or n_pairs + pairs(p) > max_pairs):
+            yield from flush()
+            group, n_pairs = [], 0
+        group.append(p)
+        if p:
+            n_pairs += pairs(p)
+    if group:
+        yield from flush()

@@ -670,6 +670,12 @@ class MaskVRD(nn.Module):
         length, valid length, index): every padded length then is ONE batch (short pairs of all slices share
         max_seq_len), and dealing that order round-robin gives every rank of a sharded run the same mix of lengths.
         Returns (order: list of pair ids, t_pad: padded length per pair id)."""
+        # (the reference's padded length of every pair; then the shortest ones that give the same results: `tight padding`)
+        t_pad = self.tight_buckets(lens, self._reference_pad(lens), self.ROWS_MIN_ROWS if self._eval_rows_form(len(lens)) else None)
+        return sorted(range(len(lens)), key=lambda i: (t_pad[i], lens[i], i)), t_pad
+
+    def _reference_pad(self, lens):
+        """The padded length the reference gives each pair of one video: max_seq_len, or its max_so_pair slice's longest rounded up."""
         P, d = len(lens), self.max_div_factor
         t_pad = [0] * P
         for s0 in range(0, P, self.max_so_pair):
@@ -677,9 +683,7 @@ class MaskVRD(nn.Module):
             t_long = (max([lens[i] for i in sl] + [self.max_seq_len]) + d - 1) // d * d
             for i in sl:
                 t_pad[i] = self.max_seq_len if lens[i] <= self.max_seq_len else t_long
-        # (the reference's padded length of every pair; then the shortest ones that give the same results: `tight padding`)
-        t_pad = self.tight_buckets(lens, t_pad, self.ROWS_MIN_ROWS if self._eval_rows_form(P) else None)
-        return sorted(range(P), key=lambda i: (t_pad[i], lens[i], i)), t_pad
+        return t_pad
 
     def _entity_streams(self, source, ids):
         """The backbone's entity stage run ONCE PER TRACKLET (per sub-sampling phase) for the pairs `ids` of a
@@ -699,6 +703,8 @@ class MaskVRD(nn.Module):
         Ts = -(-int(length.max()) // unit) * unit
         stream_row = torch.from_numpy(stream.astype(np.int64) * Ts + j0).to(dev)       # uploads first, kernels after
         starts, lengths = torch.from_numpy(start).to(dev), torch.from_numpy(length).to(dev)
+        wh = source.rows_wh(start)                             # (a source of several videos: each stream's own frame size)
+        wh = None if wh is None else torch.from_numpy(wh).to(dev)
         n = len(start)
         D = bb.s_fuse_norm.num_channels
         rows = torch.empty(n, Ts, D, device=dev, dtype=torch.float32)
@@ -707,7 +713,7 @@ class MaskVRD(nn.Module):
             c1 = min(c0 + step, n)
             # (the gather writes a subject and an object half; a stream is both)
             vis, clip, _, ent, m = ops.gather_rows(source, starts[c0:c1], starts[c0:c1], lengths[c0:c1], Ts, bb.n_bbox_so,
-                                                   bb.n_bbox_entity, ops.pair_mode())
+                                                   bb.n_bbox_entity, ops.pair_mode(), seq_wh=None if wh is None else wh[c0:c1])
             h = c1 - c0
             rows[c0:c1] = bb.entity_stage(vis[:h], clip[:h] if clip is not None else None, ent[:h], m)
         piece = -(-2 * reach // chunk) * chunk
@@ -729,8 +735,9 @@ class MaskVRD(nn.Module):
         piece_s = torch.cat([s_row, s_row + tail])                  # [start pieces | end pieces]
         piece_o = torch.cat([o_row, o_row + tail])
         piece_len = torch.cat([lens.clamp(max=piece), end_len])
+        wh = source.pair_wh_of(sel)
         vis, clip, _, ent, m = ops.gather_rows(source, piece_s, piece_o, piece_len, L, bb.n_bbox_so, bb.n_bbox_entity,
-                                               ops.pair_mode())
+                                               ops.pair_mode(), seq_wh=None if wh is None else torch.cat([wh, wh]))
         return bb.entity_stage(vis, clip, ent, torch.cat([m, m], dim=0))                   # (4B, L, D)
 
     def _shared_entity_rows(self, source, sel, shared, at, T, pieces=None):
@@ -746,7 +753,7 @@ class MaskVRD(nn.Module):
         if pieces is None:
             pieces = self._shared_pieces(source, sel, shared, T)
         _, _, so_box, _, mask = ops.gather_rows(source, s_row.contiguous(), o_row.contiguous(), lens, T, bb.n_bbox_so,
-                                                bb.n_bbox_entity, False, boxes_only=True)
+                                                bb.n_bbox_entity, False, boxes_only=True, seq_wh=source.pair_wh_of(sel))
         so = ops.assemble_pairs(rows, pieces, stream_row[:, at:at + B].reshape(-1), lens, T, piece, reach)
         return so, so_box, mask
 
@@ -1034,10 +1041,23 @@ class MaskVRD(nn.Module):
                             so_start[pp] + st, so_start[pp] + en,
                             so_start[pp] - durs[sel_s, 0] + st, so_start[pp] - durs[sel_o, 0] + st, en - st],
                            dim=1).cpu().tolist()
+        so_trajs = self._so_trajs(input_data['bboxes_list'], host)
+        return {
+            "triplets": [r[2:5] for r in host],
+            "triple_scores": tri[order].cpu().tolist(),
+            "triple_scores_avg": avg[order].cpu().tolist(),
+            "so_trajs": so_trajs,
+            "pred_durations": [r[5:7] for r in host],
+            "so_tids": [r[0:2] for r in host],
+        }
+
+    @staticmethod
+    def _so_trajs(boxes, host):
+        """The box tracks of the winners `host` (rows [subject, object, .., .., .., .., .., subject's first box, object's first
+        box, frames]) from the video's per-tracklet boxes."""
         # box tracks of the winners: every tracklet that appears is copied to the host ONCE (one concatenation, one
         # copy); each triplet then converts its slice of the host array to fresh Python lists.  The reference slices
         # and .tolist()s two device tensors per triplet (maskvrd.py:302-306): 400 device round trips.
-        boxes = input_data['bboxes_list']
         used = sorted({r[0] for r in host} | {r[1] for r in host})
         flat = torch.cat([boxes[t] for t in used], dim=0).cpu().numpy()
         rows_of, at = {}, 0
@@ -1058,11 +1078,137 @@ class MaskVRD(nn.Module):
         finally:
             if gc_was_on:
                 gc.enable()
-        return {
-            "triplets": [r[2:5] for r in host],
-            "triple_scores": tri[order].cpu().tolist(),
-            "triple_scores_avg": avg[order].cpu().tolist(),
-            "so_trajs": so_trajs,
-            "pred_durations": [r[5:7] for r in host],
-            "so_tids": [r[0:2] for r in host],
-        }
+        return so_trajs
+
+    @torch.no_grad()
+    def forward_test_videos(self, videos):
+        """forward_test for a list of videos in one pass: item i of the result is what forward_test(videos[i]) returns (None
+        for a video without a triplet, or for an empty / None entry).  The pairs of all videos run through the network as one
+        batch -- a pair's outputs depend only on its own padded length (tight padding), and every pair keeps the reference's
+        padded length of its own video's max_so_pair slice -- then one vrd_select_triplets launch picks every video's
+        top-n_max_pair triplets and the winners of all videos come to the host in one copy.  The videos come in one form:
+        `pair_source`, its plain-tensor fields, or `so_features_list`.  Eval launches cost the same for 50 pairs as for a few
+        hundred: evaluating a few dozen small videos per call is what this is for (vrdone_amd.evaluate.batched_forward_test)."""
+        import numpy as np
+        if getattr(self, "_shard", None):
+            raise NotImplementedError("forward_test_videos: a multi-video call does not shard its pairs over ranks; call "
+                                      "forward_test per video after shard_pairs(), or shard_pairs(enable=False)")
+        videos = list(videos)
+        results = [None] * len(videos)
+        live = [i for i, v in enumerate(videos) if v]
+        if not live:
+            return results
+        form = {("source" if "pair_source" in videos[i] else "fields" if "tracklet_visual" in videos[i] else "feats") for i in live}
+        if len(form) > 1:
+            raise ValueError("forward_test_videos: the videos of one call must come in one form (pair_source, its plain-tensor "
+                             "fields, or so_features_list)")
+        form = form.pop()
+        dev = self.device
+        Q, k = self.predictor.num_queries, self.topk
+        if form == "feats":
+            source = None
+            feats = [f for i in live for f in videos[i]['so_features_list']]
+            lens_v = [[int(f.shape[1]) for f in videos[i]['so_features_list']] for i in live]
+        else:
+            from ..proposals import PairSource
+            srcs = [videos[i]['pair_source'] if form == "source" else PairSource.from_fields(videos[i], dev) for i in live]
+            source, feats = PairSource.concat(srcs), None
+            lens_v = [list(s.lens) for s in srcs]
+        counts = [len(lv) for lv in lens_v]
+        lens = [L for lv in lens_v for L in lv]
+        P = len(lens)
+        # the reference's padded lengths video by video, then one tight-padding plan over all pairs of the call
+        t_pad = self.tight_buckets(lens, [t for lv in lens_v for t in self._reference_pad(lv)],
+                                   self.ROWS_MIN_ROWS if self._eval_rows_form(P) else None)
+        order = sorted(range(P), key=lambda i: (t_pad[i], lens[i], i))
+
+        # per-pair tables on the host, in one upload: [s score | o score | so_offset | so_start | so_end | video pair offsets]
+        base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        table = np.zeros(5 * P + len(live) + 1, dtype=np.int32)
+        scores = table[:2 * P].view(np.float32)
+        host_in = []
+        for j, i in enumerate(live):
+            d = videos[i]
+            h = lambda t: torch.as_tensor(t).cpu().numpy()          # noqa: E731
+            sids, oids = h(d['sids']).astype(np.int64), h(d['oids']).astype(np.int64)
+            assert len(sids) == counts[j]
+            durs, cat_scores = h(d['traj_durations']).astype(np.int64), h(d['cat_scores']).astype(np.float32)
+            so_start = np.maximum(durs[sids, 0], durs[oids, 0])
+            so_end = np.minimum(durs[sids, 1], durs[oids, 1])
+            offs = h(d['so_offset']).astype(np.int64)
+            a, b = base[j], base[j + 1]
+            scores[a:b], scores[P + a:P + b] = cat_scores[sids], cat_scores[oids]
+            table[2 * P + a:2 * P + b], table[3 * P + a:3 * P + b], table[4 * P + a:4 * P + b] = offs, so_start, so_end
+            host_in.append((sids, oids, durs, cat_scores, h(d['cat_ids']).astype(np.int64), offs, so_start))
+        table[5 * P:] = base
+        unsort = np.empty(P, dtype=np.int64)
+        unsort[np.asarray(order, dtype=np.int64)] = np.arange(P)
+        table_dev = torch.from_numpy(table).to(dev)              # uploaded before the first kernel is queued
+        unsort_dev = torch.from_numpy(unsort).to(dev)
+        f_dev = table_dev[:2 * P].view(torch.float32)
+
+        ops = _ops()
+        f16 = ops.get_precision() == "f16x3"
+        if f16:
+            flag = ops.f16_range_flag(next(self.parameters()).device)
+            flag.zero_()
+        cand = self.pair_candidates(feats, lens, order, t_pad, k, source=source)[unsort_dev]     # each video's own pair order
+        ints = cand.view(torch.int32)
+        vp = table_dev[5 * P:]
+        count, index, score = ops.select_triplets(cand, f_dev[:P], f_dev[P:], table_dev[2 * P:3 * P], table_dev[3 * P:4 * P],
+                                                  table_dev[4 * P:5 * P], vp, self.feat_stride, self.pred_min_frames,
+                                                  self.n_max_pair, max(counts))
+        # the winners' record fields, all videos at once: pair row, query, rank -> score, class, first, last frame
+        idx = index.clamp(min=0).long()
+        row = (vp[:-1, None].long() + idx // (Q * k)) * Q + (idx // k) % Q
+        rank = (idx % k)[..., None]
+        rec = ints.view(P * Q, 2 * k + 2)[row]                                                 # (V, n_max_pair, 2k + 2)
+        fields = [count.reshape(-1), index.reshape(-1), rec.gather(-1, rank).reshape(-1), rec.gather(-1, rank + k).reshape(-1),
+                  rec[..., 2 * k].reshape(-1), rec[..., 2 * k + 1].reshape(-1), score.view(torch.int32).reshape(-1)]
+        if f16:
+            # the range flag, and whether any score is not finite (forward_test's test for a repeat in f32)
+            fields.append(flag.reshape(-1).to(torch.int32))
+            fields.append((~torch.isfinite(cand[:, :, :k])).any().reshape(1).to(torch.int32))
+        host = torch.cat(fields).cpu().numpy()
+        V, N = len(live), self.n_max_pair
+        if f16 and (host[-2] != 0 or host[-1] != 0):
+            import warnings
+            warnings.warn("vrdone_amd: an activation beyond the f16x3 mode's operand range (or non-finite inputs) in a "
+                          "multi-video call: repeating its videos one by one")
+            for i in live:
+                results[i] = self.forward_test(videos[i])
+            return results
+        at = 0
+
+        def take(n, dtype=np.int32):
+            nonlocal at
+            out = host[at:at + n].view(dtype)
+            at += n
+            return out
+        cnt = take(2 * V).reshape(V, 2)
+        sel, p_score, p_cat = take(V * N).reshape(V, N), take(V * N, np.float32).reshape(V, N), take(V * N).reshape(V, N)
+        first, last, avg = take(V * N).reshape(V, N), take(V * N).reshape(V, N), take(V * N, np.float32).reshape(V, N)
+        assert not cnt[:, 1].any() and (cnt[:, 0] >= 0).all(), "a kept candidate lies outside its pair's shared frames"
+        for j, i in enumerate(live):
+            n = int(cnt[j, 0])
+            if n == 0:
+                continue
+            sids, oids, durs, cat_scores, cat_ids, offs, so_start = host_in[j]
+            fl = sel[j, :n].astype(np.int64)
+            pp = fl // (Q * k)
+            sel_s, sel_o = sids[pp], oids[pp]
+            st = first[j, :n].astype(np.int64) * self.feat_stride + offs[pp]
+            en = last[j, :n].astype(np.int64) * self.feat_stride + offs[pp] + 1
+            rows = np.stack([sel_s, sel_o, cat_ids[sel_s], p_cat[j, :n].astype(np.int64), cat_ids[sel_o],
+                             so_start[pp] + st, so_start[pp] + en,
+                             so_start[pp] - durs[sel_s, 0] + st, so_start[pp] - durs[sel_o, 0] + st, en - st], axis=1).tolist()
+            tri = np.stack([cat_scores[sel_s], p_score[j, :n], cat_scores[sel_o]], axis=1)
+            results[i] = {
+                "triplets": [r[2:5] for r in rows],
+                "triple_scores": tri.tolist(),
+                "triple_scores_avg": avg[j, :n].tolist(),
+                "so_trajs": self._so_trajs(videos[i]['bboxes_list'], rows),
+                "pred_durations": [r[5:7] for r in rows],
+                "so_tids": [r[0:2] for r in rows],
+            }
+        return results

@@ -518,13 +518,15 @@ def gather_pairs(source, sel, T, S, E, pair_wide):
     the backbone's operand buffers, computing the box features on the way (vrd_gather_pairs).
     Returns (vis, clip or None, so_box, ent, mask) like pack_pairs."""
     return gather_rows(source, source.s_row[sel].contiguous(), source.o_row[sel].contiguous(), source.lens_dev[sel].contiguous(),
-                       T, S, E, pair_wide)
+                       T, S, E, pair_wide, seq_wh=source.pair_wh_of(sel))
 
 
-def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False):
+def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False, seq_wh=None):
     """gather_pairs for explicit tables: sequence p = lens[p] frames starting at rows s_row[p] (subject half of the
     outputs) and o_row[p] (object half) of the source's per-tracklet arrays, stepping by the source's stride.
-    boxes_only: the wide visual / clip rows are not gathered (returned as None)."""
+    boxes_only: the wide visual / clip rows are not gathered (returned as None).
+    seq_wh: (B, 2) float32 device frame size per sequence (a source of several videos, PairSource.concat), else the
+    source's one frame size."""
     assert S == 5 and E == 8, "the reference's box features are 5 (pair) + 8 (entity) channels (utils/misc.py:158-217)"
     B = lens.shape[0]
     dev = source.vis.device
@@ -541,6 +543,9 @@ def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False
     a.w, a.h = source.wh
     a.out_vis, a.out_clip, a.out_so_box, a.out_ent = _ptr(vis), _ptr(clip), so_box.data_ptr(), ent.data_ptr()
     a.pair_wide = _fmt(pair_wide)
+    if seq_wh is not None:
+        assert seq_wh.dtype == torch.float32 and seq_wh.shape == (B, 2) and seq_wh.is_contiguous() and seq_wh.device == dev
+        a.seq_wh = seq_wh.data_ptr()
     _hip.check(lib.vrd_gather_pairs(C.byref(a), _stream()), "vrd_gather_pairs")
     mask = torch.arange(T, device=dev)[None, :] < lens[:, None]
     if a.pair_wide and not boxes_only:
@@ -1017,3 +1022,33 @@ def postprocess(logits, masks, valid_len, topk):
                                    ts.data_ptr(), tc.data_ptr(), sf.data_ptr(), sl.data_ptr(), _stream()),
                "vrd_postprocess")
     return ts, tc, sf, sl
+
+
+def select_triplets(cand, s_score, o_score, so_offset, so_start, so_end, video_pairs, feat_stride, pred_min_frames, n_max_pair,
+                    max_video_pairs):
+    """forward_test's candidate filter + top-n_max_pair selection for several videos in one launch (vrd_select_triplets).
+    cand (P_total, Q, 2k + 2) f32 candidate records; s_score / o_score (P_total,) f32; so_offset / so_start / so_end
+    (P_total,) int32; video_pairs (n_videos + 1,) int32 pair offsets -- all on the device.  Returns (count (n_videos, 2) int32
+    = [selected, out-of-range kept candidates], index (n_videos, n_max_pair) int32 flat candidate index within the video
+    (-1 padded), score (n_videos, n_max_pair) f32)."""
+    P, Q, W = cand.shape
+    k = (W - 2) // 2
+    n_videos = video_pairs.shape[0] - 1
+    assert cand.is_contiguous() and cand.dtype == torch.float32 and W == 2 * k + 2 and n_videos >= 1
+    for t in (s_score, o_score):
+        assert t.dtype == torch.float32 and t.shape == (P,) and t.is_contiguous()
+    for t in (so_offset, so_start, so_end):
+        assert t.dtype == torch.int32 and t.shape == (P,) and t.is_contiguous()
+    assert video_pairs.dtype == torch.int32 and video_pairs.is_contiguous()
+    dev = cand.device
+    count = torch.empty(n_videos, 2, device=dev, dtype=torch.int32)
+    index = torch.empty(n_videos, n_max_pair, device=dev, dtype=torch.int32)
+    score = torch.empty(n_videos, n_max_pair, device=dev, dtype=torch.float32)
+    a = _hip.SelectArgs()
+    a.cand, a.s_score, a.o_score = cand.data_ptr(), s_score.data_ptr(), o_score.data_ptr()
+    a.so_offset, a.so_start, a.so_end, a.video_pairs = so_offset.data_ptr(), so_start.data_ptr(), so_end.data_ptr(), video_pairs.data_ptr()
+    a.n_videos, a.max_video_pairs, a.Q, a.k = n_videos, max_video_pairs, Q, k
+    a.feat_stride, a.pred_min_frames, a.n_max_pair = feat_stride, pred_min_frames, n_max_pair
+    a.out_count, a.out_index, a.out_score = count.data_ptr(), index.data_ptr(), score.data_ptr()
+    _hip.check(lib.vrd_select_triplets(C.byref(a), _stream()), "vrd_select_triplets")
+    return count, index, score

@@ -31,6 +31,47 @@ class PairSource:
         # per-entity stage once per tracklet (stream_plan); None: pairs only
         self.first_row = None if first_row is None else np.asarray(first_row, dtype=np.int64)
         self._rows_host = None
+        # frame sizes of a source that holds several videos (concat): video j owns the tracklet rows [video_row[j],
+        # video_row[j + 1]) and its pairs' boxes are normalised by video_wh[j]; pair_wh (P, 2) on the device.  None: one video
+        self.video_row = self.video_wh = self.pair_wh = None
+
+    @classmethod
+    def concat(cls, sources):
+        """One source over the tracklets and pairs of several videos (MaskVRD.forward_test_videos): the tracklet rows one
+        after the other, every source's s_row / o_row / first_row moved by the rows in front of it, so that each tracklet,
+        stream and pair stays its own; and the per-pair / per-row frame-size tables the gathers normalise the boxes by."""
+        sources = list(sources)
+        assert sources, "PairSource.concat needs at least one source"
+        stride = sources[0].stride
+        if any(s.stride != stride for s in sources):
+            raise ValueError("PairSource.concat: the sources have different sub-sampling strides")
+        if len({s.clip is None for s in sources}) > 1 or len({(s.n_visual, s.n_clip) for s in sources}) > 1:
+            raise ValueError("PairSource.concat: the sources have different feature widths")
+        n_rows = [s.boxes.shape[0] for s in sources]
+        row0 = np.concatenate([[0], np.cumsum(n_rows)]).astype(np.int64)
+        first_row = None
+        if all(s.first_row is not None for s in sources):
+            first_row = np.concatenate([s.first_row[:-1] + r for s, r in zip(sources, row0[:-1])] + [row0[-1:]])
+        cat = lambda ts: torch.cat(ts, dim=0).contiguous()         # noqa: E731
+        out = cls(cat([s.vis for s in sources]), None if sources[0].clip is None else cat([s.clip for s in sources]),
+                  cat([s.boxes for s in sources]), cat([s.s_row + int(r) for s, r in zip(sources, row0[:-1])]),
+                  cat([s.o_row + int(r) for s, r in zip(sources, row0[:-1])]), cat([s.lens_dev for s in sources]), stride,
+                  sources[0].wh, first_row=first_row)
+        out.video_row = row0
+        out.video_wh = np.asarray([s.wh for s in sources], dtype=np.float32)
+        counts = [len(s) for s in sources]
+        out.pair_wh = torch.from_numpy(np.repeat(out.video_wh, counts, axis=0)).to(sources[0].boxes.device)
+        return out
+
+    def pair_wh_of(self, sel):
+        """(len(sel), 2) device frame sizes of the pairs `sel` (device indices), or None for a one-video source."""
+        return None if self.pair_wh is None else self.pair_wh[sel].contiguous()
+
+    def rows_wh(self, rows):
+        """(n, 2) float32 frame sizes of the videos that own the tracklet rows `rows` (numpy), or None for a one-video source."""
+        if self.video_wh is None:
+            return None
+        return self.video_wh[np.searchsorted(self.video_row, np.asarray(rows, dtype=np.int64), side="right") - 1]
 
     def __len__(self):
         return len(self.lens)
