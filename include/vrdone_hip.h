@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VRD_ABI_VERSION 35
+#define VRD_ABI_VERSION 36
 
 enum vrd_act { VRD_ACT_NONE = 0, VRD_ACT_RELU = 1, VRD_ACT_GELU = 2 };
 
@@ -45,7 +45,12 @@ enum vrd_act { VRD_ACT_NONE = 0, VRD_ACT_RELU = 1, VRD_ACT_GELU = 2 };
  *       1.0-1.3x the distance of the reference's own float32 run (tests/golden/mask_vrd_f64.npz).  e is the fixed
  *       VRD_F16_ACT_EXP for activations (|x| < 4094 representable; larger magnitudes come out as NaN, never as a
  *       silently wrong number) and a per-tensor power of two for weights (vrd_split_weight: max |w| * 2^e in
- *       [2^14, 2^15)); the GEMM epilogue multiplies the accumulator by the exact power of two that undoes both. */
+ *       [2^14, 2^15)); the GEMM epilogue multiplies the accumulator by the exact power of two that undoes both.
+ * One-product form ("f16x1", vrd_gemm_args.products = 1, vrd_attention_pair's `products` = 1; VRD_PAIR_F16 only): the same
+ *   operands, but only a_hi*w_hi is formed -- the lo planes are neither read nor multiplied.  ~11 significand bits per operand
+ *   (f16 rounding of the scaled values, subnormals kept); the global attention also rounds its probabilities once, as
+ *   f16(P * 2^VRD_F16_ACT_EXP).  An opt-in inference mode, NOT reference-grade: logits ~4e-3 from the reference (mask logits
+ *   ~5e-2), the same detections on the golden videos.  The range flag and its f32 repeat apply as in f16x3. */
 enum vrd_pair_format { VRD_PAIR_NONE = 0, VRD_PAIR_BF16 = 1, VRD_PAIR_F16 = 2 };
 #define VRD_F16_ACT_EXP 4
 
@@ -229,6 +234,11 @@ typedef struct {
                                (2^e, 2^-e), vrd_absmax_scale's output for A: the rows are split as f16 planes of A * 2^e instead
                                of A * 2^VRD_F16_ACT_EXP, for operands without a known range -- the gradients of the training
                                step's input-gradient GEMMs (the reference differentiates in float32, train.py:182-186) */
+    int32_t products;       /* MFMA products per split-precision operand pair: 0 or 3 = a_hi*w_hi + a_hi*w_lo + a_lo*w_hi (every
+                               mode so far); 1 = a_hi*w_hi only (f16x1; needs split_fmt == VRD_PAIR_F16 and W_split).  All three
+                               split-precision kernels form the same products in the same order in either form, so the choice of
+                               kernel never changes a bit.  A call that does not qualify for a split kernel runs exact f32
+                               products, as in the three-product form.  vrd_gemm_batch needs the same value in every entry. */
 } vrd_gemm_args;
 int vrd_gemm(const vrd_gemm_args* a, void* stream);
 /* `count` (1..4) GEMMs of an array of argument structs.  Problems that differ only in A, W / W_split, bias and C and
@@ -353,12 +363,14 @@ int vrd_attention(const float* q, int64_t ldq, const float* k, const float* v, i
 
 /* Same attention for pair-row q, k, v (split-precision modes; rows of width n_head*head_dim written by the projection
  * GEMMs with c_pair): both contractions as three 16-bit MFMA products, f32 softmax.  head_dim in {64, 128}.
+ * products: 0 or 3 as described; 1 (pair_fmt VRD_PAIR_F16 only) = q_hi*k_hi for the scores and p_hi*v_hi for the output, with
+ * p_hi = f16(P * 2^VRD_F16_ACT_EXP) of the f32 softmax probabilities P (the f16x1 mode).
  * pair_fmt: the format of q, k, v (VRD_PAIR_BF16 / VRD_PAIR_F16); out_pair: 0 or the same format.
  * q_mask (optional, B*Tq bytes): query rows the caller zeroes afterwards anyway (the output projection's row mask,
  * local_transformer.py:183); tiles of 32 queries without a valid one are not computed and read 0. */
 int vrd_attention_pair(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                        const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, int head_dim,
-                       float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream);
+                       float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream, int products);
 
 /* ---- MaxPool1d(3,2,1) skip * mask (models/blocks.py:1040-1046,1074) and mask[::2] ------- */
 int vrd_maxpool_mask(const float* x, int64_t ldx, int B, int Tin, int C, const uint8_t* mask_in,

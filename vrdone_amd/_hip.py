@@ -48,7 +48,7 @@ class GemmArgs(C.Structure):
                 ("res2", c_f32p), ("ldres2", C.c_int64), ("W_split", C.c_void_p),
                 ("a_pair_width", C.c_int32), ("c_pair", C.c_int32),
                 ("row_blocks", C.c_void_p), ("row_blocks_active", C.c_void_p), ("row_block_seg_len", C.c_int32),
-                ("split_fmt", C.c_int32), ("w_scale", c_f32p), ("a_scale", c_f32p)]
+                ("split_fmt", C.c_int32), ("w_scale", c_f32p), ("a_scale", c_f32p), ("products", C.c_int32)]
 
 
 MAX_SEGS = 32                                     # VRD_MAX_SEGS
@@ -176,7 +176,7 @@ _SIGNATURES = {
     "vrd_attention": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vrd_attention_pair": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, c_u8p, C.c_int, C.c_int, C.c_int,
-                                     C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+                                     C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "vrd_maxpool_mask": (C.c_int, [c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, c_u8p, c_f32p, C.c_int64, c_u8p,
                                    C.c_void_p]),
     "vrd_mask_head": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -219,7 +219,7 @@ _SIGNATURES = {
                                   C.c_void_p]),
 }
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 
 class HipLibraryError(RuntimeError):

@@ -119,6 +119,16 @@ FUSED_ATTN_BWD = os.environ.get("VRDONE_FUSED_ATTN_BWD", "1") != "0"      # A/B 
 
 
 # ------------------------------------------------------------------------------------------------------ Functions
+
+class _Differentiable(Function):
+    """The Functions of this module: applying one records autograd, which the forward-only f16x1 mode refuses (ValueError)."""
+
+    @classmethod
+    def apply(cls, *args, **kwargs):
+        ops.check_differentiable("vrdone_amd.autograd." + cls.__name__)
+        return super().apply(*args, **kwargs)
+
+
 class _ZeroArena:
     """Zero-initialised accumulators for the gradient kernels (weight / bias / LayerNorm / scale gradients are summed with
     atomics into their output), carved out of 16 MiB blocks: one fill per block instead of one `torch.zeros` per gradient
@@ -157,7 +167,7 @@ def _zeros(*shape, device):
     return _arena.take(n, torch.device(device)).view(*shape)
 
 
-class Linear(Function):
+class Linear(_Differentiable):
     """y = Conv1d(x; W (N, Cin, k), b) * row_mask, k in {1, 3}, on channels-last rows (vrd_gemm without epilogue terms)."""
 
     @staticmethod
@@ -237,7 +247,7 @@ class Linear(Function):
         return dx, dw, db, None
 
 
-class Activation(Function):
+class Activation(_Differentiable):
     @staticmethod
     def forward(ctx, x, act):
         ctx.save_for_backward(x)
@@ -250,7 +260,7 @@ class Activation(Function):
         return activation(x, ctx.act, dy=_dense(dy)), None
 
 
-class ScaleResidual(Function):
+class ScaleResidual(_Differentiable):
     """out = v * scale[c] * row_scale[r] * mask[r] + res * (mask if res_masked) + res2."""
 
     @staticmethod
@@ -278,7 +288,7 @@ class ScaleResidual(Function):
         return dv, ds, None, None, dres, None, dres2
 
 
-class LayerNormFn(Function):
+class LayerNormFn(_Differentiable):
     """Channel LayerNorm (+ReLU) (+post_add rows, period = post_add.shape[0])."""
 
     @staticmethod
@@ -310,7 +320,7 @@ class LayerNormFn(Function):
         return dx, dg.view_as(gamma), db.view_as(beta), None, dpost
 
 
-class DepthwiseConv(Function):
+class DepthwiseConv(_Differentiable):
     """D_o = mask_out * (bias_o + depthwise_conv(x (+ up2(x_up)); w_o)) for 1..3 weight sets (vrd_dwconv_ln without
     LayerNorm).  args after the fixed ones: w_0, b_0, w_1, b_1, ... (b_i may be None)."""
 
@@ -366,7 +376,7 @@ class DepthwiseConv(Function):
         return (dx, dx_up, None, None, *grads)
 
 
-class LocalAttention(Function):
+class LocalAttention(_Differentiable):
     @staticmethod
     def forward(ctx, q, k, v, mask, n_head, half_win, rel_pe=None):
         rel = None if rel_pe is None else rel_pe.detach()
@@ -394,7 +404,7 @@ class LocalAttention(Function):
         return dq, dk, dv, None, None, None, d_rel
 
 
-class Attention(Function):
+class Attention(_Differentiable):
     """Global masked attention (f32 kernels of vrd_attention)."""
 
     @staticmethod
@@ -466,7 +476,7 @@ class Attention(Function):
         return dq, dk, dv, None, None
 
 
-class MaxPoolMask(Function):
+class MaxPoolMask(_Differentiable):
     @staticmethod
     def forward(ctx, x, mask_in):
         y, m_out = ops.maxpool_mask(x, mask_in)
@@ -488,7 +498,7 @@ class MaxPoolMask(Function):
         return dx, None
 
 
-class MaskHead(Function):
+class MaskHead(_Differentiable):
     @staticmethod
     def forward(ctx, emb, feat, out_mask, fill):
         seg = ops.mask_head(emb, feat, out_mask, fill)
@@ -509,7 +519,7 @@ class MaskHead(Function):
         return demb, dfeat, None, None
 
 
-class ToChannelsLast(Function):
+class ToChannelsLast(_Differentiable):
     """(B, C, T) -> (B, T, C); its backward is the opposite layout change."""
 
     @staticmethod
@@ -521,7 +531,7 @@ class ToChannelsLast(Function):
         return ops.btc_to_bct(_dense(dy))
 
 
-class FromChannelsLast(Function):
+class FromChannelsLast(_Differentiable):
     @staticmethod
     def forward(ctx, x):
         return ops.btc_to_bct(x)

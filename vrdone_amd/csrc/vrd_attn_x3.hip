@@ -18,6 +18,10 @@
 // is consumed; one barrier per tile.  LDS rows are unpadded (the DMA writes linearly), so 16-byte chunks are
 // XOR-swizzled on the source address and on every read: K by (key & 15) for the row reads, V by (key & 3) << 2
 // for the transposed reads; both patterns are conflict free for head_dim 128.
+// NPROD = 1 (the f16x1 mode, F16 only), both kernels: one product per contraction step, S^T from k_hi . q_hi and O^T from
+// v_hi . p_hi, where p_hi = f16(P * 2^VRD_F16_ACT_EXP) is the hi plane of the three-product form's split (round to nearest,
+// subnormals kept; P <= 1 -- <= 2^8 with the second kernel's deferred rescaling -- so P * 2^4 is far inside the f16 range);
+// the softmax, its running sums and maxima stay f32.  The lo planes still arrive in LDS but are not read.
 #include "vrd_common.h"
 #include <cmath>
 #include <cstdlib>
@@ -48,7 +52,7 @@ struct AG {
     __device__ static constexpr int vswz(int key) { return ((key & 3) << 2) % CPR ^ (CPR == 8 ? ((key >> 1) & 1) << 2 : 0); }
 };
 
-template <int HD, int NW, bool F16>
+template <int HD, int NW, bool F16, int NPROD = 3>
 __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* __restrict__ q, int64_t ldq,
                                                                 const float* __restrict__ k, const float* __restrict__ v,
                                                                 int64_t ldkv, const uint8_t* __restrict__ kv_mask,
@@ -57,6 +61,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
                                                                 int64_t ldo, int pair_out, int q_blocks, int n_head_) {
     using G = AG<HD>;
     typedef typename vrd::SplitFmt<F16>::x8 bf16x8;      // eight 16-bit elements of this instantiation's format (bf16 or f16)
+    static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
+    constexpr bool LO = NPROD == 3;               // the lo planes take part
     constexpr int KS = HD / 16;                   // k16 steps of the S^T contraction
     constexpr int DT = HD / 32;                   // 32-row d tiles of O^T
     constexpr int PER_WAVE = (G::N_DMA + NW - 1) / NW;
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
         for (int s = 0; s < KS; ++s) {
             const int off = vrd::pair_index(16 * s + 8 * lh) * 2;
             qh[s] = *reinterpret_cast<const bf16x8*>(qr + off);
-            ql[s] = *reinterpret_cast<const bf16x8*>(qr + off + 64);
+            if (LO) ql[s] = *reinterpret_cast<const bf16x8*>(qr + off + 64);
         }
     }
     const int nkt = (Tk + 31) / 32;
@@ -155,7 +161,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
     // the fragments are in their registers before the tile loop: the compiler does not see the asm requests, and its own
     // counted waits for these loads, placed at their first use inside the loop, would wait for every tile's successor there
 #pragma unroll
-    for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(qh[s]), "+v"(ql[s]));
+    for (int s = 0; s < KS; ++s) {
+        if constexpr (LO) asm volatile("" : "+v"(qh[s]), "+v"(ql[s]));
+        else asm volatile("" : "+v"(qh[s]));
+    }
 
     f32x16 oacc[DT];
 #pragma unroll
@@ -197,18 +206,20 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
         for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
         // the K fragments of step s+1 are requested before the three MFMAs of step s (one chain of dependent
         // MFMAs: nothing else would hide the LDS latency)
-        bf16x8 kh = *reinterpret_cast<const bf16x8*>(st + krow + ((lh ^ G::kswz(li)) * 16));
-        bf16x8 kl = *reinterpret_cast<const bf16x8*>(st + G::PLANE + krow + ((lh ^ G::kswz(li)) * 16));
+        bf16x8 kh = *reinterpret_cast<const bf16x8*>(st + krow + ((lh ^ G::kswz(li)) * 16)), kl;
+        if (LO) kl = *reinterpret_cast<const bf16x8*>(st + G::PLANE + krow + ((lh ^ G::kswz(li)) * 16));
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             bf16x8 nh = kh, nl = kl;
             if (s + 1 < KS) {
                 const int off = krow + (((2 * (s + 1) + lh) ^ G::kswz(li)) * 16);
                 nh = *reinterpret_cast<const bf16x8*>(st + off);
-                nl = *reinterpret_cast<const bf16x8*>(st + G::PLANE + off);
+                if (LO) nl = *reinterpret_cast<const bf16x8*>(st + G::PLANE + off);
             }
-            sacc = vrd::mfma32(kl, qh[s], sacc);
-            sacc = vrd::mfma32(kh, ql[s], sacc);
+            if (LO) {
+                sacc = vrd::mfma32(kl, qh[s], sacc);
+                sacc = vrd::mfma32(kh, ql[s], sacc);
+            }
             sacc = vrd::mfma32(kh, qh[s], sacc);
             kh = nh;
             kl = nl;
@@ -249,7 +260,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
 #pragma unroll
             for (int j = 0; j < 8; ++j) pf[j] = sacc[8 * s + j];
             bf16x8 ph, pl;
-            vrd::split_n<F16>(pf, ph, pl);          // (f16: P * 2^VRD_F16_ACT_EXP)
+            vrd::split_n<F16>(pf, ph, pl);          // (f16: P * 2^VRD_F16_ACT_EXP; NPROD = 1: only ph is used)
 #pragma unroll
             for (int d = 0; d < DT; ++d) {
                 bf16x8 vh, vl;
@@ -260,7 +271,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
                     const int col = 32 * d + vcol0;                                   // first of its 4 columns
                     const int off = row * G::ROWB + ((((col * 2) >> 4) ^ G::vswz(row)) * 16) + ((col * 2) & 15);
                     const s16x4 th = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 2 * G::PLANE + off));
-                    const s16x4 tl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 3 * G::PLANE + off));
+                    s16x4 tl = th;
+                    if (LO) tl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 3 * G::PLANE + off));
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         rh[4 * part + j] = th[j];
@@ -269,8 +281,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
                 }
                 vh = __builtin_bit_cast(bf16x8, rh);
                 vl = __builtin_bit_cast(bf16x8, rl);
-                oacc[d] = vrd::mfma32(vl, ph, oacc[d]);
-                oacc[d] = vrd::mfma32(vh, pl, oacc[d]);
+                if (LO) {
+                    oacc[d] = vrd::mfma32(vl, ph, oacc[d]);
+                    oacc[d] = vrd::mfma32(vh, pl, oacc[d]);
+                }
                 oacc[d] = vrd::mfma32(vh, ph, oacc[d]);
             }
         }
@@ -414,7 +428,7 @@ __device__ unsigned long long g_attn_stamp[65];
 #define VRD_STAMP(i) do { } while (0)
 #endif
 
-template <int HD, bool F16>
+template <int HD, bool F16, int NPROD = 3>
 __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* __restrict__ q, int64_t ldq,
                                                                   const float* __restrict__ k, const float* __restrict__ v,
                                                                   int64_t ldkv, const uint8_t* __restrict__ kv_mask,
@@ -422,6 +436,10 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
                                                                   float scale_log2e, float* __restrict__ out, int64_t ldo,
                                                                   int pair_out, int q_blocks, int n_head_, int n_batch, int prefetch, int item_step) {
     using G = AG<HD>;
+    static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
+    // NPROD = 1: of the six MFMAs of a gap group only the two hi x hi ones (j = 4, 5) are issued; the softmax pieces keep their
+    // places in the gap enumeration (they then run back to back where the lo products were), the lo split of P is not formed
+    constexpr bool LO = NPROD == 3;
     constexpr int KS = HD / 16;                   // k16 steps of the S^T contraction
     constexpr int DT = HD / 32;                   // 32-row d tiles of O^T
     constexpr int NS = 4;                         // ring stages
@@ -674,7 +692,7 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
         KF f;
         const int off = krow + (((2 * s + lh) ^ G::kswz(li)) * 16);
         f.h = *reinterpret_cast<const bf16x8*>(st + off);
-        f.l = *reinterpret_cast<const bf16x8*>(st + G::PLANE + off);
+        if (LO) f.l = *reinterpret_cast<const bf16x8*>(st + G::PLANE + off);
         return f;
     };
     // V^T fragment (s, d) of the tile in stage `st`: two transposed reads per plane
@@ -687,7 +705,8 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
             const int col = 32 * d + vcol0;                                   // first of its 4 columns
             const int off = row * G::ROWB + ((((col * 2) >> 4) ^ G::vswz(row)) * 16) + ((col * 2) & 15);
             const s16x4 th = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 2 * G::PLANE + off));
-            const s16x4 tl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 3 * G::PLANE + off));
+            s16x4 tl = th;
+            if (LO) tl = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(st + 3 * G::PLANE + off));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 rh[4 * part + j] = th[j];
@@ -742,7 +761,9 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
     };
     auto split_piece = [&](auto s_c, auto q_c) __attribute__((always_inline)) {
         constexpr int s = decltype(s_c)::value, q = decltype(q_c)::value, j = q >> 2, sub = q & 3, e0 = 8 * s + 2 * j;
-        if constexpr (sub == 0) {
+        if constexpr (!LO && sub != 0) {
+            // (NPROD = 1: no lo half)
+        } else if constexpr (sub == 0) {
             if constexpr (F16)
                 asm volatile("v_cvt_pk_f16_f32 %0, %2, %3\n\tv_cvt_pk_f16_f32 %1, %4, %5"
                              : "=&v"(A.ph[s][j]), "=&v"(B.ph[s][j]) : "v"(A.x[e0]), "v"(A.x[e0 + 1]), "v"(B.x[e0]), "v"(B.x[e0 + 1]));
@@ -851,7 +872,13 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
         constexpr int s = decltype(s_c)::value, j = decltype(j_c)::value, qb = j & 1;
         f32x16& acc = qb ? sb : sa;
         constexpr int aq = VRD_AQ(qb, s) + (j >= 2 && j < 4 ? 4 : 0);          // q_lo for the middle product
-        if constexpr (s == 0 && j < 2) {
+        if constexpr (!LO) {             // hi x hi only (j = 4, 5); the chain starts from 0 at s = 0
+            if constexpr (j < 4) {
+            } else if constexpr (s == 0)
+                VRD_MFMA("", "%0, %1, a[%c2:%c3], 0", : "=&v"(acc) : "v"(kf.h), "n"(aq), "n"(aq + 3));
+            else
+                VRD_MFMA("", "%0, %1, a[%c2:%c3], %0", : "+v"(acc) : "v"(kf.h), "n"(aq), "n"(aq + 3));
+        } else if constexpr (s == 0 && j < 2) {
             VRD_MFMA("", "%0, %1, a[%c2:%c3], 0", : "=&v"(acc) : "v"(kf.l), "n"(aq), "n"(aq + 3));
         } else if constexpr (j < 2) {
             VRD_MFMA("", "%0, %1, a[%c2:%c3], %0", : "+v"(acc) : "v"(kf.l), "n"(aq), "n"(aq + 3));
@@ -864,7 +891,13 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
         constexpr int g = decltype(g_c)::value, j = decltype(j_c)::value, qb = j & 1, s = g / DT, d = g % DT;
         constexpr int ao = VRD_AO(qb, d);
         const SmBlock& X = qb ? B : A;
-        if constexpr (j < 2) {
+        if constexpr (!LO) {             // hi x hi only; the group's first MFMA reads the P^T fragments the split just wrote
+            if constexpr (j < 4) {
+            } else if constexpr (d == 0 && j == 4)
+                VRD_MFMA("s_nop 1\n\t", "a[%c2:%c3], %0, %1, a[%c2:%c3]", :: "v"(vf.h), "v"(X.ph[s]), "n"(ao), "n"(ao + 15));
+            else
+                VRD_MFMA("", "a[%c2:%c3], %0, %1, a[%c2:%c3]", :: "v"(vf.h), "v"(X.ph[s]), "n"(ao), "n"(ao + 15));
+        } else if constexpr (j < 2) {
             if constexpr (d == 0 && j == 0)      // the fragments of this k16 step were written by vector instructions just now
                 VRD_MFMA("s_nop 1\n\t", "a[%c2:%c3], %0, %1, a[%c2:%c3]", :: "v"(vf.l), "v"(X.ph[s]), "n"(ao), "n"(ao + 15));
             else
@@ -1161,10 +1194,10 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
 #undef VRD_MFMA
 }
 
-template <int HD, bool F16>
+template <int HD, bool F16, int NPROD = 3>
 int launch_w64(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kv_mask, const uint8_t* q_mask, int B,
                int Tq, int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s) {
-    auto kern = attn_flash_x3_w64_kernel<HD, F16>;
+    auto kern = attn_flash_x3_w64_kernel<HD, F16, NPROD>;
     // behind the ring: key bias + tile flags for Tk <= 4096, a flag per 32 queries (Tq <= 65536: the dispatch keeps longer ones
     // away), and -- if it fits in what is left of the 160 KiB -- the staging area of the next item's mask bytes, a dword each
     constexpr size_t lds_all = 160 * 1024;
@@ -1204,10 +1237,10 @@ int launch_w64(const float* q, int64_t ldq, const float* k, const float* v, int6
     return 0;
 }
 
-template <int HD, int NW, bool F16>
+template <int HD, int NW, bool F16, int NPROD = 3>
 int launch(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq,
            int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s) {
-    auto kern = attn_flash_x3_kernel<HD, NW, F16>;
+    auto kern = attn_flash_x3_kernel<HD, NW, F16, NPROD>;
     constexpr size_t lds_max = 2 * AG<HD>::STAGE + (4096 + 128) * sizeof(float);       // key bias + tile flags for Tk <= 4096
     const size_t lds = 2 * AG<HD>::STAGE + (size_t)((Tk + 31) / 32) * 33 * sizeof(float);
     if (lds > lds_max) {
@@ -1239,7 +1272,7 @@ extern "C" int vrd_lab_attn_stamps(unsigned long long* dst65, int reset) {
 
 extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                                   const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, int head_dim,
-                                  float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream) {
+                                  float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream, int products) {
     VRD_CHECK_ARG(q && k && v && out, "vrd_attention_pair: null pointer");
     VRD_CHECK_ARG(head_dim == 64 || head_dim == 128, "vrd_attention_pair: head_dim must be 64 or 128 (got %d)", head_dim);
     VRD_CHECK_ARG(B > 0 && B <= 65535 && Tq > 0 && Tk > 0 && n_head > 0 && n_head <= 65535, "vrd_attention_pair: bad sizes");
@@ -1249,6 +1282,8 @@ extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, c
                   "vrd_attention_pair: rows must be 16-byte aligned pair rows of width n_head*head_dim");
     VRD_CHECK_ARG(pair_fmt == VRD_PAIR_BF16 || pair_fmt == VRD_PAIR_F16, "vrd_attention_pair: pair_fmt must be VRD_PAIR_BF16 or VRD_PAIR_F16");
     VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == pair_fmt, "vrd_attention_pair: pair output comes in the operands' format");
+    VRD_CHECK_ARG(products == 0 || products == 3 || (products == 1 && pair_fmt == VRD_PAIR_F16),
+                  "vrd_attention_pair: products must be 0 or 3, or 1 with VRD_PAIR_F16 operands (got %d, pair_fmt %d)", products, pair_fmt);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool f16 = pair_fmt == VRD_PAIR_F16;
     // f16 operands hold q and k times 2^VRD_F16_ACT_EXP each: the raw scores are 2^(2 e) too large, undone in the softmax scale
@@ -1276,7 +1311,11 @@ extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, c
                      (int64_t)Tq * ldq * 4 < (int64_t(1) << 31) && Tq <= 65536;
     int rc;
 #define VRD_ATTN_ARGS q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s
-    if (w64) rc = head_dim == 128 ? (f16 ? launch_w64<128, true>(VRD_ATTN_ARGS) : launch_w64<128, false>(VRD_ATTN_ARGS))
+    if (products == 1) {
+        if (w64) rc = head_dim == 128 ? launch_w64<128, true, 1>(VRD_ATTN_ARGS) : launch_w64<64, true, 1>(VRD_ATTN_ARGS);
+        else if (head_dim == 128) rc = nw == 3 ? launch<128, 3, true, 1>(VRD_ATTN_ARGS) : launch<128, 4, true, 1>(VRD_ATTN_ARGS);
+        else rc = nw == 3 ? launch<64, 3, true, 1>(VRD_ATTN_ARGS) : launch<64, 4, true, 1>(VRD_ATTN_ARGS);
+    } else if (w64) rc = head_dim == 128 ? (f16 ? launch_w64<128, true>(VRD_ATTN_ARGS) : launch_w64<128, false>(VRD_ATTN_ARGS))
                                   : (f16 ? launch_w64<64, true>(VRD_ATTN_ARGS) : launch_w64<64, false>(VRD_ATTN_ARGS));
     else if (head_dim == 128) rc = nw == 3 ? (f16 ? launch<128, 3, true>(VRD_ATTN_ARGS) : launch<128, 3, false>(VRD_ATTN_ARGS))
                                            : (f16 ? launch<128, 4, true>(VRD_ATTN_ARGS) : launch<128, 4, false>(VRD_ATTN_ARGS));

@@ -259,6 +259,7 @@ X3Choice choose_x3(const vrd_gemm_args* a, bool vec, bool staged) {
     static const int64_t big_min_tiles = [] { const char* e = getenv("VRD_X3_BIG_MIN_TILES"); return e ? atoll(e) : 512; }();
     const bool big = dma && a->N >= 256 && K >= 96 && vrd::gemm_epilogue_lean_ok(*a) &&      // (its K loop is written for >= 3 steps)
                      (a->taps == 1 || a->T >= 32) &&      // k = 3: the kernel steps its sequence position by 8 rows per piece
+                     (a->products != 1 || (a->Cin % 64 == 0 && K >= 192)) &&     // one product: K steps of 64, three or more
                      (reinterpret_cast<uintptr_t>(a->A) & 127u) == 0 && (reinterpret_cast<uintptr_t>(a->W_split) & 127u) == 0 &&
                      ((a->M + 255) / 256) * ((a->N + 255) / 256) >= big_min_tiles;
     return X3Choice{x3, dma, big};
@@ -290,6 +291,9 @@ int validate_gemm_args(const vrd_gemm_args* a) {
                   "vrd_gemm: a_scale goes with f32-row A in the VRD_PAIR_F16 format");
     VRD_CHECK_ARG(!a->c_pair || !a->W_split || a->c_pair == (a->split_fmt ? a->split_fmt : (int)VRD_PAIR_BF16),
                   "vrd_gemm: pair output (format %d) of a split-precision GEMM must be in its operand format (%d)", a->c_pair, a->split_fmt);
+    VRD_CHECK_ARG(a->products == 0 || a->products == 1 || a->products == 3, "vrd_gemm: products must be 0, 1 or 3 (got %d)", a->products);
+    VRD_CHECK_ARG(a->products != 1 || (a->split_fmt == VRD_PAIR_F16 && a->W_split),
+                  "vrd_gemm: the one-product form (products = 1) needs a VRD_PAIR_F16 W_split (split_fmt %d)", a->split_fmt);
     VRD_CHECK_ARG(!a->row_blocks || (a->row_blocks_active && a->M % 32 == 0 && a->row_block_seg_len >= 8 &&
                                      a->row_block_seg_len % 8 == 0),
                   "vrd_gemm: a row-block list needs its active counts, M %% 32 == 0 and a segment length that is a multiple of 8 (M = %lld, seg_len %d)",
@@ -331,6 +335,7 @@ extern "C" int vrd_gemm(const vrd_gemm_args* a, void* stream) {
     // -- a call that carries W_split but does not qualify for a split kernel (K % 32, alignment) lands here
     vrd_gemm_args f = *a;
     f.split_fmt = 0;
+    f.products = 0;
     f.w_scale = nullptr;
     f.a_scale = nullptr;
     VRD_CHECK_ARG(!f.c_pair || f.c_pair == VRD_PAIR_BF16 || f.c_pair == VRD_PAIR_F16, "vrd_gemm: bad c_pair");
@@ -348,6 +353,9 @@ extern "C" int vrd_gemm_batch(const vrd_gemm_args* a, int count, void* stream) {
     VRD_CHECK_ARG(a != nullptr && count >= 1 && count <= 4, "vrd_gemm_batch: 1..4 problems (got %d)", count);
     for (int i = 0; i < count; ++i)
         if (int rc = validate_gemm_args(&a[i])) return rc;
+    for (int i = 1; i < count; ++i)
+        VRD_CHECK_ARG((a[i].products == 1) == (a[0].products == 1), "vrd_gemm_batch: every problem needs the same products (%d vs %d)",
+                      a[i].products, a[0].products);
     bool same = count > 1 && a[0].M > 0;
     for (int i = 1; i < count && same; ++i) {
         const vrd_gemm_args &x = a[i], &y = a[0];

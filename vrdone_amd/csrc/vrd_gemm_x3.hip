@@ -13,6 +13,9 @@
 // 16-bit planes written by the producing kernel, staged as plain 16-byte copies.
 // F16 (VRD_PAIR_F16, the f16x3 mode): the same with f16 planes of power-of-two scaled operands (vrd_common.h): 2^-22 per
 // plane pair, ~2^-22 |a w| dropped; the epilogue multiplies the accumulator by the power of two that undoes the scaling.
+// NPROD = 1 (the f16x1 mode, F16 only): a*w ~= a_hi*w_hi, one MFMA per K step and accumulator; the lo planes are neither loaded
+// nor staged (f32 rows: only the hi plane is made).  Every split-precision kernel has this form too, with one product per K
+// step in K order, so the choice of kernel does not change a bit of it either.
 //
 // Tiling: 128 x 128 x 32 per 256-thread workgroup, four waves x (2 x 2) blocks of 32 x 32 (each 2 x 2 accumulators of 16 x 16), operand
 // tiles [row][k] in bf16 with an 80-byte row pitch (16 consecutive rows hit 16 distinct 16-byte LDS slots,
@@ -43,9 +46,11 @@ struct X3Geo {
     static constexpr int NPA = BM / 32, NPAP = BM / 64, NPW = BN / 64;   // staging pieces per thread: f32 A, pair A, W
 };
 
-template <int TAPS, bool STAGED, bool APAIR, bool SMALL = false, bool F16 = false>
+template <int TAPS, bool STAGED, bool APAIR, bool SMALL = false, bool F16 = false, int NPROD = 3>
 __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles_m, int tiles_n, unsigned* rflag) {
     using G = X3Geo<SMALL>;
+    static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
+    constexpr bool LO = NPROD == 3;                         // the lo planes take part
     typedef typename vrd::SplitFmt<F16>::elem e16;          // the 16-bit element of this instantiation (bf16 or f16)
     typedef typename vrd::SplitFmt<F16>::x8 e16x8;
     typedef typename vrd::SplitFmt<F16>::x4 e16x4;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
                         const e16* row = reinterpret_cast<const e16*>(p.A + (r + tap - (TAPS == 3 ? 1 : 0)) * p.lda) +
                                             vrd::pair_index(ci);
                         h = *reinterpret_cast<const uint4*>(row);
-                        l = *reinterpret_cast<const uint4*>(row + 32);
+                        if (LO) l = *reinterpret_cast<const uint4*>(row + 32);
                     }
                 }
                 ra[i] = *reinterpret_cast<float4*>(&h);
@@ -142,7 +147,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
             if (n < p.N) {
                 const e16* wrow = Wsp + (int64_t)n * K * 2 + vrd::pair_index(k);
                 h = *reinterpret_cast<const uint4*>(wrow);
-                l = *reinterpret_cast<const uint4*>(wrow + 32);
+                if (LO) l = *reinterpret_cast<const uint4*>(wrow + 32);
             }
             rwh[i] = h;
             rwl[i] = l;
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
                 const int f = tid + 256 * i;
                 const int off = (f >> 2) * XP + (f & 3) * 8;
                 *reinterpret_cast<float4*>(a_hi + off) = ra[i];
-                *reinterpret_cast<float4*>(a_lo + off) = ra[2 + i];
+                if (LO) *reinterpret_cast<float4*>(a_lo + off) = ra[2 + i];
             }
         } else
 #pragma unroll
@@ -170,14 +175,14 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
             e16x4 h, l;
             vrd::split_n_scaled<F16>(x, amul, h, l, &rt_in);
             *reinterpret_cast<e16x4*>(a_hi + off) = h;
-            *reinterpret_cast<e16x4*>(a_lo + off) = l;
+            if (LO) *reinterpret_cast<e16x4*>(a_lo + off) = l;
         }
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
             const int f = tid + 256 * i;
             const int off = (f >> 2) * XP + (f & 3) * 8;
             *reinterpret_cast<uint4*>(w_hi + off) = rwh[i];
-            *reinterpret_cast<uint4*>(w_lo + off) = rwl[i];
+            if (LO) *reinterpret_cast<uint4*>(w_lo + off) = rwl[i];
         }
     };
 
@@ -203,9 +208,9 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
 #pragma unroll
         for (int t = 0; t < 2 * NT; ++t) {
             ah[t] = *reinterpret_cast<const e16x8*>(a_hi + arow + t * 16 * XP);
-            al[t] = *reinterpret_cast<const e16x8*>(a_lo + arow + t * 16 * XP);
+            if (LO) al[t] = *reinterpret_cast<const e16x8*>(a_lo + arow + t * 16 * XP);
             wh[t] = *reinterpret_cast<const e16x8*>(w_hi + wrow + t * 16 * XP);
-            wl[t] = *reinterpret_cast<const e16x8*>(w_lo + wrow + t * 16 * XP);
+            if (LO) wl[t] = *reinterpret_cast<const e16x8*>(w_lo + wrow + t * 16 * XP);
         }
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
@@ -213,7 +218,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(vrd_gemm_args p, int tiles
 #pragma unroll
             for (int bi = half * NT; bi < (half + 1) * NT; ++bi)
 #pragma unroll
-                for (int pr = 0; pr < 3; ++pr)
+                for (int pr = 3 - NPROD; pr < 3; ++pr)          // (NPROD = 1: hi x hi only)
 #pragma unroll
                     for (int bj = 0; bj < 2 * NT; ++bj) {
                         vrd::f32x4_t& c = acc[bi >> 1][bj >> 1].b[bi & 1][bj & 1];
@@ -240,7 +245,9 @@ namespace vrd {
 // called by vrd_gemm() after argument validation when W_split is given and the shape qualifies
 template <int TAPS, bool STAGED, bool APAIR, bool SMALL = false>
 static int launch_one(const vrd_gemm_args& a, int tiles_m, int tiles_n, hipStream_t s) {
-    auto kern = a.split_fmt == VRD_PAIR_F16 ? gemm_x3_kernel<TAPS, STAGED, APAIR, SMALL, true> : gemm_x3_kernel<TAPS, STAGED, APAIR, SMALL, false>;
+    auto kern = a.split_fmt != VRD_PAIR_F16 ? gemm_x3_kernel<TAPS, STAGED, APAIR, SMALL, false>
+                : a.products == 1           ? gemm_x3_kernel<TAPS, STAGED, APAIR, SMALL, true, 1>
+                                            : gemm_x3_kernel<TAPS, STAGED, APAIR, SMALL, true>;
     constexpr size_t lds = X3Geo<SMALL>::LDS;
     if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), lds, "vrd_gemm(bf16x3)")) return rc;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), lds, s, a, tiles_m, tiles_n, a.split_fmt == VRD_PAIR_F16 ? vrd::range_flag() : nullptr);

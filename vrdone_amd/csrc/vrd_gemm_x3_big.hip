@@ -115,9 +115,23 @@ __device__ __forceinline__ T load_karg(kargs_ptr_t base, int byte_off) {
 // WH = wave >> 2 as a compile-time constant: the two halves of the workgroup run their own copy of the whole body (the place
 // of a wave's LDS-DMA request inside an MFMA group is then no branch: 16 per K step before), and the copies never join, so the
 // register assignment of one does not constrain the other (joined behind the K loop, one copy spilled accumulators)
-template <int TAPS, bool PERSIST, bool F16, int WH>
+// NPROD = 1 (the f16x1 mode, F16 only; vrd_gemm_x3.hip): one MFMA (hi x hi) per accumulator and 32-wide K block.  With the
+// three-product step a K step would keep a third of its MFMA time to cover the same LDS-DMA issue (measured: the GEMM at 0.21 of
+// the one-product roof), so the one-product form takes K steps of 64: a 128-byte tile row of the ring holds the HI halves of two
+// consecutive 32-wide K blocks (chunks 0..3: block 2s, chunks 4..7: block 2s+1 -- where the three-product form keeps hi and lo of
+// one block).  Every DMA request then moves 1 KiB of operands that are all multiplied (no lo plane is fetched), a step is eight
+// groups of eight MFMAs (block 2s against the four column blocks, then block 2s+1: consecutive MFMAs write different
+// accumulators, and each accumulator still sums its K blocks in K order, so the result is the other kernels' bit for bit), and
+// the ring, the counted waits, the DMA slots and the issue priorities work per K step as before: one barrier and eight requests
+// per wave now cover 64 MFMAs instead of 96 (three products) or 32 (one product at K step 32).  The host sends it Cin % 64 == 0
+// (a K step never straddles two taps) and K >= 192 (three K steps or more).
+template <int TAPS, bool PERSIST, bool F16, int WH, int NPROD>
 __device__ __forceinline__ void gemm_x3_big_body() {
+    static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
 #if defined(__HIP_DEVICE_COMPILE__)       // (the buffer descriptor type exists in the device pass only)
+    constexpr bool LO = NPROD == 3;                  // the lo planes take part (NPROD = 1: the "lo" chunks of a row hold block 2s+1)
+    constexpr int KB = LO ? 1 : 2;                   // 32-wide K blocks per K step
+    constexpr int NQ = LO ? 12 : 8;                  // MFMAs of a group (16-row block against the four column blocks)
     typedef typename vrd::SplitFmt<F16>::x8 e16x8;      // fragment of eight 16-bit elements (bf16 or f16)
     kargs_ptr_t kp = (kargs_ptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     vrd_gemm_args p;
@@ -142,7 +156,7 @@ __device__ __forceinline__ void gemm_x3_big_body() {
             p.C = z == 1 ? bb.C[0] : z == 2 ? bb.C[1] : bb.C[2];
         }
         K = p.Cin * TAPS;
-        nkt = K / 32;
+        nkt = K / (32 * KB);
         nwg = tiles_m * tiles_n;
         nblk = (int)(p.M >> 5);
         rb = p.row_blocks;
@@ -202,8 +216,15 @@ __device__ __forceinline__ void gemm_x3_big_body() {
     unsigned va[2], vw[2];
     auto lane_offsets = [&]() {
         const unsigned a_lane = (unsigned)rin * (unsigned)(p.lda * 4), w_lane = (unsigned)rin * (unsigned)(K * 4);
-        va[0] = a_lane + chunk0, va[1] = a_lane + (chunk0 ^ 64);
-        vw[0] = w_lane + chunk0, vw[1] = w_lane + (chunk0 ^ 64);
+        if (LO) {
+            va[0] = a_lane + chunk0, va[1] = a_lane + (chunk0 ^ 64);
+            vw[0] = w_lane + chunk0, vw[1] = w_lane + (chunk0 ^ 64);
+        } else {        // tile-row chunk c (logical) <- hi chunk c & 3 of source line (block) c >> 2 of the step
+            const unsigned c0 = chunk0 >> 4, c1 = c0 ^ 4;
+            const unsigned s0 = (c0 & 3) * 16 + (c0 >> 2) * 128, s1 = (c1 & 3) * 16 + (c1 >> 2) * 128;
+            va[0] = a_lane + s0, va[1] = a_lane + s1;
+            vw[0] = w_lane + s0, vw[1] = w_lane + s1;
+        }
     };
     lane_offsets();
     struct Src {
@@ -233,11 +254,11 @@ __device__ __forceinline__ void gemm_x3_big_body() {
     auto issue_w1 = [&](const Src& c, int gk, int ks, int i) {
         char* const dst = lds + W_RING + (gk % NW_STG) * W_STAGE + wave * PER * 1024;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(c.rw, (lds_ptr_t)(dst + i * 1024), 16, vw[i & 1],
-                                                 (i < c.w_last ? i : c.w_last) * (int)w_pstride + ks * 128, 0, 0);
+                                                 (i < c.w_last ? i : c.w_last) * (int)w_pstride + ks * 128 * KB, 0, 0);
     };
     auto issue_a1 = [&](const Src& c, int gk, int ks, int i) {
         char* const dst = lds + (gk % NA_STG) * A_STAGE + wave * PER * 1024;
-        const int k0 = ks * 32;
+        const int k0 = ks * 32 * KB;
         int tap = 0, ci0 = k0;
         unsigned vo = va[i & 1];
         if (TAPS == 3) {
@@ -456,12 +477,19 @@ __device__ __forceinline__ void gemm_x3_big_body() {
             // (block-major in a step's last group: a column block's weight fragments are reloaded right behind its third product)
             constexpr bool blockmajor = !last;
 #pragma unroll
-            for (int q = 0; q < 12; ++q) {
-                const int pr = (blockmajor && g == 7) ? q % 3 : q >> 2, t = (blockmajor && g == 7) ? q / 3 : q & 3;
+            for (int q = 0; q < NQ; ++q) {
+                // three products: pr = 0 (lo x hi), 1 (hi x lo), 2 (hi x hi).  NPROD = 1: kb = the step's K block (0: the
+                // tile rows' chunks 0..3, 1: chunks 4..7, read through the `lo` offsets)
+                const int pr = LO ? ((blockmajor && g == 7) ? q % 3 : q >> 2) : 0;
+                const int kb = LO ? 0 : ((blockmajor && g == 7) ? q & 1 : q >> 2);
+                const int t = LO ? ((blockmajor && g == 7) ? q / 3 : q & 3) : ((blockmajor && g == 7) ? q >> 1 : q & 3);
+                const bool a_lo = LO ? pr == 0 : kb == 1, w_lo = LO ? pr == 1 : kb == 1;
+                const bool chain0 = LO ? pr == 0 : kb == 0, w_done = LO ? pr == 2 : kb == 1;
                 const vrd::f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
-                acc[g][t] = vrd::mfma16(pr == 0 ? a_cur.lo : a_cur.hi, pr == 1 ? w_cur.lo[t] : w_cur.hi[t], (POS == POS_FIRST && pr == 0) ? zero4 : acc[g][t]);
-                if (blockmajor && g == 7 && pr == 2) load_w1(sw1, t, w_cur);
-                if ((q == 5 && WH == 0) || (q == 11 && WH == 1)) dma_of_group();
+                acc[g][t] = vrd::mfma16(a_lo ? a_cur.lo : a_cur.hi, w_lo ? w_cur.lo[t] : w_cur.hi[t],
+                                        (POS == POS_FIRST && chain0) ? zero4 : acc[g][t]);
+                if (blockmajor && g == 7 && w_done) load_w1(sw1, t, w_cur);
+                if ((q == NQ / 2 - 1 && WH == 0) || (q == NQ - 1 && WH == 1)) dma_of_group();
             }
             a_cur = a_nxt;
             if (g == 6 && !last) {
@@ -550,19 +578,19 @@ __device__ __forceinline__ void gemm_x3_big_body() {
 #endif
 }
 
-template <int TAPS, bool PERSIST, bool F16 = false>
+template <int TAPS, bool PERSIST, bool F16 = false, int NPROD = 3>
 __global__ __launch_bounds__(512) void gemm_x3_big_kernel(BigKArgs ka_unused_) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8)) gemm_x3_big_body<TAPS, PERSIST, F16, 1>();
-    else gemm_x3_big_body<TAPS, PERSIST, F16, 0>();
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 8)) gemm_x3_big_body<TAPS, PERSIST, F16, 1, NPROD>();
+    else gemm_x3_big_body<TAPS, PERSIST, F16, 0, NPROD>();
 }
 
 }  // namespace
 
 namespace vrd {
 
-template <int TAPS, bool PERSIST, bool F16 = false>
+template <int TAPS, bool PERSIST, bool F16 = false, int NPROD = 3>
 static int launch_big_one(const vrd_gemm_args& a, hipStream_t s, const BigBatch& bb = BigBatch{}, int count = 1) {
-    auto kern = gemm_x3_big_kernel<TAPS, PERSIST, F16>;
+    auto kern = gemm_x3_big_kernel<TAPS, PERSIST, F16, NPROD>;
     if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), BIG_LDS, "vrd_gemm(bf16x3 256x256)")) return rc;
     const int tiles_m = (int)((a.M + TM - 1) / TM), tiles_n = (a.N + TN - 1) / TN;
     const int nwg = tiles_m * tiles_n;
@@ -588,6 +616,10 @@ static bool big_persist(const vrd_gemm_args& a) {
 
 static int launch_big_any(const vrd_gemm_args& a, hipStream_t s, const BigBatch& bb, int count) {
     const bool f16 = a.split_fmt == VRD_PAIR_F16;
+    if (f16 && a.products == 1) {
+        if (big_persist(a)) return launch_big_one<1, true, true, 1>(a, s, bb, count);
+        return a.taps == 1 ? launch_big_one<1, false, true, 1>(a, s, bb, count) : launch_big_one<3, false, true, 1>(a, s, bb, count);
+    }
     if (big_persist(a)) return f16 ? launch_big_one<1, true, true>(a, s, bb, count) : launch_big_one<1, true, false>(a, s, bb, count);
     if (f16) return a.taps == 1 ? launch_big_one<1, false, true>(a, s, bb, count) : launch_big_one<3, false, true>(a, s, bb, count);
     return a.taps == 1 ? launch_big_one<1, false, false>(a, s, bb, count) : launch_big_one<3, false, false>(a, s, bb, count);

@@ -16,6 +16,8 @@
 // linearly), so the 16-byte chunk index is XOR-swizzled with (row >> 1) & 7 on the SOURCE address and again on the fragment
 // read; 16 consecutive rows of one logical chunk then land in 16 distinct 16-byte LDS slots.
 // Zero padding of the k=3 convolution at sequence ends is a per-lane source pointer to a zero block.
+// NPROD = 1 (f16x1, vrd_gemm_x3.hip): one product hi x hi per K step; the lanes that would move a lo chunk read the zero block
+// instead (the same requests, half the bytes from HBM / L2), and the lo chunks in LDS are not read.
 #include "vrd_common.h"
 #include "vrd_gemm_epilogue.h"
 #include <type_traits>
@@ -35,8 +37,10 @@ __device__ constexpr int swz(int row) { return (row >> 1) & 7; }
 
 __device__ uint4 g_zero_block[8];                     // 128 zero bytes: source of padded taps
 
-template <int TAPS, bool F16>
+template <int TAPS, bool F16, int NPROD = 3>
 __global__ __launch_bounds__(512) void gemm_x3_dma_kernel(vrd_gemm_args p, int tiles_m, int tiles_n, unsigned* rflag) {
+    static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
+    constexpr bool LO = NPROD == 3;
     typedef typename vrd::SplitFmt<F16>::x8 e16x8;      // fragment of eight 16-bit elements: bf16, or f16 (VRD_PAIR_F16)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* const lds = reinterpret_cast<char*>(smem);
@@ -114,6 +118,7 @@ __global__ __launch_bounds__(512) void gemm_x3_dma_kernel(vrd_gemm_args p, int t
             } else {
                 src = gsrc[i] + w_off + lchunk[i];
             }
+            if (!LO && lchunk[i] >= 64) src = zero_src + lchunk[i];
             __builtin_amdgcn_global_load_lds(src, (lds_ptr_t)(lds + buf * STAGE + ldst[i]), 16, 0, 0);
         }
     };
@@ -145,14 +150,14 @@ __global__ __launch_bounds__(512) void gemm_x3_dma_kernel(vrd_gemm_args p, int t
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             wh[t] = *reinterpret_cast<const e16x8*>(st + w_rd + t * 16 * ROWB);
-            wl[t] = *reinterpret_cast<const e16x8*>(st + (w_rd ^ 64) + t * 16 * ROWB);
+            if (LO) wl[t] = *reinterpret_cast<const e16x8*>(st + (w_rd ^ 64) + t * 16 * ROWB);
         }
 #pragma unroll
         for (int bi = 0; bi < 4; ++bi) {
             const e16x8 ah = *reinterpret_cast<const e16x8*>(st + a_rd + bi * 16 * ROWB);
-            const e16x8 al = *reinterpret_cast<const e16x8*>(st + (a_rd ^ 64) + bi * 16 * ROWB);
+            const e16x8 al = LO ? *reinterpret_cast<const e16x8*>(st + (a_rd ^ 64) + bi * 16 * ROWB) : ah;
 #pragma unroll
-            for (int pr = 0; pr < 3; ++pr)
+            for (int pr = 3 - NPROD; pr < 3; ++pr)          // (NPROD = 1: hi x hi only)
 #pragma unroll
                 for (int bj = 0; bj < 4; ++bj) {
                     vrd::f32x4_t& c = acc[bi >> 1][bj >> 1].b[bi & 1][bj & 1];
@@ -170,9 +175,9 @@ __global__ __launch_bounds__(512) void gemm_x3_dma_kernel(vrd_gemm_args p, int t
 
 namespace vrd {
 
-template <int TAPS, bool F16>
+template <int TAPS, bool F16, int NPROD = 3>
 static int launch_dma_one(const vrd_gemm_args& a, hipStream_t s) {
-    auto kern = gemm_x3_dma_kernel<TAPS, F16>;
+    auto kern = gemm_x3_dma_kernel<TAPS, F16, NPROD>;
     static_assert(DMA_LDS >= 8 * 16384 && DMA_LDS <= 160 * 1024, "ring must hold the epilogue slabs and fit the CU");
     if (int rc = reserve_lds(reinterpret_cast<const void*>(kern), DMA_LDS, "vrd_gemm(bf16x3 dma)")) return rc;
     const int tiles_m = (int)((a.M + DBM - 1) / DBM), tiles_n = (a.N + DBN - 1) / DBN;
@@ -188,6 +193,7 @@ bool gemm_x3_dma_ok(const vrd_gemm_args& a, bool staged) {
 // (other schedules of this tile -- ping-pong wave groups, dedicated producer waves -- were measured in rounds 1-2 and not kept:
 // LABNOTES.md; their sources are in the history of this file)
 int launch_gemm_x3_dma(const vrd_gemm_args& a, hipStream_t s) {
+    if (a.split_fmt == VRD_PAIR_F16 && a.products == 1) return a.taps == 1 ? launch_dma_one<1, true, 1>(a, s) : launch_dma_one<3, true, 1>(a, s);
     if (a.split_fmt == VRD_PAIR_F16) return a.taps == 1 ? launch_dma_one<1, true>(a, s) : launch_dma_one<3, true>(a, s);
     return a.taps == 1 ? launch_dma_one<1, false>(a, s) : launch_dma_one<3, false>(a, s);
 }

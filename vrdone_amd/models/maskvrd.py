@@ -376,7 +376,9 @@ class MaskVRD(nn.Module):
         # on the device (ops.f16_range_flag; a NaN would not reach the loss reliably).  The word is read once, behind the
         # step's own launches, and such a step is taken again in the f32 mode -- the arithmetic of the reference (train.py:182-186).
         pdev = next(self.parameters()).device
-        guard = ops.get_precision() == "f16x3" and pdev.type == "cuda" and os.environ.get("VRDONE_RANGE_GUARD", "1") != "0"
+        if torch.is_grad_enabled():
+            ops.check_differentiable("MaskVRD.forward_training")
+        guard = ops.f16_planes() and pdev.type == "cuda" and os.environ.get("VRDONE_RANGE_GUARD", "1") != "0"
         if guard:
             flag = ops.f16_range_flag(pdev)
             flag.zero_()
@@ -400,7 +402,7 @@ class MaskVRD(nn.Module):
             if bits:
                 import warnings
                 flag.zero_()
-                warnings.warn("vrdone_amd: an activation beyond the f16x3 mode's operand range (" + ops.describe_range(bits) +
+                warnings.warn(f"vrdone_amd: an activation beyond the {ops.get_precision()} mode's operand range (" + ops.describe_range(bits) +
                               "): taking this step in the f32 mode")
                 del losses, predictions
                 with ops.use_precision("f32"):
@@ -985,7 +987,7 @@ class MaskVRD(nn.Module):
         unsort[torch.tensor(order, dtype=torch.int64)] = torch.arange(P)
         unsort = unsort.to(dev)                         # uploaded before the first kernel is queued
         ops = _ops()
-        f16 = ops.get_precision() == "f16x3"
+        f16 = ops.f16_planes()
         if f16:
             flag = ops.f16_range_flag(next(self.parameters()).device)
             flag.zero_()
@@ -1002,7 +1004,7 @@ class MaskVRD(nn.Module):
             # so does the repeat.  (After the exchange: every rank of a sharded run sees the same candidates and takes the
             # same branch.)
             import warnings
-            warnings.warn("vrdone_amd: an activation beyond the f16x3 mode's operand range (or non-finite inputs): repeating "
+            warnings.warn(f"vrdone_amd: an activation beyond the {ops.get_precision()} mode's operand range (or non-finite inputs): repeating "
                           "this video in the f32 mode")
             with ops.use_precision("f32"):
                 return self.forward_test(input_data)
@@ -1148,7 +1150,7 @@ class MaskVRD(nn.Module):
         f_dev = table_dev[:2 * P].view(torch.float32)
 
         ops = _ops()
-        f16 = ops.get_precision() == "f16x3"
+        f16 = ops.f16_planes()
         if f16:
             flag = ops.f16_range_flag(next(self.parameters()).device)
             flag.zero_()
@@ -1173,7 +1175,7 @@ class MaskVRD(nn.Module):
         V, N = len(live), self.n_max_pair
         if f16 and (host[-2] != 0 or host[-1] != 0):
             import warnings
-            warnings.warn("vrdone_amd: an activation beyond the f16x3 mode's operand range (or non-finite inputs) in a "
+            warnings.warn(f"vrdone_amd: an activation beyond the {ops.get_precision()} mode's operand range (or non-finite inputs) in a "
                           "multi-video call: repeating its videos one by one")
             for i in live:
                 results[i] = self.forward_test(videos[i])

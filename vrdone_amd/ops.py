@@ -103,12 +103,31 @@ def flash_pair_ok(n_head, channels, Tq):
 def pair_mode():
     """True when producers should emit pair rows for GEMM-only consumers: a split-precision mode and autograd not recording
     (a differentiable forward keeps every activation as plain f32 rows, see vrdone_amd/autograd.py)."""
-    return _precision in ("bf16x3", "f16x3") and not torch.is_grad_enabled()
+    return _precision in ("bf16x3", "f16x3", "f16x1") and not torch.is_grad_enabled()
 
 
 def pair_fmt():
     """enum vrd_pair_format of the current precision mode's pair rows and split weights (0 in the f32 mode)."""
-    return {"bf16x3": _hip.PAIR_BF16, "f16x3": _hip.PAIR_F16}.get(_precision, _hip.PAIR_NONE)
+    return {"bf16x3": _hip.PAIR_BF16, "f16x3": _hip.PAIR_F16, "f16x1": _hip.PAIR_F16}.get(_precision, _hip.PAIR_NONE)
+
+
+def f16_planes():
+    """True in the modes whose operands are f16 planes of power-of-two scaled values (f16x3, f16x1): the modes with an operand
+    range (f16_range_flag) and an f32 repeat when it is exceeded."""
+    return _precision in ("f16x3", "f16x1")
+
+
+def products():
+    """MFMA products per split-precision operand pair of the current mode, as vrd_gemm_args.products / vrd_attention_pair take
+    it: 1 in the f16x1 mode (a_hi * w_hi only), 0 (= the three-product form) otherwise."""
+    return 1 if _precision == "f16x1" else 0
+
+
+def check_differentiable(what="autograd"):
+    """The f16x1 mode is forward-only: anything that would record autograd in it raises ValueError."""
+    if _precision == "f16x1":
+        raise ValueError(f"{what}: the f16x1 precision mode is forward-only (one f16 product per GEMM / attention, no backward); "
+                         "run under torch.no_grad() or switch to f16x3 / bf16x3 / f32 for training")
 
 
 def split_backward():
@@ -158,7 +177,10 @@ def _fmt(pair):
 def recording(*tensors):
     """True when autograd is recording and one of the tensors needs a gradient: the op then runs as the
     torch.autograd.Function(s) of vrdone_amd/autograd.py (HIP kernels forward and backward)."""
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+    rec = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+    if rec:
+        check_differentiable()
+    return rec
 
 
 def join(buf, parts, dim=-1):
@@ -239,10 +261,15 @@ def packed_conv_weight(w):
 #            Activations beyond +-4094 overflow the f16 planes.  Every kernel that writes such planes reports it in a flag word
 #            on the device (f16_range_flag()); MaskVRD.forward_test, forward_training and forward_loss read the word with their
 #            results and repeat the call in the f32 mode; a direct caller of _mask_vrd checks f16_range_exceeded() itself.
+#   "f16x1": the f16x3 operands with ONE product, a_hi*w_hi (and in the global attention q_hi*k_hi, then p_hi*v_hi with the
+#            probabilities rounded once, f16(P * 2^4)): ~11 significand bits per operand.  An opt-in inference mode, NOT
+#            reference-grade: logits ~4e-3 and mask logits ~5e-2 from the reference (the north star's 1e-3 is missed), the same
+#            forward_test records on the golden videos.  Forward only: anything that would record autograd raises ValueError.
+#            Same range flag and f32 repeat as f16x3.  bench.py has no entry for it (scripts/precision_ab.py measures it).
 #   "f32":   exact f32 MFMA products (bit-level fmaf chains); logits within 9e-6; ~2.8x slower end to end (bench.py).
 # Select with set_precision() or the VRDONE_PRECISION environment variable.  Everything outside the
 # conv GEMMs and the global attention (LayerNorm, depthwise convs, softmax, banded attention) is f32 in all modes.
-_PRECISIONS = ("f32", "bf16x3", "f16x3")
+_PRECISIONS = ("f32", "bf16x3", "f16x3", "f16x1")
 _precision = os.environ.get("VRDONE_PRECISION", "f16x3")
 if _precision not in _PRECISIONS:
     raise ValueError(f"VRDONE_PRECISION must be one of {_PRECISIONS}, got {_precision!r}")
@@ -404,7 +431,7 @@ def presplit_weights(weights, plans):
     read and write outlive the dict entry.
     The job table is built (and uploaded) on the first call for a set of weights -- outside any graph capture: inside one,
     without a table, nothing is done and the per-weight launches run as before."""
-    if _precision not in ("bf16x3", "f16x3") or not weights or not _presplit_on:
+    if _precision not in ("bf16x3", "f16x3", "f16x1") or not weights or not _presplit_on:
         return
     fmt = pair_fmt()
     # (the plan is keyed on the weights' addresses, shapes and the element format: another model whose parameters land on
@@ -687,6 +714,8 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
     assert not (a_width and w_fmt != x_fmt) and not (out_pair and w_fmt != pair_fmt())
     if not _dgrad and w_fmt and (Cin * k) % 32 == 0:
         split_conv_weight(weight, w_fmt).set_args(a)
+        if w_fmt == _hip.PAIR_F16 and _split_fmt is None:
+            a.products = products()
     a.a_pair_width = a_width
     a.c_pair = _fmt(out_pair)
     if skip_rows is None:
@@ -929,7 +958,8 @@ def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=Non
             out = torch.empty(B, Tq, Cc, device=q.device, dtype=torch.float32)
         assert out.shape == (B, Tq, Cc) and out.is_contiguous()
         _hip.check(lib.vrd_attention_pair(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), _mask_ptr(q_mask, B * Tq), B, Tq, Tk, n_head,
-                                          Cc // n_head, out.data_ptr(), Cc, fmt if pair else 0, fmt, _stream()),
+                                          Cc // n_head, out.data_ptr(), Cc, fmt if pair else 0, fmt, _stream(),
+                                          products() if fmt == _hip.PAIR_F16 else 0),
                    "vrd_attention_pair")
         return Pair(out, Cc, fmt) if pair else out
     B, Tq, Cc = q.shape
