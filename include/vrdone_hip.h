@@ -35,6 +35,20 @@ extern "C" {
 
 #define VRD_ABI_VERSION 36
 
+/* `flags` of the parameter-gradient entry points (vrd_gemm_wgrad, vrd_gemm_wgrad_x3, vrd_colsum, vrd_dwconv_wgrad,
+ * vrd_layernorm_bwd).  VRD_DETERMINISTIC: the result is a function of the inputs and the shapes alone -- the same bits
+ * whatever the workgroup schedule, the operands' alignment, the scratch offered or the device's CU count.  No float atomic
+ * is used: every cross-workgroup sum is stored as partials and added up in index order (row chunk, then partial row) by
+ * further launches; the chunking assumes a fixed 256 CUs, and where a float4 and a scalar form exist the choice follows the
+ * shapes and leading dimensions (misaligned rows are read with scalar loads in the float4 form's order).  The call then NEEDS
+ * its scratch (16-byte aligned, at least the floats listed at each entry point): missing or too little is VRD_ERR_SCRATCH
+ * before any launch, and vrd_scratch_required() stores the floats that call needed (of the calling thread's last such failure).  Without the flag every call behaves
+ * as it did before `flags` existed.  (The version number stays 36: a library built before these arguments lacks the
+ * vrd_scratch_required symbol, which the Python binding requires.) */
+#define VRD_DETERMINISTIC 1
+#define VRD_ERR_SCRATCH (-3)
+int vrd_scratch_required(int64_t* floats);
+
 enum vrd_act { VRD_ACT_NONE = 0, VRD_ACT_RELU = 1, VRD_ACT_GELU = 2 };
 
 /* Element format of pair rows and of the split weight operand (W_split).  Both replace an f32 product a*w by
@@ -424,7 +438,8 @@ int vrd_select_triplets(const vrd_select_args* a, void* stream);
 /* ====================================================================================================================
  * Backward kernels (training step: the reference differentiates its ATen graph with autograd, train.py:186;
  * models/maskvrd.py:168-198).  All f32 rows (no pair rows).  Parameter gradients are ACCUMULATED (+=) into buffers the
- * caller zeroes; where several workgroups add to one element the order (last bits) varies between runs.
+ * caller zeroes; where several workgroups add to one element the order (last bits) varies between runs, unless the call
+ * passes VRD_DETERMINISTIC in its `flags`.
  * The forward of a training step runs the same forward kernels, less fused, so that every op has saved inputs:
  *   y = vrd_gemm(x, W, b, row_mask)                       dense conv, mask only
  *   u = vrd_activation(y)                                        GELU / ReLU
@@ -434,8 +449,10 @@ int vrd_select_triplets(const vrd_select_args* a, void* stream);
 /* Weight gradient of vrd_gemm's convolution (models/blocks.py:99 under autograd):
  *   dW[n, tap*Cin + ci] += sum_r G[r, n] * row_mask[r] * X[r + tap - taps/2, ci]      (rows outside r's length-T sequence: 0)
  * dW is (N, taps*Cin) tap-major like vrd_gemm's W.  f32 MFMA, exact f32 products. */
+/* VRD_DETERMINISTIC: with C = ceil(M / 512) > 1 row chunks, `scratch` takes C * N * taps * Cin floats of partial tiles (unused
+ * otherwise: may be NULL). */
 int vrd_gemm_wgrad(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
-                   int taps, int T, float* dW, void* stream);
+                   int taps, int T, float* dW, float* scratch, int64_t scratch_floats, void* stream, int flags);
 
 /* The same gradient in the split precision of the forward path (bf16x3 mode): every product as g_lo x_hi + g_hi x_lo + g_hi x_hi
  * on v_mfma_f32_32x32x16_bf16, f32 accumulate (~2^-17 relative product error, ~5x the rate of the exact-f32 MFMA).  Same
@@ -448,9 +465,13 @@ int vrd_gemm_wgrad(const float* G, int64_t ldg, const float* X, int64_t ldx, con
  * order of the additions then varies from run to run).
  * g_scale (nullable): device pointer to {2^e, 2^-e} from vrd_absmax_scale(G): the products are then formed on f16 planes --
  * G * 2^e, X * 2^VRD_F16_ACT_EXP -- at ~2^-22 relative error (the f16x3 mode's backward); NULL: bf16 planes, ~2^-17. */
+/* VRD_DETERMINISTIC: no atomics (bias sums included); scratch: with c <= min(512, ceil(M / 128)) row chunks (c = 1 below 256 rows),
+ * c * N * K floats of partial tiles when c > 1, plus (dbias) c * N + ceil(c / 32) * N floats of bias partials -- with c = 1 and
+ * fewer than 256 rows up to 9 * N; c * (N * K + 2 * N) + 9 * N floats always suffice.  The chunks follow from the shapes and a
+ * fixed 256-CU figure; VRD_WGRAD_LDS / VRD_WGRAD_BIG are not consulted. */
 int vrd_gemm_wgrad_x3(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
                       int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, const float* g_scale,
-                      void* stream);
+                      void* stream, int flags);
 
 /* scale[0] = 2^e, scale[1] = 2^-e with e such that max |x| * 2^e lies in [2^13, 2^14) over the (rows x cols) matrix x (e = 0 for
  * an all-zero or non-finite matrix; |e| <= 100): the power-of-two factor that puts a tensor of unknown range -- a gradient -- into
@@ -467,9 +488,12 @@ int vrd_absmax_scale(const float* x, int64_t ldx, int64_t rows, int cols, float*
  * `scratch` (nullable, 16-byte aligned; 1,024 * C floats always suffice) as in vrd_layernorm_bwd, used when b is NULL or lies on the
  * rows of a (b_cstride = b_rstride = 1, no offset, no shift) and the rows are float4-aligned: the row blocks' partial sums, added
  * up by a second launch instead of one float atomic per column and workgroup. */
+/* VRD_DETERMINISTIC: every form stores its P row blocks' sums (P <= 1,024 up to 2 M rows, ceil(rows / 2,048) beyond) and adds them
+ * up in a fixed tree: P * C + ceil(P / 32) * C (+ ceil(P / 1,024) * C ...) floats of scratch, always -- 1,057 * C suffice up to
+ * 2 M rows. */
 int vrd_colsum(const float* a, int64_t lda, const float* b, int64_t ldb, int b_cstride, int b_coffset, int b_rstride, int shift,
                int T, const uint8_t* row_mask, const float* row_scale, int64_t rows, int C, float* out, float* scratch,
-               int64_t scratch_floats, void* stream);
+               int64_t scratch_floats, void* stream, int flags);
 
 /* Weight and bias gradient of a depthwise MaskedConv1D (models/blocks.py:91-113 under autograd; k = 1 / 3, `stride`, group_in
  * = 1 or 2 inputs per group) in one pass over dD (rows x C, rows = B * T output rows):
@@ -477,9 +501,11 @@ int vrd_colsum(const float* a, int64_t lda, const float* b, int64_t ldb, int b_c
  *   (C, group_in, ksize) layout),  dbias[c] += sum_r dD[r, c] * row_mask[r]
  * in_row(r = s*T + t, kk) = s * stride*T + stride*t + kk - ksize/2 where that stays inside sequence s; dbias may be NULL.
  * `scratch` (nullable; 1,024 * 4 C floats always suffice): as in vrd_colsum, for ksize 3, group_in 1 and float4-aligned rows. */
+/* VRD_DETERMINISTIC: as vrd_colsum with W = C * group_in * ksize (+ C with dbias) columns: P * W + ceil(P / 32) * W (...) floats,
+ * always. */
 int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
                      const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch, int64_t scratch_floats,
-                     void* stream);
+                     void* stream, int flags);
 
 /* out[r,c] = v[r,c] * col_scale[c] * row_scale[r] * row_mask[r] + res[r,c] * (res_masked ? row_mask[r] : 1) + res2[r,c]
  * (every factor / term optional).  Training form of the affine drop-path residual: models/blocks.py:1074-1076 with
@@ -497,9 +523,11 @@ int vrd_activation(const float* x, int64_t ldx, const float* dy, int64_t lddy, i
  * ReLU(LN(x)).  dx written; dgamma / dbeta (C floats each) accumulated.  `scratch` (nullable, 16-byte aligned;
  * ceil(rows / 32) * 2 C floats always suffice, ~520 * 2 C up to 131,072 rows) takes the workgroups' partial column sums, which a second launch adds up; without it every workgroup
  * ends in one float atomic per channel, and atomics on one address are retired one after the other. */
+/* VRD_DETERMINISTIC: the partial sums always, P = ceil(rows / (4 * rows per wave)) rows of them: P * 2 C + ceil(P / 32) * 2 C (...)
+ * floats (the bound above plus 1 / 31 of it). */
 int vrd_layernorm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t rows, int C, const float* gamma,
                       const float* beta, int relu, float* dx, int64_t lddx, float* dgamma, float* dbeta, float* scratch,
-                      int64_t scratch_floats, void* stream);
+                      int64_t scratch_floats, void* stream, int flags);
 
 /* Input gradient of the depthwise convolution of vrd_dwconv_ln (without its LayerNorms: in a training step those run as
  * separate vrd_layernorm calls): dD[o] = gradient w.r.t. the masked conv output of set o, (B*Tin/stride, C) rows;

@@ -53,8 +53,10 @@ def synthetic_batch(cfg, c_in, device, n_pairs=24, seed=0):
 
 
 def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, ema_decay=0.999, verbose=True, drop_path=True,
-        graphs=False, config="vidvrd", n_pairs=24, profile=False):
-    from vrdone_amd import _hip, configs, synth
+        graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False):
+    from vrdone_amd import _hip, configs, ops, synth
+    if deterministic:
+        ops.set_deterministic(True)           # bit-reproducible steps (vrdone_amd/ops.py); the log then carries their sha256
     from vrdone_amd.models.maskvrd import MaskVRD
     cfg = configs.model_config(config)
     torch.manual_seed(seed)
@@ -104,7 +106,20 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         for key, params in (("param_delta_norm", model.parameters()), ("ema_delta_norm", ema.module.parameters())):
             norms = torch._foreach_norm(torch._foreach_sub([p.detach() for p in params], start))
             log[key] = float(torch.linalg.vector_norm(torch.stack(norms)))
+    if deterministic:
+        log["sha256"] = state_digest(model, ema)
     return log
+
+
+def state_digest(model, ema):
+    """sha256 over the bytes of every gradient of the last step, every parameter and every EMA tensor, in module order."""
+    import hashlib
+    h = hashlib.sha256()
+    tensors = [p.grad for p in model.parameters() if p.grad is not None] + [p.detach() for p in model.parameters()]
+    tensors += list(ema.module.state_dict().values())
+    for t in tensors:
+        h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
 
 
 if __name__ == "__main__":
@@ -115,5 +130,7 @@ if __name__ == "__main__":
     ap.add_argument("--config", default="vidvrd", help="vidvrd (24 pairs x 96 frames) | vidor (48 pairs x 512 frames: --pairs 48)")
     ap.add_argument("--pairs", type=int, default=24)
     ap.add_argument("--profile", action="store_true", help="per-kernel-family HIP-event time of the last step")
+    ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps; prints the sha256 of gradients, parameters, EMA")
     args = ap.parse_args()
-    print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile)))
+    print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile,
+                         deterministic=args.deterministic)))

@@ -186,19 +186,20 @@ _SIGNATURES = {
     "vrd_select_triplets": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),
     # ---- backward kernels (training step)
     "vrd_gemm_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                 c_f32p, C.c_void_p]),
+                                 c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
     "vrd_gemm_wgrad_x3": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
-                                    c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
+                                    c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_int]),
+    "vrd_scratch_required": (C.c_int, [C.POINTER(C.c_int64)]),
     "vrd_absmax_scale": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, C.c_void_p]),
     "vrd_dwconv_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p, C.c_int64,
-                                   C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p]),
+                                   C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
     "vrd_colsum": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p, c_f32p,
-                             C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int64, C.c_void_p]),
+                             C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
     "vrd_rowcol_scale": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, c_f32p, c_u8p, c_f32p, C.c_int64, C.c_int,
                                    c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_void_p]),
     "vrd_activation": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, C.c_int, c_f32p, C.c_int64, C.c_void_p]),
     "vrd_layernorm_bwd": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p,
-                                    C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p]),
+                                    C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
     "vrd_dwconv_bwd": (C.c_int, [C.POINTER(DwconvBwdArgs), C.c_void_p]),
     "vrd_local_attn_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, c_f32p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
@@ -221,9 +222,27 @@ _SIGNATURES = {
 
 ABI_VERSION = 36
 
+# `flags` of the parameter-gradient entry points (include/vrdone_hip.h): bit-reproducible sums, no float atomics; such a call
+# fails with ERR_SCRATCH (before any launch) when its scratch is short, and lib.vrd_scratch_required() says how many floats it needs
+DETERMINISTIC = 1
+ERR_SCRATCH = -3
+
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+# entry points whose trailing `flags` argument came with the deterministic mode: a caller written before it may leave it out (0)
+_FLAGS_DEFAULT = ("vrd_gemm_wgrad_x3", "vrd_colsum", "vrd_dwconv_wgrad", "vrd_layernorm_bwd")
+
+
+def _flags_default(fn):
+    n = len(fn.argtypes)
+
+    def call(*args):
+        return fn(*args, 0) if len(args) == n - 1 else fn(*args)
+    call.__name__, call.argtypes, call.restype = fn.__name__, fn.argtypes, fn.restype
+    return call
 
 
 def _load():
@@ -240,6 +259,8 @@ def _load():
         fn = getattr(lib, name)        # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
+    for name in _FLAGS_DEFAULT:
+        setattr(lib, name, _flags_default(getattr(lib, name)))
     got = lib.vrd_abi_version()
     if got != ABI_VERSION:
         raise HipLibraryError(f"libvrdone_hip.so ABI {got} != expected {ABI_VERSION}: rebuild it")

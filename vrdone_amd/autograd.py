@@ -40,45 +40,64 @@ def _dense(t):
 
 _partial_scratch = {}
 _PARTIAL_SUMS = os.environ.get("VRD_PARTIAL_SUMS", "1") != "0"      # A/B switch: 0 = the gradient kernels end in float atomics
+                                                                    # (not in the deterministic mode, which has none)
 
 
-def _partials(device):
+def _partials(device, det=False, need=0):
     """The buffer the gradient kernels park their workgroups' partial sums in before a second launch adds them up (users:
     vrd_gemm_wgrad_x3 -- the row chunks' partial tiles, include/vrdone_hip.h: 4 * CUs * 16,384 + N * K floats suffice --,
     vrd_layernorm_bwd, vrd_colsum and vrd_dwconv_wgrad; sized for weights of up to 4 M elements, beyond that the wgrad kernel
     falls back to atomics).  It is only ever live between two adjacent launches of ONE stream, so there is one per (device,
     stream): two backward passes on different streams of a device (two replicas in a process, autograd on a side stream) each
     get their own.  Launches recorded into a graph allocate theirs per call from the graph's private pool (a buffer cached
-    from one recording's pool must not be written by another recording's replays)."""
+    from one recording's pool must not be written by another recording's replays).
+    Deterministic mode (`det`): the kernels need their scratch and say how much (_grad_call); `need` floats grows the buffer to
+    that -- the largest call of a step decides, without the 4 M-element cap."""
     dev = torch.device(device)
-    if not _PARTIAL_SUMS:
+    if not _PARTIAL_SUMS and not det:
         key = (dev, None)
         if key not in _partial_scratch:
             _partial_scratch[key] = torch.empty(0, device=dev, dtype=torch.float32)
         return _partial_scratch[key]
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    n = 4 * cus * 16384 + (4 << 20)
+    n = max(4 * cus * 16384 + (4 << 20), need)
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(n, device=dev, dtype=torch.float32)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     buf = _partial_scratch.get(key)
-    if buf is None:
+    if buf is None or buf.numel() < n:
         buf = _partial_scratch[key] = torch.empty(n, device=dev, dtype=torch.float32)
     return buf
 
 
+def _grad_call(device, det, launch, what):
+    """launch(scratch) -> return code of a parameter-gradient entry point given `scratch` and the mode's flags; in the
+    deterministic mode a call whose scratch was short (VRD_ERR_SCRATCH: nothing launched) is repeated with the size it asked for."""
+    rc = launch(_partials(device, det))
+    if det and rc == _hip.ERR_SCRATCH:
+        need = C.c_int64(0)
+        check(lib.vrd_scratch_required(C.byref(need)), "vrd_scratch_required")
+        rc = launch(_partials(device, det, need.value))
+    check(rc, what)
+
+
 # ---------------------------------------------------------------------------------------------- raw launchers
-def colsum(a, out, *, b=None, b_cstride=1, b_coffset=0, b_rstride=1, shift=0, T=1, row_mask=None, row_scale=None):
-    """out[c] += sum_r a[r,c] * b[...] * mask[r] * row_scale[r]  (vrd_colsum)."""
+def colsum(a, out, *, b=None, b_cstride=1, b_coffset=0, b_rstride=1, shift=0, T=1, row_mask=None, row_scale=None, det=None):
+    """out[c] += sum_r a[r,c] * b[...] * mask[r] * row_scale[r]  (vrd_colsum; det: deterministic sums, default: the current mode)."""
     pa, rows, cols, lda = _rows(a)
     pb, ldb = (None, 0)
     if b is not None:
         pb, _, _, ldb = _rows(b)
     assert out.numel() == cols and out.is_contiguous() and out.dtype == torch.float32
-    part = _partials(a.device)
-    check(lib.vrd_colsum(pa, lda, pb, ldb, b_cstride, b_coffset, b_rstride, shift, T, _mask_ptr(row_mask, rows),
-                         _ptr(row_scale), rows, cols, out.data_ptr(), part.data_ptr(), part.numel(), _stream()), "vrd_colsum")
+    det = ops.get_deterministic() if det is None else det
+    _grad_call(a.device, det, lambda part: lib.vrd_colsum(pa, lda, pb, ldb, b_cstride, b_coffset, b_rstride, shift, T,
+                                                          _mask_ptr(row_mask, rows), _ptr(row_scale), rows, cols, out.data_ptr(),
+                                                          part.data_ptr(), part.numel(), _stream(), _flags(det)), "vrd_colsum")
     return out
+
+
+def _flags(det):
+    return _hip.DETERMINISTIC if det else 0
 
 
 def rowcol_scale(v, *, col_scale=None, row_scale=None, row_mask=None, res=None, res_masked=False, res2=None):
@@ -178,6 +197,7 @@ class Linear(_Differentiable):
         # the backward runs in the arithmetic of ITS forward, whatever the mode is by then (MaskVRD.forward_training repeats a
         # step whose activations leave the f16 range in the f32 mode: the graph it returns is differentiated outside that block)
         ctx.split_bwd, ctx.bfmt = ops.split_backward(), ops.backward_fmt()
+        ctx.det = ops.get_deterministic()             # (so is the deterministic mode)
         return y
 
     @staticmethod
@@ -226,24 +246,27 @@ class Linear(_Differentiable):
                 # its own power-of-two factor); the bias gradient (exact f32 column sums) in the same pass
                 if want_db:
                     db = _zeros(N, device=dy.device)
-                part = _partials(dy.device)
                 if ctx.bfmt == PAIR_F16:
                     if not (ctx.needs_input_grad[0] and gs is not None):
                         gs = ops.grad_scale(dy)
                 else:
                     gs = None
-                check(lib.vrd_gemm_wgrad_x3(pg, ldg, px, ldx, _mask_ptr(mask, rows), rows, N, Cin, k, T, packed.data_ptr(),
-                                            db.data_ptr() if want_db else None, part.data_ptr(), part.numel(),
-                                            gs.data_ptr() if gs is not None else None, _stream()),
-                      "vrd_gemm_wgrad_x3")
+                pdb = db.data_ptr() if want_db else None
+                _grad_call(dy.device, ctx.det, lambda part: lib.vrd_gemm_wgrad_x3(
+                    pg, ldg, px, ldx, _mask_ptr(mask, rows), rows, N, Cin, k, T, packed.data_ptr(), pdb, part.data_ptr(), part.numel(),
+                    gs.data_ptr() if gs is not None else None, _stream(), _flags(ctx.det)), "vrd_gemm_wgrad_x3")
                 want_db = False
-            else:            # exact f32 products
-                check(lib.vrd_gemm_wgrad(pg, ldg, px, ldx, _mask_ptr(mask, rows), rows, N, Cin, k, T, packed.data_ptr(), _stream()),
-                      "vrd_gemm_wgrad")
+            elif ctx.det:    # exact f32 products
+                _grad_call(dy.device, True, lambda part: lib.vrd_gemm_wgrad(
+                    pg, ldg, px, ldx, _mask_ptr(mask, rows), rows, N, Cin, k, T, packed.data_ptr(), part.data_ptr(), part.numel(),
+                    _stream(), _hip.DETERMINISTIC), "vrd_gemm_wgrad")
+            else:            # (without the flag the kernel takes no scratch)
+                check(lib.vrd_gemm_wgrad(pg, ldg, px, ldx, _mask_ptr(mask, rows), rows, N, Cin, k, T, packed.data_ptr(), None, 0,
+                                         _stream(), 0), "vrd_gemm_wgrad")
             # tap-major -> the Conv1d layout (N, Cin, k), with the parameter's own strides (DDP's bucket views expect them)
             dw = packed.view(N, Cin, 1) if k == 1 else packed.view(N, k, Cin).permute(0, 2, 1).contiguous()
         if want_db:
-            db = colsum(dy, _zeros(N, device=dy.device), row_mask=mask)
+            db = colsum(dy, _zeros(N, device=dy.device), row_mask=mask, det=ctx.det)
         return dx, dw, db, None
 
 
@@ -268,6 +291,7 @@ class ScaleResidual(_Differentiable):
         ctx.save_for_backward(v, scale if scale is not None else v.new_empty(0))
         ctx.has_scale = scale is not None
         ctx.row_scale, ctx.row_mask, ctx.res_masked = row_scale, row_mask, res_masked
+        ctx.det = ops.get_deterministic()
         return rowcol_scale(v, col_scale=scale, row_scale=row_scale, row_mask=row_mask, res=res, res_masked=res_masked, res2=res2)
 
     @staticmethod
@@ -280,7 +304,7 @@ class ScaleResidual(_Differentiable):
             dv = rowcol_scale(dy, col_scale=scale, row_scale=ctx.row_scale, row_mask=ctx.row_mask)
         if scale is not None and ctx.needs_input_grad[1]:
             ds = colsum(dy, _zeros(v.shape[-1], device=dy.device), b=v, T=1,
-                        row_mask=ctx.row_mask, row_scale=ctx.row_scale).view_as(scale)
+                        row_mask=ctx.row_mask, row_scale=ctx.row_scale, det=ctx.det).view_as(scale)
         if ctx.needs_input_grad[4]:
             dres = rowcol_scale(dy, row_mask=ctx.row_mask) if (ctx.res_masked and ctx.row_mask is not None) else dy
         if ctx.needs_input_grad[6]:
@@ -296,6 +320,7 @@ class LayerNormFn(_Differentiable):
         y = ops.layernorm(x, gamma, beta, relu=relu, post_add=post_add)
         ctx.save_for_backward(x, gamma, beta)
         ctx.relu, ctx.period = relu, None if post_add is None else post_add.shape[0]
+        ctx.det = ops.get_deterministic()
         return y
 
     @staticmethod
@@ -308,15 +333,14 @@ class LayerNormFn(_Differentiable):
         pdx, _, _, lddx = _rows(dx)
         dg = _zeros(cols, device=x.device)
         db = _zeros(cols, device=x.device)
-        part = _partials(dy.device)
-        check(lib.vrd_layernorm_bwd(px, ldx, pd, ldd, rows, cols, gamma.data_ptr(), beta.data_ptr(), 1 if ctx.relu else 0,
-                                    pdx, lddx, dg.data_ptr(), db.data_ptr(), part.data_ptr(), part.numel(), _stream()),
-              "vrd_layernorm_bwd")
+        _grad_call(dy.device, ctx.det, lambda part: lib.vrd_layernorm_bwd(
+            px, ldx, pd, ldd, rows, cols, gamma.data_ptr(), beta.data_ptr(), 1 if ctx.relu else 0, pdx, lddx, dg.data_ptr(),
+            db.data_ptr(), part.data_ptr(), part.numel(), _stream(), _flags(ctx.det)), "vrd_layernorm_bwd")
         dpost = None
         if ctx.period is not None and ctx.needs_input_grad[4]:
             # y[r] += post_add[r % period]: sum dy over the rows of each residue = column sums of the (rows/period, period*C) view
             dpost = colsum(dy.reshape(rows // ctx.period, ctx.period * cols),
-                           _zeros(ctx.period * cols, device=x.device)).view(ctx.period, cols)
+                           _zeros(ctx.period * cols, device=x.device), det=ctx.det).view(ctx.period, cols)
         return dx, dg.view_as(gamma), db.view_as(beta), None, dpost
 
 
@@ -330,6 +354,7 @@ class DepthwiseConv(_Differentiable):
         outs = ops.dwconv_ln(x, [dict(weight=w, bias=b) for w, b in zip(ws, bs)], mask_out=mask_out, stride=stride, x_up=x_up)
         ctx.save_for_backward(x, *( [x_up] if x_up is not None else [] ), *ws)
         ctx.has_up, ctx.mask_out, ctx.stride, ctx.has_bias = x_up is not None, mask_out, stride, [b is not None for b in bs]
+        ctx.det = ops.get_deterministic()
         return tuple(outs)
 
     @staticmethod
@@ -367,10 +392,10 @@ class DepthwiseConv(_Differentiable):
             gw = _zeros(Cout, gin, k, device=dev)          # the parameter's own layout and strides (DDP's bucket views expect them)
             gb = _zeros(Cout, device=dev) if ctx.has_bias[i] else None
             pd, rows_out, _, ldd = _rows(dDs[i])
-            part = _partials(dev)
-            check(lib.vrd_dwconv_wgrad(pd, ldd, pxin, ldxin, k, s, gin, Tout, _mask_ptr(ctx.mask_out, rows_out), rows_out, Cout,
-                                       gw.data_ptr(), gb.data_ptr() if gb is not None else None, part.data_ptr(), part.numel(),
-                                       _stream()), "vrd_dwconv_wgrad")
+            pgb = gb.data_ptr() if gb is not None else None
+            _grad_call(dev, ctx.det, lambda part: lib.vrd_dwconv_wgrad(
+                pd, ldd, pxin, ldxin, k, s, gin, Tout, _mask_ptr(ctx.mask_out, rows_out), rows_out, Cout, gw.data_ptr(), pgb,
+                part.data_ptr(), part.numel(), _stream(), _flags(ctx.det)), "vrd_dwconv_wgrad")
             grads.append(gw)
             grads.append(gb)
         return (dx, dx_up, None, None, *grads)

@@ -6,7 +6,10 @@
 // rows for vidvrd.yaml; 48 x 512 for vidor), so these kernels are written for correctness and sane memory access
 // (coalesced rows, one wave per row, f32 MFMA for the one real contraction), not tuned like the forward path.
 // Everything is f32; parameter gradients are ACCUMULATED (+=) into caller-zeroed buffers with float atomics where
-// several workgroups contribute to the same element (summation order, hence the last bits, vary from run to run).
+// several workgroups contribute to the same element (summation order, hence the last bits, vary from run to run) -- unless
+// the caller sets VRD_DETERMINISTIC: then every cross-workgroup sum is stored as partials and added up in index order by a
+// second launch, the chunking assumes a fixed DET_CUS compute units and no form is chosen by pointer alignment (DET
+// template arguments below; the atomics that remain sit in the !DET branches).
 //
 //  vrd_gemm_wgrad      dW of a dense conv (k = 1 / 3):  dW[n, tap*Cin+ci] += sum_r G[r,n] X[r+tap-1, ci]   (f32 MFMA)
 //  vrd_colsum          out[c] += sum_r a[r,c] * b[s*r+shift, c*bc+bo] * mask[r] * rscale[r]: bias, drop-path-scale,
@@ -41,7 +44,10 @@ inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr
 // X[r0 + (lane >> 5) + shift][ci]: 128-byte row segments), accumulates in f32 and adds its partial tile atomically.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int WG_CHUNK = 128;      // rows per wave
+constexpr int DET_CUS = 256;       // deterministic mode: the CU count every chunking assumes (a function of the shapes only)
 
+// DET: with several row chunks dW is the (chunks, N, K) array of the blocks' partial tiles (summed by wgrad_reduce_kernel)
+template <bool DET>
 __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ G, int64_t ldg, const float* __restrict__ X,
                                                     int64_t ldx, const uint8_t* __restrict__ row_mask, int64_t M, int N,
                                                     int Cin, int taps, int T, int tiles_k, float* __restrict__ dW) {
@@ -153,6 +159,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ G,
             const int nn = n0 + 32 * (q >> 1) + (e & 3) + 8 * (e >> 2) + 4 * lh;
             if (nn < N) {
                 if (single) dW[(int64_t)nn * K + j] += v[e];         // (dW holds the caller's initial value: zeros)
+                else if (DET) dW[((int64_t)blockIdx.y * N + nn) * K + j] = v[e];
                 else atomicAdd(dW + (int64_t)nn * K + j, v[e]);
             }
         }
@@ -190,7 +197,7 @@ __device__ __forceinline__ WFragT<F16> wsplit8(const float (&v)[8], float mul) {
     return f;
 }
 
-template <bool F16>
+template <bool F16, bool DET>
 __global__ __launch_bounds__(256) void wgrad_x3_kernel(const float* __restrict__ G, int64_t ldg, const float* __restrict__ X,
                                                        int64_t ldx, const uint8_t* __restrict__ row_mask, int64_t M, int N,
                                                        int Cin, int taps, int T, int tiles_k, int chunk, float* __restrict__ dW,
@@ -299,6 +306,7 @@ __global__ __launch_bounds__(256) void wgrad_x3_kernel(const float* __restrict__
             const int nn = n0 + 32 * (q >> 1) + (e & 3) + 8 * (e >> 2) + 4 * lh;
             if (nn < N) {
                 if (single) dW[(int64_t)nn * K + j] += v[e] * unscale;
+                else if (DET) dW[((int64_t)blockIdx.y * N + nn) * K + j] = v[e] * unscale;      // (as in wgrad_kernel)
                 else atomicAdd(dW + (int64_t)nn * K + j, v[e] * unscale);
             }
         }
@@ -336,7 +344,9 @@ typedef __attribute__((ext_vector_type(4))) short wl_s16x4;
 typedef __attribute__((address_space(3))) wl_s16x4* wl_lds_s16x4_ptr;
 typedef __attribute__((ext_vector_type(8))) short wl_s16x8;
 
-template <int BIG, bool VEC, int TAPS, bool F16>
+// DET: `partial` is set whenever there are several chunks; the bias sums of several chunks then follow its chunks x N x K
+// partial tiles as chunks x N rows
+template <int BIG, bool VEC, int TAPS, bool F16, bool DET>
 __global__ __launch_bounds__(WlGeo<BIG>::NTHR, BIG ? 1 : 2) void wgrad_x3_lds_kernel(
     const float* __restrict__ G, int64_t ldg, const float* __restrict__ X, int64_t ldx, const uint8_t* __restrict__ row_mask, int64_t M,
     int N, int Cin, int T, int tiles_k, int chunk, float* __restrict__ dW, float* __restrict__ dbias, float* __restrict__ partial,
@@ -582,7 +592,9 @@ __global__ __launch_bounds__(WlGeo<BIG>::NTHR, BIG ? 1 : 2) void wgrad_x3_lds_ke
             float t = 0.f;
 #pragma unroll
             for (int q = 0; q < 8; ++q) t += red[q * TILE + tid];
-            atomicAdd(dbias + n0 + tid, t);
+            if (!DET) atomicAdd(dbias + n0 + tid, t);
+            else if (gridDim.y == 1) dbias[n0 + tid] += t;
+            else partial[((int64_t)gridDim.y * K + chunk_id) * N + n0 + tid] = t;
         }
     }
     // the chunk's share of the tile: straight into dW when there is one chunk; otherwise as plain stores into the chunk's slice of
@@ -601,7 +613,7 @@ __global__ __launch_bounds__(WlGeo<BIG>::NTHR, BIG ? 1 : 2) void wgrad_x3_lds_ke
             const int nn = n0 + 64 * wn + 32 * hn + (e & 3) + 8 * (e >> 2) + 4 * lh;
             if (nn < N) {
                 if (single) dst[(int64_t)nn * K + j] += acc[hn][hj][e] * unscale;
-                else if (partial) dst[(int64_t)nn * K + j] = acc[hn][hj][e] * unscale;
+                else if (DET || partial) dst[(int64_t)nn * K + j] = acc[hn][hj][e] * unscale;
                 else atomicAdd(dst + (int64_t)nn * K + j, acc[hn][hj][e] * unscale);
             }
         }
@@ -609,12 +621,14 @@ __global__ __launch_bounds__(WlGeo<BIG>::NTHR, BIG ? 1 : 2) void wgrad_x3_lds_ke
 }
 
 // dW[i] += sum_c partial[c * NK + i]: the row chunks' partial tiles of wgrad_x3_lds_kernel, in chunk order (so the sum does not
-// depend on the order the blocks ran in, as the atomics' did).  float4 per thread when NK % 4 == 0.
+// depend on the order the blocks ran in, as the atomics' did).  float4 per thread when NK % 4 == 0 (and V4: both buffers
+// 16-byte aligned); the scalar form adds in the same order.
+template <bool V4>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int chunks, int64_t NK,
                                                            float* __restrict__ dW) {
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= NK) return;
-    if ((NK & 3) == 0) {
+    if (V4 && (NK & 3) == 0) {
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
         int c = 0;
         for (; c + 4 <= chunks; c += 4) {       // four loads in flight
@@ -641,52 +655,129 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
+// out[c] += sum_p partial[p * cols + c]: the per-block column sums of a kernel whose blocks would otherwise each end in one
+// atomic per column (atomics on one address are worked off one after the other, ~50 ns each: 512 blocks = 25 us).  Block =
+// 64 columns x 32 partial rows (a wave takes eight of them), one atomic per column and block: parts / 32 per address.
+// DET: no atomics -- with one row of blocks the sum is added to out, otherwise it becomes row blockIdx.y of `next`, which the
+// next launch of the chain reduces the same way (det_colreduce): the tree is fixed by `parts` alone.
+template <bool DET>
+__global__ __launch_bounds__(256) void colpartial_reduce_kernel(const float* __restrict__ partial, int parts, int cols,
+                                                                float* __restrict__ out0, float* __restrict__ out1, int split,
+                                                                float* __restrict__ next) {
+    __shared__ float red[3][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const int p0 = blockIdx.y * 32 + wave * 8;
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = (c < cols && p0 + q < parts) ? partial[(int64_t)(p0 + q) * cols + c] : 0.f;
+    float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+    if (wave > 0) red[wave - 1][lane] = s;
+    __syncthreads();
+    if (wave == 0 && c < cols) {
+        s += red[0][lane] + red[1][lane] + red[2][lane];
+        if (!DET) atomicAdd(c < split ? out0 + c : out1 + (c - split), s);
+        else if (gridDim.y == 1) *(c < split ? out0 + c : out1 + (c - split)) += s;
+        else next[(int64_t)blockIdx.y * cols + c] = s;
+    }
+}
+
+// Deterministic mode: floats the chain of colpartial_reduce_kernel<true> launches needs behind `parts` partial rows of `cols` columns
+int64_t det_reduce_extra(int64_t parts, int64_t cols) {
+    int64_t extra = 0;
+    while (parts > 32) {
+        parts = (parts + 31) / 32;
+        extra += parts * cols;
+    }
+    return extra;
+}
+
+// out0[c] (c < split) / out1[c - split] += sum_p partial[p * cols + c] in a fixed tree: 32 partial rows per block, level by level
+// (the levels' rows follow the parts x cols rows in the same buffer)
+int det_colreduce(float* partial, int64_t parts, int cols, float* out0, float* out1, int split, hipStream_t s) {
+    float* src = partial;
+    float* dst = partial + parts * cols;
+    for (;;) {
+        const int64_t gy = (parts + 31) / 32;
+        hipLaunchKernelGGL(colpartial_reduce_kernel<true>, dim3((unsigned)((cols + 63) / 64), (unsigned)gy), dim3(256), 0, s, src, (int)parts,
+                           cols, out0, out1, split, dst);
+        VRD_LAUNCH_CHECK();
+        if (gy == 1) return 0;
+        src = dst;
+        dst += gy * cols;
+        parts = gy;
+    }
+}
+
 constexpr int WL_BIG_ROWS = 256;     // rows per block from which the 256 x 256 tiles pay
 
 // one launch of wgrad_x3_lds_kernel<BIG, ...> (+ the reduction of its partial tiles): as few row chunks as still give
 // 2 (BIG: 1) blocks per CU
+// Row chunks of wgrad_x3_lds_kernel<BIG>: as few as still give 2 (BIG: 1) blocks per CU
 template <int BIG>
-int launch_wgrad_lds(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
-                     int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, bool vec, int n_cu, hipStream_t s,
-                     const float* gscale) {
+int64_t wgrad_lds_chunk(int64_t M, int N, int K, int n_cu) {
     using Geo = WlGeo<BIG>;
-    const int K = Cin * taps;
-    const int tiles_n = (N + Geo::TILE - 1) / Geo::TILE, tiles_k = (K + Geo::TILE - 1) / Geo::TILE;
-    const int64_t tiles = (int64_t)tiles_n * tiles_k;
+    const int64_t tiles = (int64_t)((N + Geo::TILE - 1) / Geo::TILE) * ((K + Geo::TILE - 1) / Geo::TILE);
     int64_t want = ((BIG ? 1 : 2) * (int64_t)n_cu + tiles - 1) / tiles;
     if (want < 1) want = 1;
     int64_t chunk = (M + want - 1) / want;
     chunk = (chunk + WL_ROWS - 1) / WL_ROWS * WL_ROWS;
     if (chunk < 4 * WL_ROWS) chunk = 4 * WL_ROWS;
+    return chunk;
+}
+
+// one launch of wgrad_x3_lds_kernel<BIG, ...> (+ the reduction of its partial tiles).  det: the caller checked that `scratch`
+// holds chunks x N x K partial tiles (+ the bias rows and their reduction, det_wgrad_x3_floats)
+template <int BIG>
+int launch_wgrad_lds(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
+                     int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, bool vec, int n_cu, hipStream_t s,
+                     const float* gscale, bool det) {
+    using Geo = WlGeo<BIG>;
+    const int K = Cin * taps;
+    const int tiles_n = (N + Geo::TILE - 1) / Geo::TILE, tiles_k = (K + Geo::TILE - 1) / Geo::TILE;
+    const int64_t tiles = (int64_t)tiles_n * tiles_k;
+    const int64_t chunk = wgrad_lds_chunk<BIG>(M, N, K, n_cu);
     const int64_t chunks = (M + chunk - 1) / chunk;
     VRD_CHECK_ARG(chunks <= 65535 && chunk < (1ll << 30) && tiles < (1 << 20), "vrd_gemm_wgrad_x3: too many rows (%lld)", (long long)M);
     const dim3 grid((unsigned)tiles, (unsigned)chunks);
     // the chunks' partial tiles go through `scratch` when it holds them (chunks x N x K floats, 16-byte aligned); else atomics
     const int64_t NK = (int64_t)N * K;
-    float* partial = chunks > 1 && scratch && aligned16(scratch) && aligned16(dW) && scratch_floats >= chunks * NK ? scratch : nullptr;
+    float* partial = chunks > 1 && scratch && aligned16(scratch) && (det || aligned16(dW)) && scratch_floats >= chunks * NK ? scratch : nullptr;
+    float* bias_partial = det && partial && dbias ? partial + chunks * NK : nullptr;          // (where the kernel puts them)
     constexpr size_t lds = 2 * Geo::STAGE;
-#define VRD_WGRAD_LAUNCH(VEC_, TAPS_, F16_)                                                                                        \
+#define VRD_WGRAD_LAUNCH(VEC_, TAPS_, F16_, DET_)                                                                                  \
     do {                                                                                                                           \
-        auto kern = wgrad_x3_lds_kernel<BIG, VEC_, TAPS_, F16_>;                                                                   \
+        auto kern = wgrad_x3_lds_kernel<BIG, VEC_, TAPS_, F16_, DET_>;                                                             \
         if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(kern), lds, "vrd_gemm_wgrad_x3")) return rc;                   \
         hipLaunchKernelGGL(kern, grid, dim3(Geo::NTHR), lds, s, G, ldg, X, ldx, row_mask, M, N, Cin, T, tiles_k, (int)chunk, dW,   \
                            dbias, partial, gscale);                                                                                \
     } while (0)
-    if (gscale) {
-        if (vec && taps == 1) VRD_WGRAD_LAUNCH(true, 1, true);
-        else if (vec) VRD_WGRAD_LAUNCH(true, 3, true);
-        else if (taps == 1) VRD_WGRAD_LAUNCH(false, 1, true);
-        else VRD_WGRAD_LAUNCH(false, 3, true);
-    } else if (vec && taps == 1) VRD_WGRAD_LAUNCH(true, 1, false);
-    else if (vec) VRD_WGRAD_LAUNCH(true, 3, false);
-    else if (taps == 1) VRD_WGRAD_LAUNCH(false, 1, false);
-    else VRD_WGRAD_LAUNCH(false, 3, false);
+#define VRD_WGRAD_LAUNCH_MODE(DET_)                                                                                                \
+    do {                                                                                                                           \
+        if (gscale) {                                                                                                              \
+            if (vec && taps == 1) VRD_WGRAD_LAUNCH(true, 1, true, DET_);                                                           \
+            else if (vec) VRD_WGRAD_LAUNCH(true, 3, true, DET_);                                                                   \
+            else if (taps == 1) VRD_WGRAD_LAUNCH(false, 1, true, DET_);                                                            \
+            else VRD_WGRAD_LAUNCH(false, 3, true, DET_);                                                                           \
+        } else if (vec && taps == 1) VRD_WGRAD_LAUNCH(true, 1, false, DET_);                                                       \
+        else if (vec) VRD_WGRAD_LAUNCH(true, 3, false, DET_);                                                                      \
+        else if (taps == 1) VRD_WGRAD_LAUNCH(false, 1, false, DET_);                                                               \
+        else VRD_WGRAD_LAUNCH(false, 3, false, DET_);                                                                              \
+    } while (0)
+    if (det) VRD_WGRAD_LAUNCH_MODE(true);
+    else VRD_WGRAD_LAUNCH_MODE(false);
+#undef VRD_WGRAD_LAUNCH_MODE
 #undef VRD_WGRAD_LAUNCH
     VRD_LAUNCH_CHECK();
     if (partial) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, partial, (int)chunks, NK, dW);
+        // (det: dW may sit anywhere; the scalar form adds in the same order)
+        if (!det || aligned16(dW))
+            hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, partial, (int)chunks, NK, dW);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, partial, (int)chunks, NK, dW);
         VRD_LAUNCH_CHECK();
     }
+    if (bias_partial) return det_colreduce(bias_partial, chunks, N, dbias, nullptr, N, s);
     return 0;
 }
 
@@ -696,11 +787,13 @@ int launch_wgrad_lds(const float* G, int64_t ldg, const float* X, int64_t ldx, c
 // block = rpb rows x 64 columns, a quarter of the rows per wave, one atomic per column and block: atomics on one address queue up
 // behind each other in L2 (~50 ns each), and with 32 rows per atomic a 49 k-row input put 1,536 of them on every output element.
 // ------------------------------------------------------------------------------------------------------------------
+// DET: the block's sums become row blockIdx.x of `partial` (gridDim.x x C) instead, for det_colreduce.
 constexpr int CS_ROWS = 32;      // smallest rows-per-block
+template <bool DET>
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
                                                      int64_t ldb, int bc, int bo, int bs, int shift, int T,
                                                      const uint8_t* __restrict__ mask, const float* __restrict__ rscale,
-                                                     int64_t rows, int C, int rpb, float* __restrict__ out) {
+                                                     int64_t rows, int C, int rpb, float* __restrict__ out, float* __restrict__ partial) {
     __shared__ float red[3][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
@@ -743,7 +836,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
     // the four waves (four row ranges of the same 64 columns) add up in LDS: one atomic per column and block
     if (wave > 0) red[wave - 1][lane] = s;
     __syncthreads();
-    if (wave == 0 && col_ok) atomicAdd(out + c, s + red[0][lane] + red[1][lane] + red[2][lane]);
+    if (wave == 0 && col_ok) {
+        if (DET) partial[(int64_t)blockIdx.x * C + c] = s + red[0][lane] + red[1][lane] + red[2][lane];
+        else atomicAdd(out + c, s + red[0][lane] + red[1][lane] + red[2][lane]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -752,12 +848,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
 // (dw in the parameter's own (C, gin, k) layout)
 // (vrd_colsum computes one (g, kk) per launch: twelve launches and twelve passes over dD per q / k / v convolution triple).
 // block = rpb rows x 64 columns, a quarter of the rows per wave (as vrd_colsum); one atomic per column, output and block.
+// DET: row blockIdx.x of `partial` (gridDim.x x (C * GIN * KS [+ C])) instead: dw's layout, then the bias.
 // ------------------------------------------------------------------------------------------------------------------
-template <int KS, int GIN>
+template <int KS, int GIN, bool DET>
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x,
                                                            int64_t ldx, int bs, int T, const uint8_t* __restrict__ mask,
                                                            int64_t rows, int C, int rpb, float* __restrict__ dw,
-                                                           float* __restrict__ dbias) {
+                                                           float* __restrict__ dbias, float* __restrict__ partial) {
     __shared__ float red[3][GIN * KS + 1][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
@@ -810,6 +907,16 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
     }
     __syncthreads();
     if (wave > 0 || !col_ok) return;
+    if (DET) {
+        float* pw = partial + (int64_t)blockIdx.x * ((int64_t)C * (GIN * KS) + (dbias ? C : 0));
+#pragma unroll
+        for (int g = 0; g < GIN; ++g)
+#pragma unroll
+            for (int kk = 0; kk < KS; ++kk)
+                pw[(int64_t)c * (GIN * KS) + g * KS + kk] = sw[g][kk] + red[0][g * KS + kk][lane] + red[1][g * KS + kk][lane] + red[2][g * KS + kk][lane];
+        if (dbias) pw[(int64_t)C * (GIN * KS) + c] = sb + red[0][GIN * KS][lane] + red[1][GIN * KS][lane] + red[2][GIN * KS][lane];
+        return;
+    }
 #pragma unroll
     for (int g = 0; g < GIN; ++g)
 #pragma unroll
@@ -829,7 +936,15 @@ __device__ __forceinline__ void fma4(float4& s, const float4& a, const float4& b
     s.x = fmaf(a.x, b.x, s.x), s.y = fmaf(a.y, b.y, s.y), s.z = fmaf(a.z, b.z, s.z), s.w = fmaf(a.w, b.w, s.w);
 }
 __device__ __forceinline__ void add4(float4& s, const float4& a) { s.x += a.x, s.y += a.y, s.z += a.z, s.w += a.w; }
+// A16 = false (deterministic mode, rows that are float4-shaped but not 16-byte aligned): the same four floats as four loads, so
+// the form -- and its summation tree -- depends on the shapes alone
+template <bool A16>
+__device__ __forceinline__ float4 ldv4(const float* p) {
+    if (A16) return ld4(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
 
+template <bool A16>
 __global__ __launch_bounds__(256) void colsum_vec_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb,
                                                          const uint8_t* __restrict__ mask, const float* __restrict__ rscale,
                                                          int64_t rows, int C, int rpb, float* __restrict__ out,
@@ -850,8 +965,8 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const float* __restrict
         for (int u = 0; u < 4; ++u) {
             const int64_t r = rb + u;
             const bool live = col_ok && r < r1 && (!mask || mask[r]);
-            av[u] = live ? ld4(a + r * lda + c) : zero;
-            bv[u] = live && b ? ld4(b + r * ldb + c) : one;
+            av[u] = live ? ldv4<A16>(a + r * lda + c) : zero;
+            bv[u] = live && b ? ldv4<A16>(b + r * ldb + c) : one;
             fv[u] = live && rscale ? rscale[r] : 1.f;
         }
 #pragma unroll
@@ -869,6 +984,7 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const float* __restrict
     }
 }
 
+template <bool A16>
 __global__ __launch_bounds__(256) void dwconv_wgrad_vec_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x,
                                                                int64_t ldx, int bs, int T, const uint8_t* __restrict__ mask,
                                                                int64_t rows, int C, int rpb, float* __restrict__ dw,
@@ -893,12 +1009,12 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_vec_kernel(const float* __re
             int tq = tpos + u;
             int64_t sq = seq;
             while (tq >= T) tq -= T, ++sq;
-            av[u] = live ? ld4(a + r * lda + c) : zero;
+            av[u] = live ? ldv4<A16>(a + r * lda + c) : zero;
 #pragma unroll
             for (int kk = 0; kk < 3; ++kk) {
                 const int tb = bs * tq + kk - 1;
                 const bool ok = live && tb >= 0 && tb < bs * T;
-                xv[u][kk] = ok ? ld4(x + (sq * (int64_t)bs * T + tb) * ldx + c) : zero;
+                xv[u][kk] = ok ? ldv4<A16>(x + (sq * (int64_t)bs * T + tb) * ldx + c) : zero;
             }
         }
 #pragma unroll
@@ -1111,27 +1227,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             atomicAdd(dgp + 0, g.x), atomicAdd(dgp + 1, g.y), atomicAdd(dgp + 2, g.z), atomicAdd(dgp + 3, g.w);
             atomicAdd(dbp + 0, b.x), atomicAdd(dbp + 1, b.y), atomicAdd(dbp + 2, b.z), atomicAdd(dbp + 3, b.w);
         }
-    }
-}
-
-// out[c] += sum_p partial[p * cols + c]: the per-block column sums of a kernel whose blocks would otherwise each end in one
-// atomic per column (atomics on one address are worked off one after the other, ~50 ns each: 512 blocks = 25 us).  Block =
-// 64 columns x 32 partial rows (a wave takes eight of them), one atomic per column and block: parts / 32 per address.
-__global__ __launch_bounds__(256) void colpartial_reduce_kernel(const float* __restrict__ partial, int parts, int cols,
-                                                                float* __restrict__ out0, float* __restrict__ out1, int split) {
-    __shared__ float red[3][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    const int p0 = blockIdx.y * 32 + wave * 8;
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = (c < cols && p0 + q < parts) ? partial[(int64_t)(p0 + q) * cols + c] : 0.f;
-    float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && c < cols) {
-        s += red[0][lane] + red[1][lane] + red[2][lane];
-        atomicAdd(c < split ? out0 + c : out1 + (c - split), s);
     }
 }
 
@@ -1650,54 +1745,99 @@ static int64_t colsum_vec_rows_per_block(int64_t rows, int col_blocks) {
 
 extern "C" {
 
+static thread_local int64_t g_scratch_need = 0;
+
+// deterministic mode: a call whose scratch is missing, misaligned or smaller than `need` floats fails before any launch
+// (VRD_ERR_SCRATCH; vrd_scratch_required() then reports `need`)
+#define VRD_DET_SCRATCH(need, what)                                                                                                \
+    do {                                                                                                                           \
+        const int64_t need_ = (need);                                                                                              \
+        if (need_ > 0 && !(scratch && aligned16(scratch) && scratch_floats >= need_)) {                                            \
+            g_scratch_need = need_;                                                                                                \
+            vrd::set_error("%s: the deterministic mode needs %lld floats of 16-byte aligned scratch (got %lld)", what,             \
+                           (long long)need_, (long long)(scratch ? scratch_floats : 0));                                           \
+            return VRD_ERR_SCRATCH;                                                                                                \
+        }                                                                                                                          \
+    } while (0)
+#define VRD_CHECK_FLAGS(what) VRD_CHECK_ARG((flags & ~VRD_DETERMINISTIC) == 0, "%s: unknown flags 0x%x", what, (unsigned)flags)
+
+int vrd_scratch_required(int64_t* floats) {
+    VRD_CHECK_ARG(floats, "vrd_scratch_required: null pointer");
+    *floats = g_scratch_need;
+    return 0;
+}
+
 int vrd_gemm_wgrad(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
-                   int taps, int T, float* dW, void* stream) {
+                   int taps, int T, float* dW, float* scratch, int64_t scratch_floats, void* stream, int flags) {
     VRD_CHECK_ARG(G && X && dW, "vrd_gemm_wgrad: null pointer");
     VRD_CHECK_ARG(M > 0 && N > 0 && Cin > 0 && (taps == 1 || taps == 3), "vrd_gemm_wgrad: bad sizes M=%lld N=%d Cin=%d taps=%d", (long long)M, N, Cin, taps);
     VRD_CHECK_ARG(ldg >= N && ldx >= Cin, "vrd_gemm_wgrad: leading dimension too small");
     VRD_CHECK_ARG(T > 0 && M % T == 0, "vrd_gemm_wgrad: M (%lld) must be a multiple of T (%d)", (long long)M, T);
+    VRD_CHECK_FLAGS("vrd_gemm_wgrad");
+    const bool det = flags & VRD_DETERMINISTIC;
     const int K = Cin * taps;
     const int tiles_n = (N + 63) / 64, tiles_k = (K + 63) / 64;
     const int64_t chunks = (M + 4 * WG_CHUNK - 1) / (4 * WG_CHUNK);
     VRD_CHECK_ARG(chunks <= 65535, "vrd_gemm_wgrad: too many rows (%lld)", (long long)M);
+    const int64_t NK = (int64_t)N * K;
+    if (det) VRD_DET_SCRATCH(chunks > 1 ? chunks * NK : 0, "vrd_gemm_wgrad");
     hipStream_t s = static_cast<hipStream_t>(stream);
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 2.0 * (double)M * N * K, 4.0 * ((double)M * (N + Cin) + (double)N * K));
-    hipLaunchKernelGGL(wgrad_kernel, dim3(tiles_n * tiles_k, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, M, N, Cin, taps, T,
-                       tiles_k, dW);
+    if (!det) {
+        hipLaunchKernelGGL(wgrad_kernel<false>, dim3(tiles_n * tiles_k, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, M, N, Cin,
+                           taps, T, tiles_k, dW);
+        VRD_LAUNCH_CHECK();
+        return 0;
+    }
+    // the row chunks' partial tiles, then their sum in chunk order (one chunk: straight into dW)
+    float* dst = chunks > 1 ? scratch : dW;
+    hipLaunchKernelGGL(wgrad_kernel<true>, dim3(tiles_n * tiles_k, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, M, N, Cin,
+                       taps, T, tiles_k, dst);
     VRD_LAUNCH_CHECK();
+    if (chunks > 1) {
+        if (aligned16(dW))
+            hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, scratch, (int)chunks, NK, dW);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, scratch, (int)chunks, NK, dW);
+        VRD_LAUNCH_CHECK();
+    }
     return 0;
 }
 
 int vrd_gemm_wgrad_x3(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
                       int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, const float* g_scale,
-                      void* stream) {
+                      void* stream, int flags) {
     VRD_CHECK_ARG(G && X && dW, "vrd_gemm_wgrad_x3: null pointer");
     VRD_CHECK_ARG(M > 0 && N > 0 && Cin > 0 && (taps == 1 || taps == 3), "vrd_gemm_wgrad_x3: bad sizes M=%lld N=%d Cin=%d taps=%d", (long long)M, N, Cin, taps);
     VRD_CHECK_ARG(ldg >= N && ldx >= Cin, "vrd_gemm_wgrad_x3: leading dimension too small");
     VRD_CHECK_ARG(T > 0 && M % T == 0, "vrd_gemm_wgrad_x3: M (%lld) must be a multiple of T (%d)", (long long)M, T);
+    VRD_CHECK_FLAGS("vrd_gemm_wgrad_x3");
+    const bool det = flags & VRD_DETERMINISTIC;
     const int K = Cin * taps;
-    const int n_cu = vrd::device_cu_count();
+    const int64_t NK = (int64_t)N * K;
+    // (deterministic mode: a fixed CU figure and no lab switches -- the kernel form and the chunks follow from the shapes)
+    const int n_cu = det ? DET_CUS : vrd::device_cu_count();
     hipStream_t s = static_cast<hipStream_t>(stream);
-    vrd::ProfScope prof(VRD_K_BACKWARD, s, 2.0 * (double)M * N * K, 4.0 * ((double)M * (N + Cin) + (double)N * K));
     static const bool use_lds = [] { const char* e = getenv("VRD_WGRAD_LDS"); return !(e && e[0] == '0'); }();
     // VRD_WGRAD_BIG: 0 = 128 x 128 tiles only, 2 = 256 x 256 tiles whenever the shape allows (lab); default: by rows per chunk
     static const int big_mode = [] { const char* e = getenv("VRD_WGRAD_BIG"); return e ? atoi(e) : 1; }();
-    if (use_lds && M >= 256) {
-        const bool vec = N % 4 == 0 && Cin % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0 && aligned16(G) && aligned16(X);
+    if ((det || use_lds) && M >= 256) {
+        const bool vec_shape = N % 4 == 0 && Cin % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0;
+        const bool vec = vec_shape && aligned16(G) && aligned16(X);
         // 256 x 256 tiles, one block per CU, when a block then still walks >= WL_BIG_ROWS rows (its start, its 64 k partial sums
         // and their share of the reduction are paid per block); 128 x 128 tiles, two blocks per CU, otherwise
+        // (deterministic mode: by the shapes, whatever the alignment -- the scalar-load form adds in the same order)
         const int64_t big_tiles = (int64_t)((N + 255) / 256) * ((K + 255) / 256);
-        const bool big = big_mode != 0 && vec && N >= 256 && K >= 256 &&
-                         (big_mode == 2 || M * big_tiles >= (int64_t)WL_BIG_ROWS * n_cu);
-        return big ? launch_wgrad_lds<1>(G, ldg, X, ldx, row_mask, M, N, Cin, taps, T, dW, dbias, scratch, scratch_floats, vec, n_cu, s, g_scale)
-                   : launch_wgrad_lds<0>(G, ldg, X, ldx, row_mask, M, N, Cin, taps, T, dW, dbias, scratch, scratch_floats, vec, n_cu, s, g_scale);
-    }
-    if (dbias) {                                 // the wave kernel has no bias path: a column-sum launch of its own
-        const int col_blocks = (N + 63) / 64;
-        const int64_t rpb = colsum_rows_per_block(M, col_blocks);
-        hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((M + rpb - 1) / rpb), col_blocks), dim3(256), 0, s, G, ldg, (const float*)nullptr,
-                           (int64_t)0, 1, 0, 1, 0, 1, row_mask, (const float*)nullptr, M, N, (int)rpb, dbias);
-        VRD_LAUNCH_CHECK();
+        const bool big = det ? vec_shape && N >= 256 && K >= 256 && M * big_tiles >= (int64_t)WL_BIG_ROWS * n_cu
+                             : big_mode != 0 && vec && N >= 256 && K >= 256 && (big_mode == 2 || M * big_tiles >= (int64_t)WL_BIG_ROWS * n_cu);
+        if (det) {
+            const int64_t chunk = big ? wgrad_lds_chunk<1>(M, N, K, n_cu) : wgrad_lds_chunk<0>(M, N, K, n_cu);
+            const int64_t chunks = (M + chunk - 1) / chunk;
+            VRD_DET_SCRATCH(chunks > 1 ? chunks * NK + (dbias ? chunks * N + det_reduce_extra(chunks, N) : 0) : 0, "vrd_gemm_wgrad_x3");
+        }
+        vrd::ProfScope prof(VRD_K_BACKWARD, s, 2.0 * (double)M * N * K, 4.0 * ((double)M * (N + Cin) + (double)N * K));
+        return big ? launch_wgrad_lds<1>(G, ldg, X, ldx, row_mask, M, N, Cin, taps, T, dW, dbias, scratch, scratch_floats, vec, n_cu, s, g_scale, det)
+                   : launch_wgrad_lds<0>(G, ldg, X, ldx, row_mask, M, N, Cin, taps, T, dW, dbias, scratch, scratch_floats, vec, n_cu, s, g_scale, det);
     }
     const int tiles_n = (N + 63) / 64, tiles_k = (K + 63) / 64;
     // rows per wave: as few row chunks as still fill the chip (every block ends in 4096 atomics), multiples of 32 rows
@@ -1710,36 +1850,93 @@ int vrd_gemm_wgrad_x3(const float* G, int64_t ldg, const float* X, int64_t ldx, 
     if (chunk > 1024) chunk = 1024;
     const int64_t chunks = (M + 4 * chunk - 1) / (4 * chunk);
     VRD_CHECK_ARG(chunks <= 65535, "vrd_gemm_wgrad_x3: too many rows (%lld)", (long long)M);
-    if (g_scale)
-        hipLaunchKernelGGL(wgrad_x3_kernel<true>, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, M, N, Cin,
-                           taps, T, tiles_k, (int)chunk, dW, g_scale);
-    else
-        hipLaunchKernelGGL(wgrad_x3_kernel<false>, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, M, N, Cin,
-                           taps, T, tiles_k, (int)chunk, dW, (const float*)nullptr);
+    const int col_blocks = (N + 63) / 64;
+    const int64_t rpb = colsum_rows_per_block(M, col_blocks);
+    const int64_t bias_parts = (M + rpb - 1) / rpb;
+    // deterministic mode: [chunks x N x K partial tiles (several chunks)][bias_parts x N column sums + their reduction (dbias)]
+    const int64_t tile_floats = chunks > 1 ? chunks * NK : 0;
+    if (det) VRD_DET_SCRATCH(tile_floats + (dbias ? bias_parts * N + det_reduce_extra(bias_parts, N) : 0), "vrd_gemm_wgrad_x3");
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 2.0 * (double)M * N * K, 4.0 * ((double)M * (N + Cin) + (double)N * K));
+    if (dbias) {                                 // the wave kernel has no bias path: a column-sum launch of its own
+        if (det) {
+            float* bpart = scratch + tile_floats;
+            hipLaunchKernelGGL(colsum_kernel<true>, dim3((unsigned)bias_parts, col_blocks), dim3(256), 0, s, G, ldg, (const float*)nullptr,
+                               (int64_t)0, 1, 0, 1, 0, 1, row_mask, (const float*)nullptr, M, N, (int)rpb, dbias, bpart);
+            VRD_LAUNCH_CHECK();
+            if (int rc = det_colreduce(bpart, bias_parts, N, dbias, nullptr, N, s)) return rc;
+        } else {
+            hipLaunchKernelGGL(colsum_kernel<false>, dim3((unsigned)bias_parts, col_blocks), dim3(256), 0, s, G, ldg, (const float*)nullptr,
+                               (int64_t)0, 1, 0, 1, 0, 1, row_mask, (const float*)nullptr, M, N, (int)rpb, dbias, (float*)nullptr);
+            VRD_LAUNCH_CHECK();
+        }
+    }
+    float* dst = det && chunks > 1 ? scratch : dW;
+#define VRD_WGRAD_WAVE(F16_, DET_)                                                                                                     \
+    hipLaunchKernelGGL((wgrad_x3_kernel<F16_, DET_>), dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, G, ldg, X, ldx, row_mask, \
+                       M, N, Cin, taps, T, tiles_k, (int)chunk, dst, g_scale)
+    if (g_scale && det) VRD_WGRAD_WAVE(true, true);
+    else if (g_scale) VRD_WGRAD_WAVE(true, false);
+    else if (det) VRD_WGRAD_WAVE(false, true);
+    else VRD_WGRAD_WAVE(false, false);
+#undef VRD_WGRAD_WAVE
     VRD_LAUNCH_CHECK();
+    if (det && chunks > 1) {
+        if (aligned16(dW))
+            hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, scratch, (int)chunks, NK, dW);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3((unsigned)((NK + 1023) / 1024)), dim3(256), 0, s, scratch, (int)chunks, NK, dW);
+        VRD_LAUNCH_CHECK();
+    }
     return 0;
 }
 
 int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
                      const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch, int64_t scratch_floats,
-                     void* stream) {
+                     void* stream, int flags) {
     VRD_CHECK_ARG(dD && x && dw && rows > 0 && C > 0 && lddd >= C, "vrd_dwconv_wgrad: bad arguments");
     VRD_CHECK_ARG((ksize == 1 || ksize == 3) && (group_in == 1 || group_in == 2) && stride >= 1 && T > 0 && rows % T == 0,
                   "vrd_dwconv_wgrad: unsupported k=%d group_in=%d stride=%d T=%d rows=%lld", ksize, group_in, stride, T, (long long)rows);
+    VRD_CHECK_FLAGS("vrd_dwconv_wgrad");
+    const bool det = flags & VRD_DETERMINISTIC;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool vec_shape = ksize == 3 && group_in == 1 && C % 4 == 0 && lddd % 4 == 0 && ldx % 4 == 0;
+    const bool a16 = aligned16(dD) && aligned16(x);
+    if (det) {
+        // every row block's sums as a row of partials, then det_colreduce; the float4 form by the shapes alone (A16: its loads)
+        const int col_blocks = vec_shape ? (C + 255) / 256 : (C + 63) / 64;
+        const int64_t rpb = vec_shape ? colsum_vec_rows_per_block(rows, col_blocks) : colsum_rows_per_block(rows, col_blocks);
+        const dim3 grid((unsigned)((rows + rpb - 1) / rpb), col_blocks);
+        const int64_t wcols = (int64_t)C * group_in * ksize, pcols = wcols + (dbias ? C : 0);
+        VRD_DET_SCRATCH((int64_t)grid.x * pcols + det_reduce_extra(grid.x, pcols), "vrd_dwconv_wgrad");
+        vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (1 + group_in * stride));
+        if (vec_shape && a16)
+            hipLaunchKernelGGL(dwconv_wgrad_vec_kernel<true>, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw,
+                               dbias, scratch);
+        else if (vec_shape)
+            hipLaunchKernelGGL(dwconv_wgrad_vec_kernel<false>, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw,
+                               dbias, scratch);
+#define VRD_DWW(KS, GIN) hipLaunchKernelGGL((dwconv_wgrad_kernel<KS, GIN, true>), grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw, dbias, scratch)
+        else if (ksize == 3 && group_in == 1) VRD_DWW(3, 1);
+        else if (ksize == 3) VRD_DWW(3, 2);
+        else if (group_in == 1) VRD_DWW(1, 1);
+        else VRD_DWW(1, 2);
+#undef VRD_DWW
+        VRD_LAUNCH_CHECK();
+        return det_colreduce(scratch, grid.x, (int)pcols, dw, dbias, (int)wcols, s);
+    }
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (1 + group_in * stride));
-    if (ksize == 3 && group_in == 1 && C % 4 == 0 && lddd % 4 == 0 && ldx % 4 == 0 && aligned16(dD) && aligned16(x)) {
+    if (vec_shape && a16) {
         const int col_blocks = (C + 255) / 256;
         const int64_t rpb = colsum_vec_rows_per_block(rows, col_blocks);
         const dim3 grid((unsigned)((rows + rpb - 1) / rpb), col_blocks);
         const int64_t pcols = (int64_t)C * 3 + (dbias ? C : 0);
         float* partial = grid.x > 8 && scratch && aligned16(scratch) && scratch_floats >= (int64_t)grid.x * pcols ? scratch : nullptr;
-        hipLaunchKernelGGL(dwconv_wgrad_vec_kernel, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw, dbias,
+        hipLaunchKernelGGL(dwconv_wgrad_vec_kernel<true>, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw, dbias,
                            partial);
         VRD_LAUNCH_CHECK();
         if (partial) {
-            hipLaunchKernelGGL(colpartial_reduce_kernel, dim3((unsigned)((pcols + 63) / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial,
-                               (int)grid.x, (int)pcols, dw, dbias, C * 3);
+            hipLaunchKernelGGL(colpartial_reduce_kernel<false>, dim3((unsigned)((pcols + 63) / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial,
+                               (int)grid.x, (int)pcols, dw, dbias, C * 3, (float*)nullptr);
             VRD_LAUNCH_CHECK();
         }
         return 0;
@@ -1747,7 +1944,7 @@ int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx,
     const int col_blocks = (C + 63) / 64;
     const int64_t rpb = colsum_rows_per_block(rows, col_blocks);
     const dim3 grid((unsigned)((rows + rpb - 1) / rpb), col_blocks);
-#define VRD_DWW(KS, GIN) hipLaunchKernelGGL((dwconv_wgrad_kernel<KS, GIN>), grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw, dbias)
+#define VRD_DWW(KS, GIN) hipLaunchKernelGGL((dwconv_wgrad_kernel<KS, GIN, false>), grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, (int)rpb, dw, dbias, (float*)nullptr)
     if (ksize == 3 && group_in == 1) VRD_DWW(3, 1);
     else if (ksize == 3) VRD_DWW(3, 2);
     else if (group_in == 1) VRD_DWW(1, 1);
@@ -1759,31 +1956,53 @@ int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx,
 
 int vrd_colsum(const float* a, int64_t lda, const float* b, int64_t ldb, int b_cstride, int b_coffset, int b_rstride, int shift,
                int T, const uint8_t* row_mask, const float* row_scale, int64_t rows, int C, float* out, float* scratch,
-               int64_t scratch_floats, void* stream) {
+               int64_t scratch_floats, void* stream, int flags) {
     VRD_CHECK_ARG(a && out && rows > 0 && C > 0 && lda >= C, "vrd_colsum: bad arguments");
     VRD_CHECK_ARG(!b || (T > 0 && rows % T == 0 && b_cstride >= 1 && b_rstride >= 1 && b_coffset >= 0 && b_coffset < b_cstride),
                   "vrd_colsum: bad second operand (T=%d rows=%lld)", T, (long long)rows);
+    VRD_CHECK_FLAGS("vrd_colsum");
+    const bool det = flags & VRD_DETERMINISTIC;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (b ? 2 : 1));
     const bool same_rows = !b || (b_cstride == 1 && b_coffset == 0 && b_rstride == 1 && shift == 0);
-    if (same_rows && C % 4 == 0 && lda % 4 == 0 && aligned16(a) && (!b || (ldb % 4 == 0 && ldb >= C && aligned16(b)))) {
+    const bool vec_shape = same_rows && C % 4 == 0 && lda % 4 == 0 && (!b || (ldb % 4 == 0 && ldb >= C));
+    const bool a16 = aligned16(a) && (!b || aligned16(b));
+    if (det) {
+        // as in vrd_dwconv_wgrad: partial rows + det_colreduce, the form by the shapes alone
+        const int col_blocks = vec_shape ? (C + 255) / 256 : (C + 63) / 64;
+        const int64_t rpb = vec_shape ? colsum_vec_rows_per_block(rows, col_blocks) : colsum_rows_per_block(rows, col_blocks);
+        const dim3 grid((unsigned)((rows + rpb - 1) / rpb), col_blocks);
+        VRD_DET_SCRATCH((int64_t)grid.x * C + det_reduce_extra(grid.x, C), "vrd_colsum");
+        vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (b ? 2 : 1));
+        if (vec_shape && a16)
+            hipLaunchKernelGGL(colsum_vec_kernel<true>, grid, dim3(256), 0, s, a, lda, b, ldb, row_mask, row_scale, rows, C, (int)rpb, out, scratch);
+        else if (vec_shape)
+            hipLaunchKernelGGL(colsum_vec_kernel<false>, grid, dim3(256), 0, s, a, lda, b, ldb, row_mask, row_scale, rows, C, (int)rpb, out, scratch);
+        else
+            hipLaunchKernelGGL(colsum_kernel<true>, grid, dim3(256), 0, s, a, lda, b, ldb, b ? b_cstride : 1, b ? b_coffset : 0, b ? b_rstride : 1,
+                               shift, b ? T : 1, row_mask, row_scale, rows, C, (int)rpb, out, scratch);
+        VRD_LAUNCH_CHECK();
+        return det_colreduce(scratch, grid.x, C, out, nullptr, C, s);
+    }
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (b ? 2 : 1));
+    if (vec_shape && a16) {
         const int col_blocks = (C + 255) / 256;
         const int64_t rpb = colsum_vec_rows_per_block(rows, col_blocks);
         const dim3 grid((unsigned)((rows + rpb - 1) / rpb), col_blocks);
         float* partial = grid.x > 8 && scratch && aligned16(scratch) && scratch_floats >= (int64_t)grid.x * C ? scratch : nullptr;
-        hipLaunchKernelGGL(colsum_vec_kernel, grid, dim3(256), 0, s, a, lda, b, ldb, row_mask, row_scale, rows, C, (int)rpb, out, partial);
+        hipLaunchKernelGGL(colsum_vec_kernel<true>, grid, dim3(256), 0, s, a, lda, b, ldb, row_mask, row_scale, rows, C, (int)rpb, out, partial);
         VRD_LAUNCH_CHECK();
         if (partial) {
-            hipLaunchKernelGGL(colpartial_reduce_kernel, dim3((unsigned)((C + 63) / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial, (int)grid.x,
-                               C, out, (float*)nullptr, C);
+            hipLaunchKernelGGL(colpartial_reduce_kernel<false>, dim3((unsigned)((C + 63) / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial, (int)grid.x,
+                               C, out, (float*)nullptr, C, (float*)nullptr);
             VRD_LAUNCH_CHECK();
         }
         return 0;
     }
     const int col_blocks = (C + 63) / 64;
     const int64_t rpb = colsum_rows_per_block(rows, col_blocks);
-    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((rows + rpb - 1) / rpb), col_blocks), dim3(256), 0, s, a, lda, b, ldb,
-                       b ? b_cstride : 1, b ? b_coffset : 0, b ? b_rstride : 1, shift, b ? T : 1, row_mask, row_scale, rows, C, (int)rpb, out);
+    hipLaunchKernelGGL(colsum_kernel<false>, dim3((unsigned)((rows + rpb - 1) / rpb), col_blocks), dim3(256), 0, s, a, lda, b, ldb,
+                       b ? b_cstride : 1, b ? b_coffset : 0, b ? b_rstride : 1, shift, b ? T : 1, row_mask, row_scale, rows, C, (int)rpb, out,
+                       (float*)nullptr);
     VRD_LAUNCH_CHECK();
     return 0;
 }
@@ -1821,27 +2040,33 @@ int vrd_activation(const float* x, int64_t ldx, const float* dy, int64_t lddy, i
 
 int vrd_layernorm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t rows, int C, const float* gamma,
                       const float* beta, int relu, float* dx, int64_t lddx, float* dgamma, float* dbeta, float* scratch,
-                      int64_t scratch_floats, void* stream) {
+                      int64_t scratch_floats, void* stream, int flags) {
     VRD_CHECK_ARG(x && dy && gamma && beta && dx && dgamma && dbeta, "vrd_layernorm_bwd: null pointer");
     VRD_CHECK_ARG(C == 256 || C == 512, "vrd_layernorm_bwd: C must be 256 or 512 (got %d)", C);
     VRD_CHECK_ARG(ldx >= C && lddy >= C && lddx >= C && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && aligned16(x) && aligned16(dy) &&
                       aligned16(dx) && aligned16(gamma) && aligned16(beta),
                   "vrd_layernorm_bwd: rows must be 16-byte aligned");
+    VRD_CHECK_FLAGS("vrd_layernorm_bwd");
+    const bool det = flags & VRD_DETERMINISTIC;
     if (rows <= 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 12.0 * (double)rows * C);
     int64_t rpw = (rows / (4 * 512) + 3) / 4 * 4;            // ~512 blocks on long inputs; a multiple of 4 rows, 8 .. 64
     if (rpw < LNB_ROWS) rpw = LNB_ROWS;
     if (rpw > 64) rpw = 64;
     dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
+    // deterministic mode: always the partial rows, then det_colreduce
+    if (det) VRD_DET_SCRATCH((int64_t)grid.x * 2 * C + det_reduce_extra(grid.x, 2 * C), "vrd_layernorm_bwd");
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 12.0 * (double)rows * C);
     // with a scratch buffer the blocks' column sums take two steps (rows of partial sums, then colpartial_reduce_kernel)
-    float* partial = grid.x > 32 && scratch && aligned16(scratch) && scratch_floats >= (int64_t)grid.x * 2 * C ? scratch : nullptr;
+    float* partial = det ? scratch
+                         : grid.x > 32 && scratch && aligned16(scratch) && scratch_floats >= (int64_t)grid.x * 2 * C ? scratch : nullptr;
     if (C == 256) hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, dim3(256), 0, s, x, ldx, dy, lddy, rows, gamma, beta, relu, dx, lddx, dgamma, dbeta, (int)rpw, partial);
     else hipLaunchKernelGGL(layernorm_bwd_kernel<2>, grid, dim3(256), 0, s, x, ldx, dy, lddy, rows, gamma, beta, relu, dx, lddx, dgamma, dbeta, (int)rpw, partial);
     VRD_LAUNCH_CHECK();
+    if (det) return det_colreduce(partial, grid.x, 2 * C, dgamma, dbeta, C, s);
     if (partial) {
-        hipLaunchKernelGGL(colpartial_reduce_kernel, dim3((unsigned)(2 * C / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial, (int)grid.x, 2 * C,
-                           dgamma, dbeta, C);
+        hipLaunchKernelGGL(colpartial_reduce_kernel<false>, dim3((unsigned)(2 * C / 64), (grid.x + 31) / 32), dim3(256), 0, s, partial, (int)grid.x, 2 * C,
+                           dgamma, dbeta, C, (float*)nullptr);
         VRD_LAUNCH_CHECK();
     }
     return 0;

@@ -138,11 +138,16 @@ class _FactorPool:
     launches each (rand, add, floor, div) -- 120 of the step's ~560 tensor-op launches, each a node of a recorded step.
     A pool drawn while a HIP graph is being recorded belongs to that recording (its `rand` is replayed, so every replay gets
     fresh factors; the slices recorded into the graph point into it) and is dropped when the capture state changes, as
-    autograd._ZeroArena's blocks are."""
+    autograd._ZeroArena's blocks are.
+    Deterministic mode (ops.get_deterministic()): MaskVRD.forward_training calls reset() first, so that a step's factors are
+    drawn during that step -- from the generator state the caller seeded -- instead of being what is left of an earlier pool."""
     POOL = 4096
 
     def __init__(self):
         self.pools = {}                # (device, keep_prob) -> [factors, next index, drawn during a capture]
+
+    def reset(self):
+        self.pools.clear()
 
     def take(self, n, keep_prob, device):
         capturing = torch.cuda.is_current_stream_capturing()

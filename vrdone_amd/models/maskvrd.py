@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .backbones import MaskConvTransformerBackbone, MaskConvTransformerBackboneWithCLIP
-from .blocks import _ops
+from .blocks import _factor_pool, _ops
 from .. import train_graph
 from . import losses
 from .fpns import FPN1D_Fuse
@@ -378,6 +378,9 @@ class MaskVRD(nn.Module):
         pdev = next(self.parameters()).device
         if torch.is_grad_enabled():
             ops.check_differentiable("MaskVRD.forward_training")
+        if ops.get_deterministic():
+            # (the stochastic-depth factors of this call are drawn in this call: the same seed gives the same step)
+            _factor_pool.reset()
         guard = ops.f16_planes() and pdev.type == "cuda" and os.environ.get("VRDONE_RANGE_GUARD", "1") != "0"
         if guard:
             flag = ops.f16_range_flag(pdev)

@@ -302,6 +302,54 @@ class use_precision:
         return False
 
 
+# Deterministic mode: a training step's losses, gradients, updated parameters and EMA weights are the same bits for the same
+# seed, inputs, precision mode and device type -- whatever the workgroup schedule, the allocator's alignment, the scratch offered,
+# eager or HIP-graph execution, this process or another.  It passes VRD_DETERMINISTIC to the parameter-gradient kernels (partial
+# sums added in index order, no float atomics, shape-only chunking: include/vrdone_hip.h) and re-draws the stochastic-depth
+# factors of every forward_training call (models/blocks.py, _FactorPool).  Opt-in: set_deterministic() / use_deterministic() /
+# VRDONE_DETERMINISTIC=0|1; undecided, it follows torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic,
+# the switches the reference's utils.set_seed sets.  Read at forward time; every autograd Function records it for its backward.
+_deterministic = None                    # None: follow torch's flags
+_env_det = os.environ.get("VRDONE_DETERMINISTIC")
+if _env_det is not None:
+    if _env_det not in ("0", "1"):
+        raise ValueError(f"VRDONE_DETERMINISTIC must be 0 or 1, got {_env_det!r}")
+    _deterministic = _env_det == "1"
+
+
+def set_deterministic(on):
+    """True / False: the mode on / off whatever torch's flags say; None: follow torch's flags again."""
+    global _deterministic
+    _deterministic = None if on is None else bool(on)
+
+
+def get_deterministic():
+    if _deterministic is not None:
+        return _deterministic
+    return bool(torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic)
+
+
+class use_deterministic:
+    """`with ops.use_deterministic(True):` -- the mode inside the block, the previous setting (explicit or following torch) after it."""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.prev = _deterministic
+        set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
+
+
+def grad_flags():
+    """`flags` of the parameter-gradient kernels in the current mode."""
+    return _hip.DETERMINISTIC if get_deterministic() else 0
+
+
 # ---- the f16x3 mode's operand range (include/vrdone_hip.h, vrd_f16_range_flag)
 _range_flags = {}
 

@@ -42,7 +42,7 @@ from . import ops
 MAX_SHAPES = 4
 WARMUP_ITERS = 3
 
-_GRAPHS = weakref.WeakKeyDictionary()          # model -> {on, recordings: {(batch shape, deep supervision, precision mode): _Recording}}
+_GRAPHS = weakref.WeakKeyDictionary()          # model -> {on, recordings: {(batch shape, ..., precision, deterministic mode): _Recording}}
 
 
 def _storage_key(model):
@@ -162,18 +162,24 @@ def recordings(model):
     return {} if state is None else state["recordings"]
 
 
-def mask_vrd(model, x, m):
-    """`model._mask_vrd(x, m, with_aux=model.deep_supervision)` through the recorded graphs (recorded on the first use of a
-    batch shape; that call replays them too and returns real predictions)."""
-    graphs = _GRAPHS[model]["recordings"]
-    # everything that shapes the captured launch sequence besides the batch shape: precision mode, launch-wave size, the
-    # stochastic-depth probabilities and pinned keep vectors of every AffineDropPath, which parameters train
+def recording_key(model, x, m):
+    """Everything that shapes the captured launch sequence besides the batch shape: precision mode, launch-wave size, the
+    stochastic-depth probabilities and pinned keep vectors of every AffineDropPath, which parameters train, and (last) the
+    deterministic mode (its gradient kernels take other launches and scratch)."""
     from .models.blocks import AffineDropPath
     drops = tuple((mod.drop_prob, None if mod.keep is None else mod.keep.data_ptr()) for mod in model.modules()
                   if isinstance(mod, AffineDropPath))
     trainable = tuple(p.requires_grad for p in model.parameters())
-    key = (tuple(x.shape), tuple(m.shape), bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops,
-           trainable)
+    return (tuple(x.shape), tuple(m.shape), bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops,
+            trainable, ops.get_deterministic())
+
+
+def mask_vrd(model, x, m):
+    """`model._mask_vrd(x, m, with_aux=model.deep_supervision)` through the recorded graphs (recorded on the first use of a
+    batch shape; that call replays them too and returns real predictions)."""
+    graphs = _GRAPHS[model]["recordings"]
+    key = recording_key(model, x, m)
+    det = key[-1]
     rec = graphs.get(key)
     if rec is not None and rec.storage != _storage_key(model):
         graphs.clear()                         # the parameters were replaced or moved: every recording is stale
@@ -182,5 +188,11 @@ def mask_vrd(model, x, m):
         if len(graphs) >= MAX_SHAPES:
             return model._mask_vrd(x, m, with_aux=model.deep_supervision)
         assert x.is_cuda and not x.requires_grad
-        rec = graphs[key] = _Recording(model, x, m)
+        if det:
+            # the warm-up runs draw stochastic-depth factors: the recording leaves the generator as it found it, so that the
+            # replay below draws what an eager step would have drawn from the state the caller seeded
+            with torch.random.fork_rng(devices=[x.device]):
+                rec = graphs[key] = _Recording(model, x, m)
+        else:
+            rec = graphs[key] = _Recording(model, x, m)
     return rec(x, m)
