@@ -2,8 +2,14 @@
 """Headline benchmark: subject-object pairs/second through MaskVRD._mask_vrd (backbone with SOS
 fusion -> 1-D FPN -> mask-segmentation predictor) on synthetic pair x frame tensors.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, and the GEMM
+families' roofline from the HIP events of the timed region.  --full adds everything else the line can carry, each from runs
+of its own: the other precision modes (`alt_precision`, `reference_arithmetic`), the ragged leg, the per-rank shard
+projection, the whole eval call (`forward_test`), the training step, the CPU baseline and the other kernel families' times
+(one more, untimed step); the --no-* options leave single parts of it out.
 
 Workload (BASELINE.json metric): configs/vidvrd.yaml model, 2048 pairs x 256 frames, which the
 reference's eval batching pads to T_pad = 288 (models/maskvrd.py:378-379); inputs (B, 2069, 288)
@@ -49,14 +55,17 @@ def parse():
     ap.add_argument("--pair-chunk", type=int, default=0, help="pairs per launch wave inside _mask_vrd (0 = model default)")
     ap.add_argument("--no-prof", action="store_true", help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--precision", default=None, choices=["f16x3", "bf16x3", "f32"], help="GEMM product mode of the headline (default: the library default, f16x3)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra runs in the other precision modes")
-    ap.add_argument("--no-ragged", action="store_true", help="skip the extra run on ragged pair lengths")
-    ap.add_argument("--no-forward-test", action="store_true", help="skip the secondary metric (whole eval call on one synthetic video)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the training-step leg (BASELINE config 3: forward + backward on a 24-pair batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other part of the line too (other precision modes, ragged leg, shard projection, "
+                         "eval call, training step, CPU baseline, all kernel families' times); a plain run times the headline only")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the extra runs in the other precision modes")
+    ap.add_argument("--no-ragged", action="store_true", help="(--full) skip the extra run on ragged pair lengths")
+    ap.add_argument("--no-forward-test", action="store_true", help="(--full) skip the secondary metric (whole eval call on one synthetic video)")
+    ap.add_argument("--no-train-step", action="store_true", help="(--full) skip the training-step leg (BASELINE config 3: forward + backward on a 24-pair batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-shard-projection", action="store_true",
-                    help="skip timing the 1/2, 1/4, 1/8 per-rank shares of the batch on this one GPU (N = 1 only)")
-    ap.add_argument("--cpu-pairs", type=int, default=64)
+                    help="(--full) skip timing the 1/2, 1/4, 1/8 per-rank shares of the batch on this one GPU (N = 1 only)")
+    ap.add_argument("--cpu-pairs", type=int, default=64, help="(--full) pairs of the CPU baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline's last timed step returned (pred_logits, pred_masks) to DIR/<name>.npy, float32")
     return ap.parse_args()
@@ -290,7 +299,7 @@ def main():
             fence()
             # The timed region records HIP events around the launches of the GEMM families only -- what `roofline` needs.  Two
             # events around each of a step's ~600 launches cost 0.8 % of it (142.8 against 141.7 ms, three A/Bs on one box);
-            # the other families' times come from one more, untimed step with events around every launch.
+            # with --full, the other families' times come from one more, untimed step with events around every launch.
             _hip.prof_select(GEMM_FAMILIES)
             _hip.prof_enable(not args.no_prof)
             _hip.prof_reset()
@@ -303,7 +312,7 @@ def main():
                 keep["logits"], keep["masks"] = logits.clone(), masks.clone()
             _hip.prof_enable(False)
             prof = _hip.prof_read() if (rank == 0 and not args.no_prof) else {}
-            if prof and world == 1:
+            if prof and world == 1 and args.full:
                 _hip.prof_select(None)
                 _hip.prof_enable(True)
                 _hip.prof_reset()
@@ -368,13 +377,14 @@ def main():
         if rank == 0:
             dump_outputs(args.dump_outputs, last["logits"], last["masks"])
         del last
+    # (everything below the headline runs with --full only)
     alts = {}
-    if not args.no_alt:
+    if args.full and not args.no_alt:
         for alt_mode in ("f16x3", "bf16x3", "f32"):
             if alt_mode != main_mode:
                 alts[alt_mode] = run(alt_mode, 1, args.steps)
     ragged = None
-    if not args.no_ragged:
+    if args.full and not args.no_ragged:
         # SURVEY 8d's second input set, reported separately: same pairs, lengths ~ U[2, frames] (seed 1235), padded to
         # the same T_pad like the reference's eval batching pads a slice to its longest pair
         gen = torch.Generator().manual_seed(1235 + rank)
@@ -394,7 +404,7 @@ def main():
     # N = 2, 4, 8 (strong scaling: the global batch is fixed).  A projection of the scaling curve, not a measurement of
     # it: it leaves out the all-gather (payload below, < 1 ms over xGMI) and rank-to-rank skew.
     projection = None
-    if world == 1 and not args.no_shard_projection:
+    if world == 1 and args.full and not args.no_shard_projection:
         if ragged is not None or "x" not in batch:          # the ragged leg replaced the full-length batch
             batch.clear()
             full_x, full_m = synth.synth_pairs(args.pairs, c_in, t_pad, [args.frames] * args.pairs, seed=1234, device=dev)
@@ -448,7 +458,7 @@ def main():
         del full_x, full_m
 
     ft = None
-    if not args.no_forward_test and args.config == "vidvrd":
+    if args.full and not args.no_forward_test and args.config == "vidvrd":
         # secondary metric: the whole eval call MaskVRD.forward_test -- batching of the dataloader's
         # per-pair matrices, the path, device post-processing, result lists -- on one synthetic video of 46 tracklets;
         # with N > 1 the product's pair-sharded form (MaskVRD.shard_pairs: compact-candidate all-gather), every rank
@@ -504,7 +514,7 @@ def main():
     # BASELINE config 3: one training step's forward + backward through the HIP path (vidvrd.yaml, 24 pairs in T_pad 96,
     # synthetic ground truth; optimizer excluded -- that is the reference's own code).  Rank 0, N = 1 only.
     train = None
-    if not args.no_train_step and args.config == "vidvrd" and world == 1:
+    if args.full and not args.no_train_step and args.config == "vidvrd" and world == 1:
         sys.path.insert(0, os.path.join(REPO, "scripts"))
         from train_step import synthetic_batch
         batch.clear()
@@ -607,7 +617,7 @@ def main():
             line["algorithmic_tflops"] = fpp * args.pairs * args.steps / elapsed / 1e12
         if prof:
             line["roofline"] = roofline(main_mode, prof)
-            if world > 1:
+            if world > 1 or not args.full:
                 line["roofline"]["profiled_families"] = "GEMM families only (shares below are among those)"
             else:
                 line["roofline"]["profiled_families"] = ("HIP events inside the timed region around the GEMM families' launches; the other "
@@ -644,7 +654,7 @@ def main():
             line["forward_test"] = ft
         if train is not None:
             line["train_step"] = train
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()}
             line["cpu_baseline"] = cpu_baseline(cfg, sd_cpu, c_in, args.frames, t_pad, args.cpu_pairs)
         print(json.dumps(line), flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box (through gpurun) from the repo root:  bash scripts/collect_profiles.sh r04 "f16x3 bf16x3 f32" [sq]
 # Produces, under gpurun_out/profiles_<tag>/ (scripts/stage_profiles.sh turns them into profiles/<tag>_*):
-#   bench.json                        the bench line (events on, CPU baseline on), default mode, alt modes included; run LAST,
+#   bench.json                        the --full bench line (events on, CPU baseline on), default mode, alt modes included; run LAST,
 #                                     after the traffic summaries of this run were written into profiles/ on the box
 #   kernel_stats_<mode>.csv           rocprofv3 --kernel-trace --stats of the same command in one precision mode
 #   pmc_FETCH_SIZE_<mode>.csv / pmc_WRITE_SIZE_<mode>.csv   per dispatch, separate passes (TCC slots)
@@ -41,5 +41,5 @@ for MODE in $MODES; do
   # profiles/*_hbm_traffic_<mode>.json whose source stamp matches the tree (stage_profiles.sh writes the same files at home)
   (cd $R && python3 scripts/summarize_traffic.py $OUT profiles/${TAG}_hbm_traffic$SUF.json $SUF > /dev/null)
 done
-echo "[collect] bench line" && timeout -k 10 600 python3 $R/bench.py --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+echo "[collect] bench line" && timeout -k 10 600 python3 $R/bench.py --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 ls -la $OUT

@@ -1,6 +1,6 @@
 """The bench line's contract on a small workload (the driver parses this line; a field that goes missing would only show at
-round end): one JSON line on stdout with the metric fields, the `roofline` and `cpu_baseline` objects, and the N > 1 path
-started without a launcher (two ranks sharing the GPU over gloo)."""
+round end): one JSON line on stdout with the metric fields; with --full the `cpu_baseline` and `reference_arithmetic` objects,
+without it nothing but the headline; and the N > 1 path started without a launcher (two ranks sharing the GPU over gloo)."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def run_bench(*flags, env=None):
 
 
 def test_bench_line_contract_small():
-    b = run_bench("--pairs", "64", "--steps", "2", "--warmup", "1", "--cpu-pairs", "2", "--no-ragged", "--no-forward-test",
+    b = run_bench("--pairs", "64", "--steps", "2", "--warmup", "1", "--full", "--cpu-pairs", "2", "--no-ragged", "--no-forward-test",
                   "--no-train-step", "--no-shard-projection")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
@@ -45,6 +45,31 @@ def test_bench_line_contract_small():
     ra = b["reference_arithmetic"]
     assert ra["gemm_precision"] == "f32" and ra["value"] > 0 and ra["unit"] == "pairs/s"
     assert abs(ra["value"] - 64 / (ra["ms_per_step"] * 1e-3)) <= 1e-6 * ra["value"] and 0 < ra["roofline"]["frac"] < 1
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full: one timed region (the headline's), its outputs dumped, and a line with the headline fields and the GEMM
+    families' roofline from that region -- no other precision, leg, projection, eval call, training step or CPU baseline."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--pairs", "64", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    b = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in b, k
+    assert b["steps"] == 2 and b["warmup"] == 1 and b["unit"] == "pairs/s" and b["higher_is_better"] is True
+    assert b["dtype"].startswith(b["config"]["gemm_precision"]) and "64 pairs x 256 frames" in b["metric"]
+    assert abs(b["value"] - 64 / (b["ms_per_step"] * 1e-3)) <= 1e-6 * b["value"]
+    for k in ("alt_precision", "reference_arithmetic", "ragged_variant", "shard_projection", "forward_test", "train_step", "cpu_baseline"):
+        assert k not in b, k
+    assert 0 < b["roofline"]["frac"] < 1 and b["roofline"]["profiled_families"].startswith("GEMM families only")
+    assert set(b["kernel_ms_per_step"]) <= {"gemm_f32_mfma", "gemm_x3_mfma", "gemm_x3_dma", "gemm_x3_big"}
+    assert out.stderr.count("timed region:") == 1, out.stderr[-2000:]
+    import numpy as np
+    logits, masks = np.load(tmp_path / "pred_logits.npy"), np.load(tmp_path / "pred_masks.npy")
+    assert logits.shape[0] == 64 and masks.shape[0] == 64 and logits.dtype == np.float32
+    assert np.isfinite(logits).all() and np.isfinite(masks).all()
 
 
 def test_bench_starts_its_own_ranks():
