@@ -83,14 +83,28 @@ const char* vrd_last_error(void);
 /* ---- operand range of the VRD_PAIR_F16 format ----
  * A value x with |x * 2^VRD_F16_ACT_EXP| >= 65,520 does not fit the f16 planes of a pair row: it is stored as hi = inf,
  * lo = -inf and poisons every product it enters, but a NaN does not reach the outputs reliably (the ReLU behind the embedding
- * LayerNorms and the max-pools of the branch blocks drop it: fmax(NaN, x) = x).  Every kernel that WRITES pair rows in this
- * format, or splits f32 rows into them while staging, therefore reports: it ORs a tag naming its family into one 32-bit flag
- * word per device -- 1 boundary tensors (vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs), 2 vrd_layernorm, 4 vrd_dwconv_ln,
- * 8 pair-row outputs of vrd_gemm / vrd_gemm_batch, 16 f32 rows split inside vrd_gemm, 32 pair-row outputs of vrd_local_attn /
- * vrd_attention.  (vrd_attention_pair needs none: its outputs are averages of value rows that were checked when they were
- * written.)  The word lives in device memory for the life of the process; the caller reads it together with a call's
- * results (an asynchronous 4-byte copy on the same stream), repeats the call in another precision if it is non-zero, and
- * clears it with a 4-byte memset.  The reference computes in float32 and has no such limit (models/blocks.py:728-737).
+ * LayerNorms and the max-pools of the branch blocks drop it: fmax(NaN, x) = x).  The exact threshold: |x| >= 4095 reports
+ * (4095 * 16 = 65,520 rounds to inf), the last float32 below 4095 still fits (hi = 65,504, lo = 16); |x| < 4094 stays the
+ * documented safe bound (4094 decodes exactly).  Every kernel that WRITES pair rows in this format, or splits f32 rows into
+ * such planes while staging, therefore reports: it ORs a tag naming its family into one 32-bit flag word per device --
+ *    1  boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs
+ *    2  vrd_layernorm, vrd_conv_ln
+ *    4  vrd_dwconv_ln (its pair-row output sets only; f32 output sets of the same call do not count)
+ *    8  pair-row outputs of vrd_gemm / vrd_gemm_batch (every kernel and epilogue of the family)
+ *   16  f32 rows split while staged: A of vrd_gemm / vrd_gemm_batch (the value times a_scale[0] where a_scale is given),
+ *       q / k / v of vrd_attention_rows and of vrd_attention_bwd (its f16 form, o_scale given)
+ *   32  pair-row outputs of vrd_local_attn / vrd_local_attn_segs / vrd_attention
+ *   64  reserved.
+ * Entry points that take or make such rows and do NOT report: vrd_attention_pair (its outputs are averages of value rows that
+ * were checked when they were written; its inputs must be in range like any pair row), vrd_assemble_pairs (f32 rows only: the
+ * GEMM that consumes them reports, tag 16), and vrd_gemm_wgrad_x3 with g_scale: it splits X at 2^VRD_F16_ACT_EXP unchecked.  An
+ * X element out of range leaves every dW entry of its column(s) non-finite and the other columns untouched -- loud, but not
+ * reported: call it only on an X that a reporting kernel has split before (the host mirror's autograd.Linear takes it only behind
+ * a forward vrd_gemm that ran a split kernel on the same rows, and the exact-f32 vrd_gemm_wgrad otherwise).
+ * The word lives in device memory for the life of the process; bits accumulate across launches and streams until the caller
+ * clears them.  The caller reads it together with a call's results (an asynchronous 4-byte copy on the same stream), repeats
+ * the call in another precision if it is non-zero, and clears it with a 4-byte memset.  The reference computes in float32 and
+ * has no such limit (models/blocks.py:728-737).
  * `flag` receives the device address of the CURRENT device's word. */
 int vrd_f16_range_flag(void** flag);
 
@@ -255,6 +269,10 @@ typedef struct {
                                products, as in the three-product form.  vrd_gemm_batch needs the same value in every entry. */
 } vrd_gemm_args;
 int vrd_gemm(const vrd_gemm_args* a, void* stream);
+/* The kernel family (enum vrd_kernel_id) vrd_gemm would run these arguments on, without launching anything: VRD_K_GEMM (exact
+ * f32 products, no range check of A), VRD_K_GEMM_X3 / _X3_DMA / _X3_BIG (split precision: f32-row A is checked, tag 16 of the range
+ * flag).  -1 (error string set) for arguments vrd_gemm would refuse.  The host mirror asks it instead of repeating the rule. */
+int vrd_gemm_family(const vrd_gemm_args* a);
 /* `count` (1..4) GEMMs of an array of argument structs.  Problems that differ only in A, W / W_split, bias and C and
  * that the 256 x 256 split-precision kernel takes -- the q / k / v projections of one attention block
  * (models/blocks.py:935-947, models/local_transformer.py:157-161) -- run as ONE grid (one ragged last round of tiles

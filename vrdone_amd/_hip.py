@@ -163,6 +163,7 @@ _SIGNATURES = {
                                    C.c_void_p]),
     "vrd_split_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vrd_gemm": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
+    "vrd_gemm_family": (C.c_int, [C.POINTER(GemmArgs)]),
     "vrd_gemm_batch": (C.c_int, [C.POINTER(GemmArgs), C.c_int, C.c_void_p]),
     "vrd_row_blocks": (C.c_int, [c_u8p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrd_conv_ln": (C.c_int, [C.POINTER(ConvLnArgs), C.c_void_p]),
@@ -275,9 +276,15 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed ({rc}): {lib.vrd_last_error().decode()}")
 
 
-# tags of the f16 operand-range flag word (vrd_f16_range_flag)
-RANGE_TAGS = {1: "boundary tensors (bct_to_btc / pack_pairs / gather_pairs)", 2: "layernorm", 4: "dwconv_ln", 8: "gemm outputs",
-              16: "f32 rows split inside a gemm", 32: "attention outputs", 64: "other"}
+# tags of the f16 operand-range flag word (vrd_f16_range_flag; enum RangeTag of csrc/vrd_common.h): the entry points that OR each
+# bit.  A value x reports from |x| >= 4095 on (|x * 2^4| >= 65520 rounds to hi = inf); |x| < 4094 is the documented safe bound.
+RANGE_TAGS = {1: "boundary tensors (vrd_bct_to_btc / vrd_pack_pairs / vrd_gather_pairs)",
+              2: "vrd_layernorm / vrd_conv_ln outputs",
+              4: "vrd_dwconv_ln outputs",
+              8: "pair-row outputs of vrd_gemm / vrd_gemm_batch",
+              16: "f32 rows split while staged (vrd_gemm / vrd_gemm_batch, vrd_attention_rows, vrd_attention_bwd)",
+              32: "pair-row outputs of vrd_local_attn / vrd_local_attn_segs / vrd_attention",
+              64: "other"}
 
 
 def prof_enable(on=True):

@@ -191,12 +191,18 @@ class Linear(_Differentiable):
 
     @staticmethod
     def forward(ctx, x, weight, bias, row_mask):
-        y = ops.conv_gemm(x, weight, bias, row_mask=row_mask)
+        family = []
+        y = ops.conv_gemm(x, weight, bias, row_mask=row_mask, _family=family)
         ctx.save_for_backward(x, weight)
         ctx.row_mask, ctx.has_bias = row_mask, bias is not None
         # the backward runs in the arithmetic of ITS forward, whatever the mode is by then (MaskVRD.forward_training repeats a
         # step whose activations leave the f16 range in the f32 mode: the graph it returns is differentiated outside that block)
         ctx.split_bwd, ctx.bfmt = ops.split_backward(), ops.backward_fmt()
+        # the f16-plane weight gradient splits the saved x at the fixed 2^VRD_F16_ACT_EXP without a range check of its own: it is
+        # taken only where the forward GEMM above split the same rows (and reported on them, tag 16 of ops.f16_range_flag); a
+        # forward on the exact-f32 kernel (Cin * k % 32 != 0, unaligned rows: the library says which, vrd_gemm_family) is
+        # followed by the exact-f32 weight gradient
+        ctx.f16_wgrad = ctx.bfmt != PAIR_F16 or family[0] != _hip.K_GEMM
         ctx.det = ops.get_deterministic()             # (so is the deterministic mode)
         return y
 
@@ -241,7 +247,7 @@ class Linear(_Differentiable):
         if ctx.needs_input_grad[1]:
             packed = _zeros(N, k * Cin, device=dy.device)
             px, _, _, ldx = _rows(x)
-            if ctx.split_bwd:
+            if ctx.split_bwd and ctx.f16_wgrad:
                 # split-precision products like the forward GEMMs of the mode (bf16 planes; f16x3 mode: f16 planes, the gradient at
                 # its own power-of-two factor); the bias gradient (exact f32 column sums) in the same pass
                 if want_db:

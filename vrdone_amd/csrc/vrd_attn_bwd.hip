@@ -266,6 +266,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_rows_kernel(const float* 
 // s_v = v_scale[0] (vrd_absmax_scale of V): |dS| <= (|dP| + |delta|) / 8 <= 16 max|dO| max|V| < 2^32 / (s_o s_v), so dS s_s stays
 // below 2^15; what the bound gives away against the values that actually occur costs nothing but range, the planes keep 2^-25
 // absolute precision down to their subnormals.  The accumulators are rescaled where they leave the kernel.
+// rflag: q, k and v are split here again, and the caller need not have run attn_fwd_rows_kernel on them (lse_in NULL): the split of
+// this wave's query rows and of every k / v tile of pass 2 feeds a tracker (RANGE_GEMM_IN), so the call reports on its own.
 template <bool F16>
 __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k,
                                                                 const float* __restrict__ v, int64_t ldkv, const float* __restrict__ o,
@@ -273,8 +275,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const float* __
                                                                 const uint8_t* __restrict__ kv_mask, int Tq, int Tk, int n_head,
                                                                 float scale, float* __restrict__ dq, const float* __restrict__ lse_in,
                                                                 float* __restrict__ lse_out, float* __restrict__ delta_out,
-                                                                const float* __restrict__ o_scale, const float* __restrict__ v_scale) {
+                                                                const float* __restrict__ o_scale, const float* __restrict__ v_scale,
+                                                                unsigned* rflag) {
     typedef e16x8<F16> bf16x8;                                         // (this instantiation's eight 16-bit elements)
+    vrd::RangeTrack rt;
     constexpr float a_inv = F16 ? vrd::F16_ACT_INV : 1.0f;
     const float s_o = F16 ? vrd::uniform_load(o_scale) : 1.f, s_o_inv = F16 ? vrd::uniform_load(o_scale + 1) : 1.f;
     const float s_s = F16 ? s_o * vrd::uniform_load(v_scale) * 0x1p-17f : 1.f;
@@ -294,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const float* __
     const uint8_t* const mk = kv_mask ? kv_mask + (int64_t)b * Tk : nullptr;
 
     bf16x8 qh[KS], ql[KS], gh[KS], gl[KS];
-    load_col_frags<F16>(qrow, lh, q_ok, qh, ql);
+    load_col_frags<F16>(qrow, lh, q_ok, qh, ql, &rt);
     load_col_frags<F16>(drow, lh, q_ok, gh, gl, nullptr, s_o);
     // delta = sum_d dO O over the query's row: this lane holds half of the d's
     float delta = 0.f;
@@ -320,8 +324,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const float* __
     auto commit = [&](int buf, bool second) {
         char* st = lds + buf * 6 * PLANE;
         if (second) {
-            commit_tile<true, true, F16>(rk, st, st + 2 * PLANE);
-            commit_tile<true, false, F16>(rv, st + 4 * PLANE, nullptr);
+            commit_tile<true, true, F16>(rk, st, st + 2 * PLANE, &rt);
+            commit_tile<true, false, F16>(rv, st + 4 * PLANE, nullptr, &rt);
         } else {
             commit_tile<true, false, F16>(rk, st, nullptr);
         }
@@ -413,6 +417,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_kernel(const float* __
             delta_out[((int64_t)b * n_head + h) * Tq + tq] = delta;
         }
     }
+    if (F16) rt.report(rflag, vrd::RANGE_GEMM_IN);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -554,7 +559,7 @@ extern "C" int vrd_attention_bwd(const float* q, int64_t ldq, const float* k, co
         if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(attn_bwd_dq_kernel<true>), DQ_LDS, "vrd_attention_bwd(dq)")) return rc;
         if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<true>), DKV_LDS, "vrd_attention_bwd(dk, dv)")) return rc;
         hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, gq, dim3(NW * 64), DQ_LDS, s, q, ldq, k, v, ldkv, out, dO, ldo, kv_mask, Tq, Tk, n_head, scale, dq,
-                           lse, lse_own, delta, o_scale, v_scale);
+                           lse, lse_own, delta, o_scale, v_scale, vrd::range_flag());
         VRD_LAUNCH_CHECK();
         hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, gk, dim3(NW * 64), DKV_LDS, s, q, ldq, k, v, ldkv, dO, ldo, kv_mask, Tq, Tk, n_head, scale,
                            lse ? lse : lse_own, delta, dk, dv, o_scale, v_scale);
@@ -562,7 +567,7 @@ extern "C" int vrd_attention_bwd(const float* q, int64_t ldq, const float* k, co
         if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(attn_bwd_dq_kernel<false>), DQ_LDS, "vrd_attention_bwd(dq)")) return rc;
         if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<false>), DKV_LDS, "vrd_attention_bwd(dk, dv)")) return rc;
         hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, gq, dim3(NW * 64), DQ_LDS, s, q, ldq, k, v, ldkv, out, dO, ldo, kv_mask, Tq, Tk, n_head, scale, dq,
-                           lse, lse_own, delta, (const float*)nullptr, (const float*)nullptr);
+                           lse, lse_own, delta, (const float*)nullptr, (const float*)nullptr, (unsigned*)nullptr);
         VRD_LAUNCH_CHECK();
         hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, gk, dim3(NW * 64), DKV_LDS, s, q, ldq, k, v, ldkv, dO, ldo, kv_mask, Tq, Tk, n_head, scale,
                            lse ? lse : lse_own, delta, dk, dv, (const float*)nullptr, (const float*)nullptr);

@@ -212,11 +212,11 @@ __device__ __forceinline__ mfma_acc16_t mfma16(f16x8_t a, f16x8_t b, mfma_acc16_
 // per two elements) and ORs the producer's tag into the device's flag word (vrd_f16_range_flag) if that does not fit.  The
 // host mirror reads the word with a call's results and repeats the call in the f32 mode.
 enum RangeTag : unsigned {
-    RANGE_INPUT = 1u,        // boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs / vrd_assemble_pairs
-    RANGE_LAYERNORM = 2u,    // vrd_layernorm
+    RANGE_INPUT = 1u,        // boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs (vrd_assemble_pairs writes f32 rows only)
+    RANGE_LAYERNORM = 2u,    // vrd_layernorm, vrd_conv_ln
     RANGE_DWCONV_LN = 4u,    // vrd_dwconv_ln
     RANGE_GEMM_OUT = 8u,     // pair-row outputs of vrd_gemm (c_pair)
-    RANGE_GEMM_IN = 16u,     // f32 rows split inside a GEMM / attention kernel while they are staged
+    RANGE_GEMM_IN = 16u,     // f32 rows split inside a GEMM / attention kernel while they are staged (vrd_gemm, vrd_attention_rows / _bwd)
     RANGE_ATTN_OUT = 32u,    // pair-row outputs of the attention kernels
     RANGE_OTHER = 64u,
 };
@@ -233,6 +233,7 @@ struct RangeTrack {
 // hi / lo planes of N values in format F16 (the f16 format scales by 2^VRD_F16_ACT_EXP first); rt: see RangeTrack
 template <bool F16, int N, typename V>
 __device__ __forceinline__ void split_n(const float (&x)[N], V& h, V& l, RangeTrack* rt = nullptr) {
+    static_assert(N == 1 || N % 2 == 0, "the tracker sees the values two at a time: an odd N > 1 would hide its last one");
     typedef typename SplitFmt<F16>::elem E;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -250,6 +251,7 @@ __device__ __forceinline__ void split_n(const float (&x)[N], V& h, V& l, RangeTr
 // the same with a run-time factor in place of 2^VRD_F16_ACT_EXP (F16 only; bf16 planes take the values as they are)
 template <bool F16, int N, typename V>
 __device__ __forceinline__ void split_n_scaled(const float (&x)[N], float mul, V& h, V& l, RangeTrack* rt = nullptr) {
+    static_assert(N == 1 || N % 2 == 0, "the tracker sees the values two at a time: an odd N > 1 would hide its last one");
     typedef typename SplitFmt<F16>::elem E;
 #pragma unroll
     for (int j = 0; j < N; ++j) {

@@ -302,6 +302,21 @@ int validate_gemm_args(const vrd_gemm_args* a) {
 }
 }  // namespace
 
+// the operand layouts vrd_gemm's kernels are chosen by: float4 loads of A / W, float4 epilogue
+static bool gemm_vec(const vrd_gemm_args* a) { return (a->Cin % 4 == 0) && (a->lda % 4 == 0) && aligned16(a->A) && aligned16(a->W); }
+static bool gemm_staged(const vrd_gemm_args* a) {
+    // float4 epilogue needs 16-byte aligned output / residual rows
+    return (a->ldc % 4 == 0) && aligned16(a->C) && (!a->res || (a->ldres % 4 == 0 && aligned16(a->res))) &&
+           (!a->res2 || (a->ldres2 % 4 == 0 && aligned16(a->res2)));
+}
+
+extern "C" int vrd_gemm_family(const vrd_gemm_args* a) {
+    VRD_CHECK_ARG(a != nullptr, "vrd_gemm_family: null args");
+    if (validate_gemm_args(a)) return -1;
+    const X3Choice pick = choose_x3(a, gemm_vec(a), gemm_staged(a));
+    return pick.big ? VRD_K_GEMM_X3_BIG : pick.dma ? VRD_K_GEMM_X3_DMA : (pick.x3 ? VRD_K_GEMM_X3 : VRD_K_GEMM);
+}
+
 extern "C" int vrd_gemm(const vrd_gemm_args* a, void* stream) {
     VRD_CHECK_ARG(a != nullptr, "vrd_gemm: null args");
     if (int rc = validate_gemm_args(a)) return rc;
@@ -311,10 +326,7 @@ extern "C" int vrd_gemm(const vrd_gemm_args* a, void* stream) {
     VRD_CHECK_ARG(tiles_m64 * tiles_n < (int64_t)1 << 31, "vrd_gemm: grid too large");
     const int tiles_m = (int)tiles_m64;
     const int K = a->Cin * a->taps;
-    const bool vec = (a->Cin % 4 == 0) && (a->lda % 4 == 0) && aligned16(a->A) && aligned16(a->W);
-    // float4 epilogue needs 16-byte aligned output / residual rows
-    const bool staged = (a->ldc % 4 == 0) && aligned16(a->C) && (!a->res || (a->ldres % 4 == 0 && aligned16(a->res))) &&
-                        (!a->res2 || (a->ldres2 % 4 == 0 && aligned16(a->res2)));
+    const bool vec = gemm_vec(a), staged = gemm_staged(a);
     static const int bk_env = [] { const char* e = getenv("VRD_GEMM_BK"); return e ? atoi(e) : 0; }();
     const int bk = bk_env == 32 ? 32 : 16;
     hipStream_t s = static_cast<hipStream_t>(stream);

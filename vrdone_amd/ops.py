@@ -701,7 +701,7 @@ def row_blocks(mask):
 
 def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False,
               res2=None, out=None, out_pair=False, skip_rows=None, row_scale=None, _launch=None, _dgrad=False, _split_fmt=None,
-              _a_scale=None, _bfmt=None):
+              _a_scale=None, _bfmt=None, _family=None):
     """Dense Conv1d (k = 1 or 3, stride 1, zero padding k//2) with the fused epilogue of
     vrd_gemm.  x: (B, T, Cin) tensor or Pair; weight: the Conv1d parameter (N, Cin, k).
     out_pair: write the result as pair rows of width N (returns a Pair).
@@ -711,6 +711,7 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
     row_scale (rows,): per-row factor on the branch term (stochastic depth, blocks.py:1107-1120); autograd path only.
     _split_fmt: element format of the split products instead of the mode's (the unfused backward GEMMs pass PAIR_BF16; 0 = exact
     f32 products whatever the mode, None = the mode's format).
+    _family: a list that receives the kernel family (_hip.K_GEMM* = enum vrd_kernel_id) the library runs this call on.
     _dgrad / _a_scale: the conv's input-gradient GEMM on the parameter's transposed operand; x is then a gradient, and in the
     f16 format its rows are split at the power-of-two factor of grad_scale(x) (vrd_gemm_args.a_scale).
     Under autograd (`recording`) the op runs as autograd.conv_gemm and returns a fresh tensor (`out` is ignored)."""
@@ -783,11 +784,25 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
         pr, rr, rc, ldr = _rows(res2)
         assert rr == rows and rc == N
         a.res2, a.ldres2 = pr, ldr
+    if _family is not None:
+        fam = lib.vrd_gemm_family(C.byref(a))
+        if fam < 0:
+            _hip.check(fam, "vrd_gemm_family")
+        _family.append(fam)
     if _launch is not None:            # conv_gemm_batch collects the argument structs instead of launching
         _launch.append(a)
     else:
         _hip.check(lib.vrd_gemm(C.byref(a), _stream()), "vrd_gemm")
     return Pair(out, N, a.c_pair) if a.c_pair else out
+
+
+def split_forward(x, weight, bias=None, **kwargs):
+    """True when conv_gemm(x, weight, ...) runs a split-precision GEMM kernel in the current mode, False when it lands on the
+    exact-f32 kernel: the library's own answer for the arguments conv_gemm builds (vrd_gemm_family), nothing is launched.  In the
+    f16 modes only the split kernels check f32 rows against the operand range (tag 16 of f16_range_flag)."""
+    family = []
+    conv_gemm(x, weight, bias, _launch=[], _family=family, **kwargs)
+    return family[0] != _hip.K_GEMM
 
 
 def conv_gemm_batch(calls):
@@ -927,7 +942,7 @@ def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=
         a.pre_gamma, a.pre_beta = _param_ptr(pre_ln[0], x, "LayerNorm weight"), _param_ptr(pre_ln[1], x, "LayerNorm bias")
     a.mask_out = _mask_ptr(mask_out, B * Tout)
     a.n_out = len(sets)
-    outs = []
+    outs, blocks = [], []
     for i, s in enumerate(sets):
         assert tuple(s["weight"].shape) == (Cout, g, k) and s["weight"].is_contiguous()
         o = s.get("out")
@@ -938,7 +953,10 @@ def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=
         a.w[i], a.bias[i] = _param_ptr(s["weight"], x, "depthwise weight"), _param_ptr(s.get("bias"), x, "depthwise bias")
         a.gamma[i], a.beta[i] = (_param_ptr(s.get("gamma"), x, "LayerNorm weight"),
                                  _param_ptr(s.get("beta"), x, "LayerNorm bias"))
-        a.packed[i] = _dwconv_block(s["weight"], s.get("bias"), s.get("gamma"), s.get("beta")).data_ptr()
+        # (held until the launch is queued: one weight tensor in two sets with different LayerNorm parameters replaces its own
+        # cache entry, and the first set's image would be freed, and its memory handed out again, before the kernel reads it)
+        blocks.append(_dwconv_block(s["weight"], s.get("bias"), s.get("gamma"), s.get("beta")))
+        a.packed[i] = blocks[-1].data_ptr()
         a.relu[i] = 1 if s.get("relu") else 0
         a.y[i], a.ldy[i] = po, ldo
         a.out_pair[i] = _fmt(s.get("pair"))
