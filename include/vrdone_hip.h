@@ -631,6 +631,36 @@ int vrd_assign(const float* cost, int64_t ld, const int32_t* first, const int32_
 int vrd_ema_update(float* const* ema, const float* const* model, const int64_t* numel, const int32_t* chunk_tensor,
                    const int32_t* chunk_index, int n_chunks, float decay, float one_minus_decay, void* stream);
 
+/* ---- gradient-norm clipping and AdamW over pointer tables (train.py:187-190: clip_grad_norm_ + AdamW.step) -------------------
+ * Tables as for vrd_ema_update, all DEVICE arrays: per tensor t a pointer per role (grad / param / exp_avg / exp_avg_sq, f32,
+ * contiguous), numel[t], vec[t] (non-zero: every pointer of the tensor is 16-byte aligned and the float4 form is used; zero:
+ * scalar loads and stores -- the values do not depend on it) and, for the update, group[t] = the tensor's row of `groups`.
+ * chunk c of a launch works on elements chunk_index[c]*4096 ... of tensor chunk_tensor[c]; a tensor that is not in the chunk map
+ * (no gradient this step, no elements) is not touched and its pointers are not read.  No launch synchronises with the host.
+ *
+ * partial[c] = the sum of squares of chunk c's gradient elements (double; one workgroup per chunk, no atomics). */
+int vrd_grad_sumsq(const float* const* grad, const int64_t* numel, const int32_t* vec, const int32_t* chunk_tensor,
+                   const int32_t* chunk_index, int n_chunks, double* partial, void* stream);
+/* One workgroup adds partial[0 .. n_chunks) in index order in a fixed tree (the sum depends on values and shapes only) and writes
+ * out[0] = total_norm = sqrt(sum), out[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6)) (torch.nn.utils.clip_grad_norm_;
+ * a NaN norm gives a NaN coefficient as there); max_norm <= 0: clip_coef = 1. */
+int vrd_grad_norm_finish(const double* partial, int n_chunks, float max_norm, float* out, void* stream);
+/* torch.optim.AdamW's update (amsgrad / maximize / capturable off) of every tensor in the chunk map, with g = grad * clip_coef[0]
+ * (clip_coef: device pointer, e.g. vrd_grad_norm_finish's out + 1; NULL: 1); the gradients themselves are not written:
+ *   p *= 1 - lr_wd;  m += (1 - beta1) * (g - m);  v = v * beta2 + (1 - beta2) * g * g;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)
+ * each operation rounded to f32.  groups: n_groups rows of VRD_ADAMW_GROUP_FLOATS floats
+ *   {lr * weight_decay, beta1, beta2, eps, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), 1 - beta1, 1 - beta2}
+ * which the host computes in double and rounds to f32 (1 - beta formed in f32 from the rounded beta would be off by up to 5e-5
+ * of its value).  Tensors that share a row share hyper-parameters AND step count t. */
+#define VRD_ADAMW_GROUP_FLOATS 8
+int vrd_adamw_step(float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                   const int32_t* group, const int32_t* vec, const float* groups, int n_groups, const int32_t* chunk_tensor,
+                   const int32_t* chunk_index, int n_chunks, const float* clip_coef, void* stream);
+/* grad *= clip_coef[0] in place for every tensor in the chunk map (the standalone clip; the product is the one vrd_adamw_step
+ * forms, so clip-then-step and the folded step give the same bits). */
+int vrd_scale_tensors(float* const* grad, const int64_t* numel, const int32_t* vec, const int32_t* chunk_tensor, const int32_t* chunk_index,
+                      int n_chunks, const float* clip_coef, void* stream);
+
 /* ---- the training criterion for all decoder layers of a step --------------------------------------------
  * Replaces the tensor code of models/maskvrd.py:417-496 (bipartite_match: the three cost matrices), :498-588 (loss_labels,
  * loss_masks on the final head and the auxiliary heads) and models/losses.py:4-354 (masked focal / dice, plain and fuzzy

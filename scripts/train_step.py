@@ -53,7 +53,10 @@ def synthetic_batch(cfg, c_in, device, n_pairs=24, seed=0):
 
 
 def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, ema_decay=0.999, verbose=True, drop_path=True,
-        graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False):
+        graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False, fused_tail=False, torch_fused=False):
+    """fused_tail: clip + AdamW as vrdone_amd.optim.FusedAdamW.step(max_grad_norm=clip) (three launches) instead of torch's
+    clip_grad_norm_ + AdamW.step; torch_fused: torch's own AdamW(fused=True), the second baseline of that comparison.
+    log["tail_ms"]: wall time of clip + optimiser step, between two synchronisations."""
     from vrdone_amd import _hip, configs, ops, synth
     if deterministic:
         ops.set_deterministic(True)           # bit-reproducible steps (vrdone_amd/ops.py); the log then carries their sha256
@@ -70,10 +73,15 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         model.enable_training_graphs()        # forward + backward of the network as two HIP-graph replays (train_graph.py)
     from vrdone_amd.ema import ModelEma
     ema = ModelEma(model, decay=ema_decay)                                # one-launch EMA (vrd_ema_update), same values
-    opt = torch.optim.AdamW(param_groups(model, weight_decay), lr=lr)
+    if fused_tail:
+        from vrdone_amd.optim import FusedAdamW
+        opt = FusedAdamW(param_groups(model, weight_decay), lr=lr)
+    else:
+        opt = torch.optim.AdamW(param_groups(model, weight_decay), lr=lr, **({"fused": True} if torch_fused else {}))
     data = synthetic_batch(cfg, configs.input_channels(cfg), device, n_pairs=n_pairs, seed=seed)
     start = [p.detach().clone() for p in model.parameters()]
-    log = {"total_loss": [], "step_ms": [], "params_without_grad": [], "nonfinite_grads": []}
+    log = {"total_loss": [], "step_ms": [], "tail_ms": [], "params_without_grad": [], "nonfinite_grads": []}
+    zero_grad = set()
     for step in range(steps):
         if profile and step == steps - 1:                                 # per-kernel-family time of the last step (HIP events)
             _hip.prof_enable(True)
@@ -86,11 +94,20 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         named = list(model.named_parameters())
         log["params_without_grad"] += [name for name, p in named if p.grad is None]
         with_grad = [(name, p.grad) for name, p in named if p.grad is not None]
-        norms = torch.stack(torch._foreach_norm([g for _, g in with_grad]))       # one multi-tensor launch, one sync
+        norms = torch.stack(torch._foreach_norm([g for _, g in with_grad])).cpu()       # one multi-tensor launch, one sync
         log["nonfinite_grads"] += [with_grad[i][0] for i in torch.nonzero(~torch.isfinite(norms)).flatten().tolist()]
-        if clip > 0:
-            torch.nn.utils.clip_grad_norm_(model.parameters(), clip)     # train.py:187-188
-        opt.step()
+        zero = {with_grad[i][0] for i in torch.nonzero(norms == 0).flatten().tolist()}     # gradient identically zero in every step
+        zero_grad = zero if step == 0 else zero_grad & zero
+        torch.cuda.synchronize()
+        t_tail = time.perf_counter()
+        if fused_tail:
+            opt.step(max_grad_norm=clip if clip > 0 else None)           # both in three launches (vrdone_amd/optim.py)
+        else:
+            if clip > 0:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), clip)     # train.py:187-188
+            opt.step()
+        torch.cuda.synchronize()
+        log["tail_ms"].append(1e3 * (time.perf_counter() - t_tail))
         ema.update(model)                                                 # train.py:194 (ModelEma.update, utils/train_utils.py:21-29)
         torch.cuda.synchronize()
         log["step_ms"].append(1e3 * (time.perf_counter() - t0))
@@ -104,8 +121,12 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         log["kernel_launches_last_step"] = {k: v["launches"] for k, v in prof.items() if v["launches"]}
     with torch.no_grad():          # (multi-tensor ops: a per-parameter expression here was 3 x 521 x 2 launches in the step profile)
         for key, params in (("param_delta_norm", model.parameters()), ("ema_delta_norm", ema.module.parameters())):
-            norms = torch._foreach_norm(torch._foreach_sub([p.detach() for p in params], start))
-            log[key] = float(torch.linalg.vector_norm(torch.stack(norms)))
+            norms = torch.stack(torch._foreach_norm(torch._foreach_sub([p.detach() for p in params], start)))
+            log[key] = float(torch.linalg.vector_norm(norms))
+            if key == "param_delta_norm":
+                names = [name for name, _ in model.named_parameters()]
+                log["params_unmoved"] = [names[i] for i in torch.nonzero(norms == 0).flatten().tolist()]
+                log["params_zero_grad"] = [name for name in names if name in zero_grad]
     if deterministic:
         log["sha256"] = state_digest(model, ema)
     return log
@@ -130,7 +151,9 @@ if __name__ == "__main__":
     ap.add_argument("--config", default="vidvrd", help="vidvrd (24 pairs x 96 frames) | vidor (48 pairs x 512 frames: --pairs 48)")
     ap.add_argument("--pairs", type=int, default=24)
     ap.add_argument("--profile", action="store_true", help="per-kernel-family HIP-event time of the last step")
+    ap.add_argument("--fused-tail", action="store_true", help="clip + AdamW as three launches (vrdone_amd.optim.FusedAdamW)")
+    ap.add_argument("--torch-fused", action="store_true", help="torch.optim.AdamW(fused=True): the other baseline of the tail comparison")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps; prints the sha256 of gradients, parameters, EMA")
     args = ap.parse_args()
     print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile,
-                         deterministic=args.deterministic)))
+                         deterministic=args.deterministic, fused_tail=args.fused_tail, torch_fused=args.torch_fused)))

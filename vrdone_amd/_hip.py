@@ -15,6 +15,7 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 PAIR_NONE, PAIR_BF16, PAIR_F16 = 0, 1, 2          # enum vrd_pair_format
 F16_ACT_EXP = 4                                   # VRD_F16_ACT_EXP
 ABSMAX_SCALE_FLOATS = 516                         # VRD_ABSMAX_SCALE_FLOATS: vrd_absmax_scale's buffer (factors, ticket, partial maxima)
+ADAMW_GROUP_FLOATS = 8                            # VRD_ADAMW_GROUP_FLOATS: one row of vrd_adamw_step's hyper-parameter table
 (K_GEMM, K_LAYERNORM, K_DWCONV_LN, K_LOCAL_ATTN, K_ATTN_SMALL, K_ATTN_FLASH, K_POOL, K_MASK_HEAD,
  K_TRANSPOSE, K_POSTPROC, K_GEMM_X3, K_GEMM_X3_DMA, K_GEMM_X3_BIG, K_BACKWARD, K_COUNT) = range(15)   # enum vrd_kernel_id
 KERNEL_NAMES = ["gemm_f32_mfma", "layernorm", "dwconv_ln", "local_attn", "attn_small", "attn_flash",
@@ -213,6 +214,12 @@ _SIGNATURES = {
                                      C.c_int, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "vrd_assign": (C.c_int, [c_f32p, C.c_int64, c_i32p, c_i32p, C.c_int, C.c_int, c_i32p, C.c_void_p]),
     "vrd_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32p, c_i32p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    # ---- gradient-norm clip + AdamW over pointer tables (csrc/vrd_optim.hip; vrdone_amd/optim.py)
+    "vrd_grad_sumsq": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vrd_grad_norm_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_float, c_f32p, C.c_void_p]),
+    "vrd_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_f32p, C.c_int, c_i32p,
+                                 c_i32p, C.c_int, c_f32p, C.c_void_p]),
+    "vrd_scale_tensors": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_void_p]),
     "vrd_attn_bwd_softmax": (C.c_int, [c_f32p, c_f32p, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vrd_criterion_costs": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p]),
     "vrd_criterion_losses": (C.c_int, [C.c_void_p, c_i32p, c_f32p, C.c_float, c_f32p, C.c_void_p]),
