@@ -87,7 +87,7 @@ const char* vrd_last_error(void);
  * (4095 * 16 = 65,520 rounds to inf), the last float32 below 4095 still fits (hi = 65,504, lo = 16); |x| < 4094 stays the
  * documented safe bound (4094 decodes exactly).  Every kernel that WRITES pair rows in this format, or splits f32 rows into
  * such planes while staging, therefore reports: it ORs a tag naming its family into one 32-bit flag word per device --
- *    1  boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs
+ *    1  boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs, vrd_gather_train
  *    2  vrd_layernorm, vrd_conv_ln
  *    4  vrd_dwconv_ln (its pair-row output sets only; f32 output sets of the same call do not count)
  *    8  pair-row outputs of vrd_gemm / vrd_gemm_batch (every kernel and epilogue of the family)
@@ -178,6 +178,40 @@ typedef struct {
     const float* seq_wh;    /* (P, 2) w, h per gathered sequence (the pairs of several videos in one call), or NULL: w, h */
 } vrd_gather_args;
 int vrd_gather_pairs(const vrd_gather_args* a, void* stream);
+
+/* Training batching from PER-TRAJECTORY features: what the reference's `_train_getitem` (dataloaders/vidvrd.py:324-457) and the
+ * zero-padded batch of models/maskvrd.py:338-360 build on the host, in one launch.  vis / clip / boxes as for vrd_gather_pairs
+ * (the ground-truth trajectories' frames, one row each; boxes clamped).  Sequence p (one surviving relation key) covers
+ * lens[p] <= T frames, frame t being row s_row[p] + t*stride (o_row[p] + t*stride) -- the sub-sampling offset and the start of
+ * the random max_seq_len crop are folded into s_row / o_row by the host.  lead[p] = sub-sampled frames of the pair in front of
+ * the crop: the reference differentiates the boxes before it crops, so frame 0 of a sequence with lead[p] > 0 takes its
+ * difference to row s_row[p] - stride (which the host guarantees to lie in the same trajectory interval) instead of the
+ * extrapolated first difference.  seq_wh (P, 2): w, h of the video sequence p comes from.
+ * Writes the operand buffers of vrd_pack_pairs / vrd_gather_pairs at T frames (zero rows for t >= lens[p]; box arithmetic of
+ * vrd_gather_pairs), out_mask (P, T) bytes 1 / 0 = t < lens[p], and out_targets (G, T) floats: relation g is 1.0 on frames
+ * [seg_lo[g], seg_hi[g]) and 0.0 elsewhere (G may be 0).  Source rows that are not 16-byte aligned are read with scalar loads.
+ * Reports f16 range tag 1 when pair_wide == VRD_PAIR_F16. */
+typedef struct {
+    const float* vis;
+    const float* clip;
+    const float* boxes;
+    const int64_t* s_row;
+    const int64_t* o_row;
+    const int32_t* lens;
+    const int32_t* lead;
+    const float* seq_wh;
+    const int32_t* seg_lo;
+    const int32_t* seg_hi;
+    int32_t P, G, T, V, Cc, stride;
+    float* out_vis;
+    float* out_clip;
+    float* out_so_box;
+    float* out_ent;
+    uint8_t* out_mask;
+    float* out_targets;
+    int32_t pair_wide;      /* enum vrd_pair_format of out_vis / out_clip */
+} vrd_gather_train_args;
+int vrd_gather_train(const vrd_gather_train_args* a, void* stream);
 
 /* Entity-stage rows of a batch of P pairs put together from rows computed ONCE PER TRACKLET (second half).
  * The reference runs the embedding convs, the visual/box fusion and the first stem block on the subject and the object

@@ -5,6 +5,13 @@ no weight decay on biases, LayerNorm / scale parameters and embeddings; configs/
 24-pair synthetic batch of BASELINE config 3 (6 videos x 4 pairs, T = max_seq_len = 96).
 
     python scripts/train_step.py --steps 5          # on the GPU box
+
+--entry-lists / --device-source feed the steps from synthetic per-video cache entries (what proposals.load_train_video
+returns) instead of one fixed batch: per step either proposals.train_getitem on the host and the lists moved to the device, or
+proposals.train_tables and a device-resident proposals.TrainSource (the batch is then gathered by one kernel launch inside the
+step).  `data_ms` is the wall time of that feeding stage, from the cache entries to what model(...) is handed, between two
+synchronisations; the batch assembly on the device (the per-pair copies of the list form, the gather launch of the source form)
+is part of `step_ms` as it always was.  The source's one-time upload is `source_upload_ms`.
 """
 import argparse
 import json
@@ -52,9 +59,49 @@ def synthetic_batch(cfg, c_in, device, n_pairs=24, seed=0):
             "preds_list": to(preds), "masks_list": to(masks), "segs_list": to(segs)}
 
 
+def synthetic_entries(cfg, n_pairs, seed=0, keys_per_video=4):
+    """n_pairs / keys_per_video training cache entries (the dict of proposals.load_train_video): three trajectories per video,
+    keys_per_video relation keys among them, 1-3 relations per key of which the first covers at least 60 % of the pair -- so
+    every key survives the max_seq_len crop of the pairs that are up to a quarter longer than it, and a step always has
+    n_pairs sequences."""
+    from collections import defaultdict
+    assert n_pairs % keys_per_video == 0 and keys_per_video <= 6
+    T, V = cfg["max_seq_len"], cfg["visual_dim"]
+    Cc = cfg["clip_dim"] if cfg.get("with_clip_feature", False) else 0
+    g = torch.Generator().manual_seed(seed + 77)
+    rnd = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g))          # noqa: E731
+    entries = []
+    for v in range(n_pairs // keys_per_video):
+        n_frames = rnd(T // 2, T + T // 4)
+        w, h = [(320, 240), (640, 360), (1280, 720)][v % 3]
+        spans = {t: [[rnd(0, 6), n_frames - rnd(0, 6)]] for t in range(3)}
+        e = {"video_hw": (h, w), "relation_merged": defaultdict(list), "relation_keys": [], "visual_features": {}, "entity_bboxes": {},
+             "entity_classes": {t: t + 1 for t in range(3)}, "traj_intervals": spans}
+        if Cc:
+            e["clip_features"] = {}
+        for t, ((a, b),) in spans.items():
+            e["visual_features"][t] = [torch.randn(b - a, V, generator=g)]
+            xy = torch.rand(b - a, 2, generator=g) * torch.tensor([w * 0.5, h * 0.5])
+            e["entity_bboxes"][t] = [torch.cat([xy, xy + 8 + torch.rand(b - a, 2, generator=g) * torch.tensor([w * 0.4, h * 0.4])], dim=1)]
+            if Cc:
+                e["clip_features"][t] = [torch.randn(b - a, Cc, generator=g)]
+        for s, o in [(0, 1), (1, 0), (0, 2), (2, 1), (1, 2), (2, 0)][:keys_per_video]:
+            lo, hi = max(spans[s][0][0], spans[o][0][0]), min(spans[s][0][1], spans[o][0][1])
+            n = hi - lo
+            for r in range(rnd(1, 3)):
+                length = rnd(-(-6 * n // 10), n) if r == 0 else rnd(2, n)
+                begin = lo + rnd(0, n - length)
+                e["relation_merged"][(s, o, 0, 0)].append({"predicate": rnd(1, cfg["num_classes"]), "begin_fid": begin, "end_fid": begin + length})
+            e["relation_keys"].append([s, o, 0, 0])
+        entries.append(e)
+    return entries
+
+
 def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, ema_decay=0.999, verbose=True, drop_path=True,
-        graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False, fused_tail=False, torch_fused=False):
-    """fused_tail: clip + AdamW as vrdone_amd.optim.FusedAdamW.step(max_grad_norm=clip) (three launches) instead of torch's
+        graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False, fused_tail=False, torch_fused=False,
+        feed=None):
+    """feed: None (one fixed synthetic batch), "lists" or "source" (per step from synthetic cache entries, see the module text).
+    fused_tail: clip + AdamW as vrdone_amd.optim.FusedAdamW.step(max_grad_norm=clip) (three launches) instead of torch's
     clip_grad_norm_ + AdamW.step; torch_fused: torch's own AdamW(fused=True), the second baseline of that comparison.
     log["tail_ms"]: wall time of clip + optimiser step, between two synchronisations."""
     from vrdone_amd import _hip, configs, ops, synth
@@ -78,11 +125,43 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         opt = FusedAdamW(param_groups(model, weight_decay), lr=lr)
     else:
         opt = torch.optim.AdamW(param_groups(model, weight_decay), lr=lr, **({"fused": True} if torch_fused else {}))
-    data = synthetic_batch(cfg, configs.input_channels(cfg), device, n_pairs=n_pairs, seed=seed)
-    start = [p.detach().clone() for p in model.parameters()]
     log = {"total_loss": [], "step_ms": [], "tail_ms": [], "params_without_grad": [], "nonfinite_grads": []}
+    if feed is None:
+        data = synthetic_batch(cfg, configs.input_channels(cfg), device, n_pairs=n_pairs, seed=seed)
+    else:
+        import random
+        from vrdone_amd import proposals
+        assert feed in ("lists", "source")
+        entries = synthetic_entries(cfg, n_pairs, seed=seed)
+        log["data_ms"] = []
+        if feed == "source":
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            source = proposals.TrainSource.concat([proposals.TrainSource.from_entry(e, device) for e in entries])
+            torch.cuda.synchronize()
+            log["source_upload_ms"] = 1e3 * (time.perf_counter() - t0)
+
+        def feed_step(step):
+            rng = random.Random(1000 * seed + step)
+            T = cfg["max_seq_len"]
+            if feed == "source":
+                tables = proposals.TrainTables.concat([proposals.train_tables(v, 1, T, rng=rng) for v in source.videos])
+                tables.on_device(source)                                  # the one upload of the step
+                return {"train_source": source, "train_tables": tables}
+            out = {k: [] for k in ("so_features_list", "preds_list", "masks_list", "segs_list")}
+            for e in entries:
+                for k, v in proposals.train_getitem(e, 1, T, rng=rng).items():
+                    out[k] += [t.to(device, non_blocking=True) for t in v]     # utils.dict_to_device, utils/misc.py:98-112
+            return out
+    start = [p.detach().clone() for p in model.parameters()]
     zero_grad = set()
     for step in range(steps):
+        if feed is not None:
+            torch.cuda.synchronize()
+            t_data = time.perf_counter()
+            data = feed_step(step)
+            torch.cuda.synchronize()
+            log["data_ms"].append(1e3 * (time.perf_counter() - t_data))
         if profile and step == steps - 1:                                 # per-kernel-family time of the last step (HIP events)
             _hip.prof_enable(True)
             _hip.prof_reset()
@@ -113,7 +192,8 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         log["step_ms"].append(1e3 * (time.perf_counter() - t0))
         log["total_loss"].append(float(loss_dict["total_loss"].detach()))
         if verbose:
-            print(f"step {step}: total_loss {log['total_loss'][-1]:.4f}  ({log['step_ms'][-1]:.1f} ms)", flush=True)
+            fed = f"  data {log['data_ms'][-1]:.1f} ms" if feed is not None else ""
+            print(f"step {step}: total_loss {log['total_loss'][-1]:.4f}  ({log['step_ms'][-1]:.1f} ms){fed}", flush=True)
     if profile:
         prof = _hip.prof_read()
         _hip.prof_enable(False)
@@ -154,6 +234,10 @@ if __name__ == "__main__":
     ap.add_argument("--fused-tail", action="store_true", help="clip + AdamW as three launches (vrdone_amd.optim.FusedAdamW)")
     ap.add_argument("--torch-fused", action="store_true", help="torch.optim.AdamW(fused=True): the other baseline of the tail comparison")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps; prints the sha256 of gradients, parameters, EMA")
+    ap.add_argument("--device-source", action="store_true", help="per step: proposals.train_tables + a device-resident TrainSource (prints data_ms)")
+    ap.add_argument("--entry-lists", action="store_true", help="per step: proposals.train_getitem on the same cache entries, lists moved to the device (prints data_ms)")
     args = ap.parse_args()
+    assert not (args.device_source and args.entry_lists)
     print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile,
-                         deterministic=args.deterministic, fused_tail=args.fused_tail, torch_fused=args.torch_fused)))
+                         deterministic=args.deterministic, fused_tail=args.fused_tail, torch_fused=args.torch_fused,
+                         feed="source" if args.device_source else "lists" if args.entry_lists else None)))

@@ -130,6 +130,14 @@ class GatherArgs(C.Structure):
                 ("pair_wide", C.c_int32), ("seq_wh", c_f32p)]
 
 
+class GatherTrainArgs(C.Structure):                   # vrd_gather_train_args
+    _fields_ = [("vis", c_f32p), ("clip", c_f32p), ("boxes", c_f32p), ("s_row", C.c_void_p), ("o_row", C.c_void_p),
+                ("lens", C.c_void_p), ("lead", C.c_void_p), ("seq_wh", c_f32p), ("seg_lo", C.c_void_p), ("seg_hi", C.c_void_p),
+                ("P", C.c_int32), ("G", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("Cc", C.c_int32), ("stride", C.c_int32),
+                ("out_vis", c_f32p), ("out_clip", c_f32p), ("out_so_box", c_f32p), ("out_ent", c_f32p), ("out_mask", c_u8p),
+                ("out_targets", c_f32p), ("pair_wide", C.c_int32)]
+
+
 class SelectArgs(C.Structure):                        # vrd_select_args
     _fields_ = [("cand", c_f32p), ("s_score", c_f32p), ("o_score", c_f32p), ("so_offset", c_i32p), ("so_start", c_i32p),
                 ("so_end", c_i32p), ("video_pairs", c_i32p),
@@ -159,6 +167,7 @@ _SIGNATURES = {
     "vrd_btc_to_bct": (C.c_int, [c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
     "vrd_pack_pairs": (C.c_int, [C.POINTER(PackArgs), C.c_void_p]),
     "vrd_gather_pairs": (C.c_int, [C.POINTER(GatherArgs), C.c_void_p]),
+    "vrd_gather_train": (C.c_int, [C.POINTER(GatherTrainArgs), C.c_void_p]),
     "vrd_assemble_pairs": (C.c_int, [C.POINTER(AssembleArgs), C.c_void_p]),
     "vrd_split_weight": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, c_f32p,
                                    C.c_void_p]),
@@ -285,7 +294,7 @@ def check(rc, what):
 
 # tags of the f16 operand-range flag word (vrd_f16_range_flag; enum RangeTag of csrc/vrd_common.h): the entry points that OR each
 # bit.  A value x reports from |x| >= 4095 on (|x * 2^4| >= 65520 rounds to hi = inf); |x| < 4094 is the documented safe bound.
-RANGE_TAGS = {1: "boundary tensors (vrd_bct_to_btc / vrd_pack_pairs / vrd_gather_pairs)",
+RANGE_TAGS = {1: "boundary tensors (vrd_bct_to_btc / vrd_pack_pairs / vrd_gather_pairs / vrd_gather_train)",
               2: "vrd_layernorm / vrd_conv_ln outputs",
               4: "vrd_dwconv_ln outputs",
               8: "pair-row outputs of vrd_gemm / vrd_gemm_batch",

@@ -313,6 +313,16 @@ class MaskVRD(nn.Module):
             outs.append(self._heads(*self.backbone.cl(x, m), with_aux))
         return self._merge(outs)
 
+    def _mask_vrd_parts(self, vis, clip, so_box, ent, masks2d, with_aux=None):
+        """`_mask_vrd` from the backbone's operand buffers (ops.gather_train) instead of the (B, C_in, T) boundary tensor:
+        what `_mask_vrd` runs behind `backbone._unpack`, in one launch wave."""
+        B = masks2d.shape[0]
+        if B > self._chunk_size(B):
+            raise ValueError(f"a device-built training batch runs as one launch wave: {B} sequences exceed pair_chunk = {self.pair_chunk}")
+        if self.training and torch.is_grad_enabled():
+            _ops().presplit_weights(self._dense_conv_weights(), self.__dict__.setdefault("_split_plans", {}))
+        return self._heads(*self.backbone.cl_parts(vis, clip, so_box, ent, masks2d), with_aux)
+
     def __deepcopy__(self, memo):
         """copy.deepcopy(model) (ModelEma does it, utils/train_utils.py:13): the derived-operand caches stay behind -- their
         job tables point at THIS model's buffers, and the copy builds its own on first use."""
@@ -368,6 +378,8 @@ class MaskVRD(nn.Module):
     def forward_training(self, input_data):
         """Loss dict of reference maskvrd.py:169-199: batching, network, Hungarian matching and the class / focal /
         dice losses (+ one set per auxiliary decoder layer), ending in 'total_loss'.
+        input_data: the dataloader's lists (so_features_list, preds_list, masks_list, segs_list: proposals.train_getitem) or
+        {'train_source': proposals.TrainSource, 'train_tables': proposals.TrainTables}: the batch is then gathered on the device.
         With autograd recording (a training step, train.py:182-186) the network runs the differentiable HIP ops of
         vrdone_amd/autograd.py, AffineDropPath samples per-sample keep factors, and total_loss.backward() reaches
         every parameter.  Under torch.no_grad() it is the validation loss on the fused inference kernels."""
@@ -385,12 +397,27 @@ class MaskVRD(nn.Module):
         if guard:
             flag = ops.f16_range_flag(pdev)
             flag.zero_()
-        x, m = self._train_batch(input_data['so_features_list'])
-        if torch.is_grad_enabled() and self.training and train_graph.enabled(self):
-            predictions = train_graph.mask_vrd(self, x, m)        # two HIP-graph replays instead of ~2,000 launches
+        graphs = torch.is_grad_enabled() and self.training and train_graph.enabled(self)
+        if 'train_source' in input_data:
+            # a batch built on the device (proposals.TrainSource / train_tables): one gather launch writes the operand buffers of
+            # the backbone's first stage and the target masks -- no (B, C_in, T) tensor, no vrd_bct_to_btc
+            source, tables = input_data['train_source'], input_data['train_tables']
+            if graphs:
+                predictions, targets = train_graph.mask_vrd_source(self, source, tables)
+            else:
+                bb = self.backbone
+                *parts, m2, targets = ops.gather_train(source, tables, self.max_seq_len, bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())
+                predictions = self._mask_vrd_parts(*parts, m2, with_aux=self.deep_supervision)
+            d, sizes = tables.on_device(source), tables.sizes
+            ground_truth = {'preds_list': d["preds"].split(sizes), 'masks_list': targets.split(sizes), 'segs_list': d["segs"].split(sizes)}
         else:
-            predictions = self._mask_vrd(x, m, with_aux=self.deep_supervision)
-        losses = self.criterion(predictions, input_data)
+            ground_truth = input_data
+            x, m = self._train_batch(input_data['so_features_list'])
+            if graphs:
+                predictions = train_graph.mask_vrd(self, x, m)        # two HIP-graph replays instead of ~2,000 launches
+            else:
+                predictions = self._mask_vrd(x, m, with_aux=self.deep_supervision)
+        losses = self.criterion(predictions, ground_truth)
         if guard:
             # (one 4-byte read behind the step's launches: a host synchronisation, like the loss.item() of the reference's loop,
             # train.py:188-191.  Under torch.distributed every rank must take the same branch -- a rank that repeated its step

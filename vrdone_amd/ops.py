@@ -629,6 +629,52 @@ def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False
     return vis, clip, so_box, ent, mask
 
 
+def train_buffers(B, T, V, Cc, S, E, device):
+    """Fresh operand buffers of a B-sequence training batch, in gather_train's `out=` order: [vis (2B, T, V), so_box
+    (B, T, S), ent (2B, T, E), mask (B, T) bool] + [clip (2B, T, Cc)] when Cc."""
+    new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)      # noqa: E731
+    bufs = [new(2 * B, T, V), new(B, T, S), new(2 * B, T, E), torch.empty(B, T, device=device, dtype=torch.bool)]
+    return bufs + ([new(2 * B, T, Cc)] if Cc else [])
+
+
+def gather_train(source, tables, T, S, E, pair_wide, out=None):
+    """The training batch of `tables` (proposals.TrainTables) from the rows of `source` (proposals.TrainSource), one launch
+    (vrd_gather_train): the backbone's operand buffers at T frames -- written into `out` (train_buffers' list: a training
+    graph's input buffers) when given -- and the (G, T) 0/1 target masks of all relations.
+    Returns (vis, clip or None, so_box, ent, mask (B, T) bool, targets)."""
+    assert S == 5 and E == 8, "the reference's box features are 5 (pair) + 8 (entity) channels (utils/misc.py:158-217)"
+    B = len(tables)
+    if B == 0:
+        raise ValueError("gather_train: the tables hold no sequence")
+    dev = source.vis.device
+    V, Cc = source.n_visual, source.n_clip
+    if tables.max_seq_len != T:
+        raise ValueError(f"gather_train: tables made for max_seq_len {tables.max_seq_len}, batch length {T}")
+    d = tables.on_device(source)
+    G = d["preds"].shape[0]
+    bufs = train_buffers(B, T, V, Cc, S, E, dev) if out is None else out
+    vis, so_box, ent, mask = bufs[:4]
+    clip = bufs[4] if Cc else None
+    assert vis.shape == (2 * B, T, V) and so_box.shape == (B, T, S) and ent.shape == (2 * B, T, E) and mask.shape == (B, T)
+    assert mask.dtype == torch.bool and all(t.is_contiguous() and t.device == dev for t in bufs)
+    for t in (source.vis, source.clip, source.boxes):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.device == dev)
+    targets = torch.empty(G, T, device=dev, dtype=torch.float32)
+    a = _hip.GatherTrainArgs()
+    a.vis, a.clip, a.boxes = source.vis.data_ptr(), _ptr(source.clip), source.boxes.data_ptr()
+    a.s_row, a.o_row, a.lens, a.lead = d["s_row"].data_ptr(), d["o_row"].data_ptr(), d["lens"].data_ptr(), d["lead"].data_ptr()
+    a.seq_wh, a.seg_lo, a.seg_hi = d["seq_wh"].data_ptr(), d["seg_lo"].data_ptr(), d["seg_hi"].data_ptr()
+    a.P, a.G, a.T, a.V, a.Cc, a.stride = B, G, T, V, Cc, tables.stride
+    a.out_vis, a.out_clip, a.out_so_box, a.out_ent = vis.data_ptr(), _ptr(clip), so_box.data_ptr(), ent.data_ptr()
+    a.out_mask, a.out_targets = mask.data_ptr(), targets.data_ptr()
+    a.pair_wide = _fmt(pair_wide)
+    _hip.check(lib.vrd_gather_train(C.byref(a), _stream()), "vrd_gather_train")
+    if a.pair_wide:
+        vis = Pair(vis, V, a.pair_wide)
+        clip = Pair(clip, Cc, a.pair_wide) if Cc else None
+    return vis, clip, so_box, ent, mask, targets
+
+
 def assemble_pairs(streams, snippets, stream_row, lens, T, piece, reach):
     """(2P, T, D) entity-stage rows of P pairs from rows computed once per tracklet (`streams`, any shape (..., D);
     stream_row (2P,) int64 = row of frame 0 of each subject then object) and the window-edge pieces `snippets`

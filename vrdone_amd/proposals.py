@@ -246,7 +246,8 @@ def prepare_test_proposal(raw, feat_stride, stride_offset, proposal_min_frames, 
 # --------------------------------------------------------------------------------------------------------------------
 # Training side: the per-video ground-truth cache and the per-step sample construction of the reference's
 # training dataloader.  Host code (the sample construction draws from Python's `random`, call for call like the reference,
-# so that a seeded run sees the same crops); the model side takes the resulting lists as `forward_training` input.
+# so that a seeded run sees the same crops); the model side takes the resulting lists as `forward_training` input -- or, further
+# down, a device-resident TrainSource and the index tables of `train_tables`, from which it gathers the batch itself.
 # --------------------------------------------------------------------------------------------------------------------
 def load_train_video(anno_json, gt_features_pkl, entity_cat_name_to_id, pred_cat_name_to_id):
     """One training video's cache entry; restates `_prepare_train`, dataloaders/vidvrd.py:172-322.
@@ -343,15 +344,11 @@ def load_train_video(anno_json, gt_features_pkl, entity_cat_name_to_id, pred_cat
             "entity_classes": classes, "traj_intervals": intervals}
 
 
-def truncate_feats(so_feat, pred, segment, max_seq_len, trunc_thresh=0.5, max_times=10, rng=None):
-    """Random max_seq_len crop of a pair that keeps at least one relation >= trunc_thresh inside (reference
-    utils/misc.py:219-273, which derives from ActionFormer); None when ten draws find none.  so_feat (C, L), segment
-    (N, 2) in feature steps.  Draws `rng.randint(0, L - max_seq_len)` per try, like the reference's `random.randint`."""
+def _truncate_window(L, pred, segment, max_seq_len, trunc_thresh=0.5, max_times=10, rng=None):
+    """The decision half of `truncate_feats`: (start, kept predicates, their segments relative to start) of the max_seq_len
+    window out of L > max_seq_len steps, or None; the same draws from `rng`."""
     import random
     rng = rng or random
-    L = so_feat.shape[1]
-    if L <= max_seq_len:
-        return so_feat, pred, segment
     for _ in range(max_times):
         st = rng.randint(0, L - max_seq_len)
         ed = st + max_seq_len
@@ -360,8 +357,22 @@ def truncate_feats(so_feat, pred, segment, max_seq_len, trunc_thresh=0.5, max_ti
         inter = (right - left).clamp(min=0)
         keep = inter / (segment[:, 1] - segment[:, 0]).abs() >= trunc_thresh
         if int(keep.sum()) > 0:
-            return so_feat[:, st:ed], pred[keep], torch.stack((left[keep], right[keep]), dim=1) - st
+            return st, pred[keep], torch.stack((left[keep], right[keep]), dim=1) - st
     return None
+
+
+def truncate_feats(so_feat, pred, segment, max_seq_len, trunc_thresh=0.5, max_times=10, rng=None):
+    """Random max_seq_len crop of a pair that keeps at least one relation >= trunc_thresh inside (reference
+    utils/misc.py:219-273, which derives from ActionFormer); None when ten draws find none.  so_feat (C, L), segment
+    (N, 2) in feature steps.  Draws `rng.randint(0, L - max_seq_len)` per try, like the reference's `random.randint`."""
+    L = so_feat.shape[1]
+    if L <= max_seq_len:
+        return so_feat, pred, segment
+    win = _truncate_window(L, pred, segment, max_seq_len, trunc_thresh, max_times, rng)
+    if win is None:
+        return None
+    st, pred, segment = win
+    return so_feat[:, st:st + max_seq_len], pred, segment
 
 
 def _so_box_features(sb, ob):
@@ -445,6 +456,214 @@ def train_getitem(video, feat_stride, max_seq_len, cut_max_preds=False, proposal
     if not feats_out:
         return {}
     return {"so_features_list": feats_out, "preds_list": preds_out, "masks_list": masks_out, "segs_list": segs_out}
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Training batches built on the device: `TrainSource` keeps a cache entry's rows on the device, `train_tables` makes
+# train_getitem's decisions (same draws, same `continue` rules) on indices alone, and MaskVRD.forward_training gathers
+# the operand buffers and the target masks from the two in one launch (vrd_gather_train).
+# --------------------------------------------------------------------------------------------------------------------
+class TrainVideo:
+    """The host side of one video inside a TrainSource: its relation tables, and where each trajectory interval's rows
+    start in the source's arrays (`first_row[(trajectory, interval)]`, counted from `row0`)."""
+
+    def __init__(self, index, row0, entry, first_row, n_rows):
+        self.index, self.row0, self.first_row, self.n_rows = int(index), int(row0), first_row, int(n_rows)
+        self.video_hw = tuple(entry["video_hw"]) if entry else None
+        self.relation_merged = entry["relation_merged"] if entry else {}
+        self.relation_keys = entry["relation_keys"] if entry else []
+        self.traj_intervals = entry["traj_intervals"] if entry else {}
+
+    def moved(self, index, row0):
+        new = TrainVideo.__new__(TrainVideo)
+        new.__dict__.update(self.__dict__)
+        new.index, new.row0 = int(index), int(row0)
+        return new
+
+    def __bool__(self):
+        return bool(self.relation_keys)
+
+
+class TrainSource:
+    """A training cache entry (load_train_video) with its per-frame rows on the device: vis (R, V), clip (R, Cc) or None and
+    the clamped boxes (R, 4), interval after interval in (trajectory, interval) order -- the layout of PairSource --; the
+    relation tables stay on the host (`videos`).  `concat` puts several videos into one row space: a step of train_policy
+    spans several videos."""
+
+    def __init__(self, vis, clip, boxes, videos):
+        self.vis, self.clip, self.boxes, self.videos = vis, clip, boxes, list(videos)
+        self.n_visual = 0 if vis is None else vis.shape[1]
+        self.n_clip = 0 if clip is None else clip.shape[1]
+        # (n videos, 2) w, h: what sequence p's boxes are normalised by, looked up through TrainTables.src
+        self.frame_wh = np.asarray([(v.video_hw[1], v.video_hw[0]) if v.video_hw else (1, 1) for v in self.videos], dtype=np.float32)
+
+    @classmethod
+    def from_entry(cls, entry, device):
+        if not entry:
+            return cls(None, None, None, [TrainVideo(0, 0, {}, {}, 0)])
+        h, w = entry["video_hw"]
+        first_row, vis, boxes, clip, at = {}, [], [], [], 0
+        for t in sorted(entry["visual_features"]):
+            for i, rows in enumerate(entry["visual_features"][t]):
+                first_row[(t, i)] = at
+                at += rows.shape[0]
+                vis.append(rows)
+                boxes.append(_clamped(entry["entity_bboxes"][t][i], w, h))
+                assert boxes[-1].shape[0] == rows.shape[0]
+                if "clip_features" in entry:
+                    clip.append(entry["clip_features"][t][i])
+        put = lambda ts: torch.cat(ts, dim=0).to(device=device, dtype=torch.float32).contiguous()        # noqa: E731
+        return cls(put(vis), put(clip) if clip else None, put(boxes), [TrainVideo(0, 0, entry, first_row, at)])
+
+    @classmethod
+    def concat(cls, sources):
+        """One source over the rows of several: video j of the result is `videos[j]`, its rows moved behind those of the
+        sources in front of it; every video keeps its own frame size.  Empty sources (no rows) keep their place in `videos`."""
+        sources = list(sources)
+        assert sources, "TrainSource.concat needs at least one source"
+        full = [s for s in sources if s.vis is not None]
+        if len({(s.n_visual, s.n_clip) for s in full}) > 1:
+            raise ValueError("TrainSource.concat: the sources have different feature widths")
+        videos, at = [], 0
+        for s in sources:
+            for v in s.videos:
+                videos.append(v.moved(len(videos), at + v.row0))
+            at += 0 if s.vis is None else s.vis.shape[0]
+        if not full:
+            return cls(None, None, None, videos)
+        cat = lambda ts: torch.cat(ts, dim=0).contiguous()         # noqa: E731
+        return cls(cat([s.vis for s in full]), None if full[0].clip is None else cat([s.clip for s in full]),
+                   cat([s.boxes for s in full]), videos)
+
+    def __len__(self):
+        return len(self.videos)
+
+
+class TrainTables:
+    """train_tables' result: per surviving relation key the first subject / object row in the source (sub-sampling offset
+    and crop folded in), its length, `lead` (sub-sampled frames in front of the crop: what the first frame's box differences
+    look back to) and the video it belongs to; per key `preds` (N,) int64 and `segs` (N, 2) like train_getitem's lists."""
+
+    def __init__(self, stride, max_seq_len, keys=(), s_row=(), o_row=(), lens=(), lead=(), src=(), preds=(), segs=()):
+        self.stride, self.max_seq_len = int(stride), int(max_seq_len)
+        self.keys = list(keys)
+        self.s_row, self.o_row = np.asarray(s_row, dtype=np.int64), np.asarray(o_row, dtype=np.int64)
+        self.lens, self.lead, self.src = (np.asarray(a, dtype=np.int32) for a in (lens, lead, src))
+        self.preds, self.segs = list(preds), list(segs)
+        self._device = None
+
+    def __len__(self):
+        return len(self.keys)
+
+    @property
+    def sizes(self):
+        return [int(p.shape[0]) for p in self.preds]
+
+    @classmethod
+    def concat(cls, tables):
+        """The keys of several tables (the (video, pair_duration) slices of one train_policy step, all addressing ONE
+        TrainSource) one after the other."""
+        tables = list(tables)
+        assert tables and len({(t.stride, t.max_seq_len) for t in tables}) == 1
+        cat = lambda name: np.concatenate([getattr(t, name) for t in tables])          # noqa: E731
+        return cls(tables[0].stride, tables[0].max_seq_len, [k for t in tables for k in t.keys], cat("s_row"), cat("o_row"),
+                   cat("lens"), cat("lead"), cat("src"), [p for t in tables for p in t.preds], [s for t in tables for s in t.segs])
+
+    def check(self, source):
+        """Every row the gather will read lies inside the source (the kernel trusts the tables)."""
+        n_rows = 0 if source.boxes is None else source.boxes.shape[0]
+        back = np.minimum(self.lead, 1).astype(np.int64) * self.stride
+        last = (self.lens.astype(np.int64) - 1) * self.stride
+        for row in (self.s_row, self.o_row):
+            if len(row) and (int((row - back).min()) < 0 or int((row + last).max()) >= n_rows):
+                raise ValueError("TrainTables: a sequence reaches outside its source's rows (tables of another source?)")
+        if len(self.src) and (int(self.src.min()) < 0 or int(self.src.max()) >= len(source.videos)):
+            raise ValueError("TrainTables: video index outside the source")
+        if len(self.lens) and (int(self.lens.min()) < 2 or int(self.lens.max()) > self.max_seq_len):
+            raise ValueError("TrainTables: sequence lengths must lie in [2, max_seq_len]")
+
+    def on_device(self, source):
+        """The tables as device tensors, uploaded once, in ONE host-to-device copy: {s_row, o_row (K,) int64; lens, lead (K,)
+        int32; seq_wh (K, 2) float32; seg_lo, seg_hi (G,) int32; preds (G,) int64; segs (G, 2) in the dtype torch.cat gives
+        the per-key lists}."""
+        dev = source.boxes.device
+        if self._device is not None and self._device[0] is source:
+            return self._device[1]
+        self.check(source)
+        segs = torch.cat(self.segs, dim=0)
+        seg_i = segs.to(torch.int64)
+        if not bool(((seg_i[:, 0] >= 0) & (seg_i[:, 0] < seg_i[:, 1]) & (seg_i[:, 1] <= self.max_seq_len)).all()):
+            raise ValueError("TrainTables: a relation segment lies outside [0, max_seq_len]")
+        parts = [("s_row", self.s_row), ("o_row", self.o_row), ("preds", torch.cat(self.preds).to(torch.int64).numpy()),
+                 ("segs", segs.contiguous().numpy().reshape(-1)), ("lens", self.lens), ("lead", self.lead),
+                 ("seq_wh", source.frame_wh[self.src].reshape(-1)), ("seg_lo", seg_i[:, 0].numpy().astype(np.int32)),
+                 ("seg_hi", seg_i[:, 1].numpy().astype(np.int32))]
+        parts.sort(key=lambda kv: -kv[1].dtype.itemsize)               # 8-byte tables first: every view stays aligned
+        raw = np.concatenate([np.ascontiguousarray(a).view(np.uint8).reshape(-1) for _, a in parts])
+        buf = torch.from_numpy(raw).to(dev)
+        out, at = {}, 0
+        for name, a in parts:
+            out[name] = buf[at:at + a.nbytes].view(torch.from_numpy(a[:0].copy()).dtype)
+            at += a.nbytes
+        out["seq_wh"] = out["seq_wh"].view(-1, 2)
+        out["segs"] = out["segs"].view(-1, 2)
+        self._device = (source, out)
+        return out
+
+
+def train_tables(video, feat_stride, max_seq_len, cut_max_preds=False, proposal_max_preds=0, pair_duration=None, rng=None):
+    """train_getitem's decisions without its tensors: `video` is a one-video TrainSource or one of a concatenated source's
+    `videos`; same arguments, same draws from `rng` in the same order (the sub-sampling offset per key, the crop draws of
+    truncate_feats), same `continue` rules.  Touches no feature row.  Returns TrainTables (len 0 when nothing survives)."""
+    import random
+    rng = rng or random
+    if isinstance(video, TrainSource):
+        assert len(video.videos) == 1, "train_tables takes one video: pass source.videos[j] of a concatenated source"
+        video = video.videos[0]
+    out = TrainTables(feat_stride, max_seq_len)
+    if not video:
+        return out
+    merged, keys = video.relation_merged, video.relation_keys
+    if pair_duration is not None:
+        keys = keys[pair_duration[0]:pair_duration[1]]
+        merged = {k: v for k, v in merged.items() if list(k) in keys}
+    rows = {name: [] for name in ("s_row", "o_row", "lens", "lead")}
+    for key in merged:
+        offset = rng.randint(0, feat_stride - 1)
+        s, o, si, oi = key
+        if cut_max_preds and proposal_max_preds < len(merged[key]):
+            continue
+        s_iv, o_iv = video.traj_intervals[s][si], video.traj_intervals[o][oi]
+        lo, hi = max(s_iv[0], o_iv[0]), min(s_iv[1], o_iv[1])
+        L = len(range(offset, max(hi - lo, 0), feat_stride))              # frames of per[lo - iv[0]:hi - iv[0]][offset::feat_stride]
+        if L < 2:
+            continue
+        preds, segs = [], []
+        for r in merged[key]:
+            left = np.ceil((r["begin_fid"] - lo - offset) / feat_stride)
+            right = np.ceil((r["end_fid"] - lo - offset) / feat_stride)
+            if left < right:
+                preds.append(r["predicate"])
+                segs.append([left, right])
+        if not preds:
+            continue
+        preds, segs, st = torch.tensor(preds, dtype=torch.int64), torch.tensor(np.array(segs), dtype=torch.int64), 0
+        if L > max_seq_len:
+            win = _truncate_window(L, preds, segs, max_seq_len, rng=rng)
+            if win is None:
+                continue
+            st, preds, segs = win
+            L = max_seq_len
+        first = lo + offset + st * feat_stride
+        rows["s_row"].append(video.row0 + video.first_row[(s, si)] + first - s_iv[0])
+        rows["o_row"].append(video.row0 + video.first_row[(o, oi)] + first - o_iv[0])
+        rows["lens"].append(L)
+        rows["lead"].append(st)
+        out.keys.append(tuple(key))
+        out.preds.append(preds)
+        out.segs.append(segs)
+    return TrainTables(feat_stride, max_seq_len, out.keys, rows["s_row"], rows["o_row"], rows["lens"], rows["lead"],
+                       [video.index] * len(out.keys), out.preds, out.segs)
 
 
 def train_policy(video_num_pairs, num_pairs):

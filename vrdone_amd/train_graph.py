@@ -52,18 +52,19 @@ def _storage_key(model):
 
 
 class _Recording:
-    """Forward and backward graph of `model._mask_vrd` for one batch shape."""
+    """Forward and backward graph of the network for one batch shape: `network(*inputs)` is `model._mask_vrd` on the padded
+    batch and its mask, or `model._mask_vrd_parts` on the operand buffers a device-built batch is gathered into."""
 
-    def __init__(self, model, x, m):
+    def __init__(self, model, inputs, network_of):
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.storage = _storage_key(model)
         aliases = [nn.Parameter(p.detach()) for p in self.params]             # same storage, no autograd history
         by_id = {id(p): a for p, a in zip(self.params, aliases)}
         slots = [(mod, name, p) for mod in model.modules() for name, p in mod._parameters.items() if id(p) in by_id]
-        self.static_x, self.static_m = x.clone(), m.clone()
+        self.static_in = [t.clone() for t in inputs]
 
         def network():
-            return model._mask_vrd(self.static_x, self.static_m, with_aux=model.deep_supervision)
+            return network_of(*self.static_in)
 
         def grad_outputs(flat):
             return [torch.empty_like(o) if o.requires_grad else None for o in flat]
@@ -98,16 +99,18 @@ class _Recording:
             for mod, name, p in slots:
                 mod._parameters[name] = p
 
-    def __call__(self, x, m):
-        flat = _Replay.apply(self, x, m, *self.params)
+    def __call__(self, *inputs):
+        flat = _Replay.apply(self, len(inputs), *inputs, *self.params)
         return pytree.tree_unflatten(list(flat), self.spec)
 
 
 class _Replay(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rec, x, m, *params):
-        rec.static_x.copy_(x)
-        rec.static_m.copy_(m)
+    def forward(ctx, rec, n_in, *args):
+        for buf, t in zip(rec.static_in, args[:n_in]):
+            if t.data_ptr() != buf.data_ptr():       # (a batch gathered straight into the recording's buffers is already there)
+                buf.copy_(t)
+        ctx.n_in = n_in
         rec.fwd.replay()
         ctx.rec = rec
         outs = tuple(o.detach() for o in rec.static_out)
@@ -138,7 +141,7 @@ class _Replay(torch.autograd.Function):
                                    ".grad before the next step (gradient accumulation)")
             else:
                 out.append(g.detach().clone() if p.grad is not None else g.detach())
-        return (None, None, None) + tuple(out)
+        return (None, None) + (None,) * ctx.n_in + tuple(out)
 
 
 def enable(model, on=True):
@@ -162,7 +165,7 @@ def recordings(model):
     return {} if state is None else state["recordings"]
 
 
-def recording_key(model, x, m):
+def _mode_key(model):
     """Everything that shapes the captured launch sequence besides the batch shape: precision mode, launch-wave size, the
     stochastic-depth probabilities and pinned keep vectors of every AffineDropPath, which parameters train, and (last) the
     deterministic mode (its gradient kernels take other launches and scratch)."""
@@ -170,29 +173,66 @@ def recording_key(model, x, m):
     drops = tuple((mod.drop_prob, None if mod.keep is None else mod.keep.data_ptr()) for mod in model.modules()
                   if isinstance(mod, AffineDropPath))
     trainable = tuple(p.requires_grad for p in model.parameters())
-    return (tuple(x.shape), tuple(m.shape), bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops,
-            trainable, ops.get_deterministic())
+    return (bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops, trainable, ops.get_deterministic())
+
+
+def recording_key(model, x, m):
+    """The key of the recording a padded batch x, m replays: its shapes and `_mode_key`."""
+    return (tuple(x.shape), tuple(m.shape)) + _mode_key(model)
+
+
+def _recording(model, key):
+    """The recording of `key`, or None (not recorded yet, or stale: the parameters were replaced or moved)."""
+    graphs = _GRAPHS[model]["recordings"]
+    rec = graphs.get(key)
+    if rec is not None and rec.storage != _storage_key(model):
+        graphs.clear()                         # every recording is stale
+        rec = None
+    return rec
+
+
+def _record(model, key, inputs, network_of):
+    graphs = _GRAPHS[model]["recordings"]
+    assert all(t.is_cuda and not t.requires_grad for t in inputs)
+    if key[-1]:
+        # the warm-up runs draw stochastic-depth factors: the recording leaves the generator as it found it, so that the
+        # replay that follows draws what an eager step would have drawn from the state the caller seeded
+        with torch.random.fork_rng(devices=[inputs[0].device]):
+            rec = graphs[key] = _Recording(model, inputs, network_of)
+    else:
+        rec = graphs[key] = _Recording(model, inputs, network_of)
+    return rec
 
 
 def mask_vrd(model, x, m):
     """`model._mask_vrd(x, m, with_aux=model.deep_supervision)` through the recorded graphs (recorded on the first use of a
     batch shape; that call replays them too and returns real predictions)."""
-    graphs = _GRAPHS[model]["recordings"]
     key = recording_key(model, x, m)
-    det = key[-1]
-    rec = graphs.get(key)
-    if rec is not None and rec.storage != _storage_key(model):
-        graphs.clear()                         # the parameters were replaced or moved: every recording is stale
-        rec = None
+    rec = _recording(model, key)
     if rec is None:
-        if len(graphs) >= MAX_SHAPES:
+        if len(_GRAPHS[model]["recordings"]) >= MAX_SHAPES:
             return model._mask_vrd(x, m, with_aux=model.deep_supervision)
-        assert x.is_cuda and not x.requires_grad
-        if det:
-            # the warm-up runs draw stochastic-depth factors: the recording leaves the generator as it found it, so that the
-            # replay below draws what an eager step would have drawn from the state the caller seeded
-            with torch.random.fork_rng(devices=[x.device]):
-                rec = graphs[key] = _Recording(model, x, m)
-        else:
-            rec = graphs[key] = _Recording(model, x, m)
+        rec = _record(model, key, [x, m], lambda sx, sm: model._mask_vrd(sx, sm, with_aux=model.deep_supervision))
     return rec(x, m)
+
+
+def mask_vrd_source(model, source, tables):
+    """The training network on a batch gathered from a proposals.TrainSource: (predictions, target masks (G, T)).  The gather
+    (ops.gather_train) runs outside the graphs and writes straight into the recording's input buffers -- the operand buffers of
+    the backbone's first stage --, so a replayed step is one gather launch and the two replays; the first use of a batch shape
+    gathers into fresh buffers, records, and replays like `mask_vrd`."""
+    bb = model.backbone
+    B, T = len(tables), model.max_seq_len
+    key = (("operand buffers", B, T, source.n_visual, source.n_clip),) + _mode_key(model)
+    rec = _recording(model, key)
+    gather = lambda out: ops.gather_train(source, tables, T, bb.n_bbox_so, bb.n_bbox_entity, False, out=out)      # noqa: E731
+    if rec is None:
+        *parts, m2, targets = gather(None)
+        inputs = [parts[0], parts[2], parts[3], m2] + ([parts[1]] if parts[1] is not None else [])       # train_buffers' order
+        if len(_GRAPHS[model]["recordings"]) >= MAX_SHAPES:
+            return model._mask_vrd_parts(*parts, m2, with_aux=model.deep_supervision), targets
+        rec = _record(model, key, inputs, lambda vis, so_box, ent, sm, clip=None:
+                      model._mask_vrd_parts(vis, clip, so_box, ent, sm, with_aux=model.deep_supervision))
+        return rec(*inputs), targets
+    targets = gather(rec.static_in)[-1]
+    return rec(*rec.static_in), targets
