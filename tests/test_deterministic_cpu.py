@@ -1,6 +1,7 @@
 """The deterministic mode's switch, its graph-recording key and the C ABI of its gradient kernels (no GPU needed: the
 library validates arguments -- the mode's scratch requirement included -- before any device access)."""
 import ctypes
+import json
 import os
 import re
 import subprocess
@@ -155,6 +156,32 @@ def test_deterministic_calls_without_scratch_are_refused_before_any_launch():
     assert lib.vrd_layernorm_bwd(P, C, P, C, rows, C, P, P, 0, P, C, P, P, None, 0, None, D) == _hip.ERR_SCRATCH
     # unknown flag bits are an argument error
     assert lib.vrd_colsum(P, C, None, 0, 1, 0, 1, 0, 1, None, None, rows, C, P, None, 0, None, 2) == -1
+
+
+def test_scratch_need_matches_the_recorded_chunking():
+    """tests/golden/det_scratch_need.json (scripts/record_det_scratch_need.py): the scratch every deterministic gradient call of a
+    grid of shapes asked for when the file was recorded.  The need is the kernel form, the row chunks / row blocks and the depth
+    of the reduction tree in one number -- the summation order -- so it must not move; aligned and shifted operands ask for the
+    same.  One float less than the need is refused again."""
+    from vrdone_amd import _hip
+    with open(os.path.join(REPO, "tests", "golden", "det_scratch_need.json")) as f:
+        doc = json.load(f)
+    assert {c["fn"] for c in doc["calls"]} == set(GRAD_CALLS)
+    wrong = []
+    for c in doc["calls"]:
+        fn, args, at, need = getattr(_hip.lib, c["fn"]), list(c["args"]), doc["scratch_arg"][c["fn"]], c["need"]
+        assert args[at] is None and args[at + 1] == 0 and args[-1] == _hip.DETERMINISTIC
+        if need == 0:
+            # no scratch: the call goes on to its launches, which dummy addresses allow only where there is no device to reach
+            if not torch.cuda.is_available() and fn(*args) == _hip.ERR_SCRATCH:
+                wrong.append((c, _need()))
+            continue
+        if fn(*args) != _hip.ERR_SCRATCH or _need() != need:
+            wrong.append((c, _need()))
+        args[at], args[at + 1] = 256, need - 1
+        if fn(*args) != _hip.ERR_SCRATCH or _need() != need:
+            wrong.append((c, "one float short", _need()))
+    assert not wrong, wrong[:10]
 
 
 def test_flags_default_to_zero_for_earlier_callers():

@@ -1,4 +1,4 @@
-"""Backward kernels (csrc/vrd_backward.hip) and the autograd layer (vrdone_amd/autograd.py) on a real MI355X.
+"""Backward kernels (csrc/vrd_backward.hip, vrd_wgrad.hip, vrd_colsum.hip) and the autograd layer (vrdone_amd/autograd.py) on a real MI355X.
 
 Every differentiable op is compared -- outputs and the gradients of every input and parameter -- with torch.autograd
 through the oracle's functional restatement of the same reference code (oracle/vrd_oracle.py), evaluated on the CPU in

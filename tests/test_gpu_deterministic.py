@@ -81,7 +81,7 @@ def _rel(got, want):
     return float((got.double() - want).norm() / want.norm().clamp_min(1e-30))
 
 
-def _wgrad_want(G, X, mask, k):
+def _wgrad_want(G, X, mask, k, T=T):
     Gm = (G * mask[:, None]).double()
     Xs = X.double().view(-1, T, X.shape[1])
     taps = [torch.nn.functional.pad(Xs, (0, 0, 1, 1))[:, t:t + T].reshape(-1, X.shape[1]) for t in range(3)] if k == 3 else [X.double()]
@@ -202,6 +202,140 @@ def test_layernorm_backward_bits(C):
     xhat = (xd - xd.mean(1, keepdim=True)) / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + 1e-5)
     assert _rel(dg, (dy.double() * xhat).sum(0)) <= 1e-6
     assert _rel(db, dy.double().sum(0)) <= 1e-6
+
+
+# Small inputs: the same calls where the scratch holds few partial rows -- 33 of them (the first two-level reduction), one block,
+# two chunks, tile partials + bias rows + their levels in one buffer.  _variants' NaN-filled scratch shows a region read before it
+# was written or a level written over another.  Tolerances: those of the 49 k-row tests above.
+TS = 16            # frames per sequence of the small inputs
+
+
+def _small_colsum(rows, C):
+    from vrdone_amd import _hip
+    g = torch.Generator().manual_seed(rows + C)
+    a, b = torch.randn(rows, C, generator=g), torch.randn(rows, C, generator=g)
+    mask, rs = (torch.rand(rows, generator=g) < 0.8).to(torch.uint8), torch.rand(rows, generator=g)
+    ins = {off: (_placed(a, off), _placed(b, off)) for off in (0, 1, 4)}
+    md, rd = mask.to(DEV), rs.to(DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(off, outs, sp, n):
+        ad, bd = ins[off]
+        return _hip.lib.vrd_colsum(ad.data_ptr(), C, bd.data_ptr(), C, 1, 0, 1, 0, TS, md.data_ptr(), rd.data_ptr(), rows, C, outs[0].data_ptr(),
+                                   sp, n, stream, _hip.DETERMINISTIC)
+
+    (got,) = _variants(call, [torch.zeros(C, device=DEV)])
+    assert _rel(got, ((a * mask[:, None] * rs[:, None]).double() * b.double()).sum(0)) <= 1e-6
+
+
+def _small_dwconv(rows, C, ks, gin, stride):
+    from vrdone_amd import _hip
+    g = torch.Generator().manual_seed(rows + ks + 10 * gin)
+    dD, x = torch.randn(rows, C, generator=g), torch.randn(rows * stride, C * gin, generator=g)
+    mask = (torch.rand(rows, generator=g) < 0.8).to(torch.uint8)
+    ins = {off: (_placed(dD, off), _placed(x, off)) for off in (0, 1, 4)}
+    md = mask.to(DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(off, outs, sp, n):
+        dd, xd = ins[off]
+        return _hip.lib.vrd_dwconv_wgrad(dd.data_ptr(), C, xd.data_ptr(), C * gin, ks, stride, gin, TS, md.data_ptr(), rows, C,
+                                         outs[0].data_ptr(), outs[1].data_ptr(), sp, n, stream, _hip.DETERMINISTIC)
+
+    dw, db = _variants(call, [torch.zeros(C, gin, ks, device=DEV), torch.zeros(C, device=DEV)])
+    Gm = (dD * mask[:, None]).double().view(-1, TS, C)
+    xs = x.double().view(-1, stride * TS, C, gin)
+    want = torch.zeros(C, gin, ks, dtype=torch.float64)
+    for kk in range(ks):
+        ti = stride * torch.arange(TS) + kk - ks // 2
+        ok = (ti >= 0) & (ti < stride * TS)
+        want[:, :, kk] = (Gm[..., None] * (xs[:, ti.clamp(0, stride * TS - 1)] * ok[None, :, None, None])).sum((0, 1))
+    assert _rel(dw, want) <= 1e-6
+    assert _rel(db, Gm.sum((0, 1))) <= 1e-6
+
+
+def _small_layernorm(rows, C):
+    from vrdone_amd import _hip
+    g = torch.Generator().manual_seed(rows + C)
+    x, dy = torch.randn(rows, C, generator=g), torch.randn(rows, C, generator=g)
+    gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    ins = {off: (_placed(x, off), _placed(dy, off)) for off in (0, 4)}        # (the kernel wants 16-byte aligned rows)
+    gd, bd = gamma.to(DEV), beta.to(DEV)
+    dx = torch.empty(rows, C, device=DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(off, outs, sp, n):
+        xd, dyd = ins[off]
+        return _hip.lib.vrd_layernorm_bwd(xd.data_ptr(), C, dyd.data_ptr(), C, rows, C, gd.data_ptr(), bd.data_ptr(), 0, dx.data_ptr(), C,
+                                          outs[0].data_ptr(), outs[1].data_ptr(), sp, n, stream, _hip.DETERMINISTIC)
+
+    dg, db = _variants(call, [torch.zeros(C, device=DEV), torch.zeros(C, device=DEV)], offsets=(0, 4))
+    xd = x.double()
+    xhat = (xd - xd.mean(1, keepdim=True)) / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + 1e-5)
+    assert _rel(dg, (dy.double() * xhat).sum(0)) <= 1e-6
+    assert _rel(db, dy.double().sum(0)) <= 1e-6
+
+
+def _small_wgrad(plane, M, N, Cin, k):
+    """f32: vrd_gemm_wgrad; bf16 / f16: vrd_gemm_wgrad_x3 with dbias"""
+    from vrdone_amd import _hip
+    g = torch.Generator().manual_seed(M + N + k)
+    G, X = torch.randn(M, N, generator=g), torch.randn(M, Cin, generator=g)
+    mask = (torch.rand(M, generator=g) < 0.8).to(torch.uint8)
+    ins = {off: (_placed(G, off), _placed(X, off)) for off in (0, 1, 4)}
+    md = mask.to(DEV)
+    stream = torch.cuda.current_stream().cuda_stream
+    scale = None
+    if plane == "f16":           # (vrd_absmax_scale wants float4 rows: the factor of a copy padded with zero columns, the same maximum)
+        N4 = (N + 3) // 4 * 4
+        Gp = torch.zeros(M, N4, device=DEV)
+        Gp[:, :N] = G.to(DEV)
+        scale = torch.zeros(_hip.ABSMAX_SCALE_FLOATS, device=DEV)
+        _hip.check(_hip.lib.vrd_absmax_scale(Gp.data_ptr(), N4, M, N4, scale.data_ptr(), stream), "vrd_absmax_scale")
+
+    def call(off, outs, sp, n):
+        Gd, Xd = ins[off]
+        if plane == "f32":
+            return _hip.lib.vrd_gemm_wgrad(Gd.data_ptr(), N, Xd.data_ptr(), Cin, md.data_ptr(), M, N, Cin, k, TS, outs[0].data_ptr(), sp, n, stream,
+                                           _hip.DETERMINISTIC)
+        gs = scale.data_ptr() if plane == "f16" else None
+        return _hip.lib.vrd_gemm_wgrad_x3(Gd.data_ptr(), N, Xd.data_ptr(), Cin, md.data_ptr(), M, N, Cin, k, TS, outs[0].data_ptr(),
+                                          outs[1].data_ptr(), sp, n, gs, stream, _hip.DETERMINISTIC)
+
+    outs = [torch.zeros(N, k * Cin, device=DEV)] + ([] if plane == "f32" else [torch.zeros(N, device=DEV)])
+    res = _variants(call, outs)
+    if M * N * Cin > 1 << 30:    # (the float64 products of the largest case on the device: seconds on the CPU)
+        assert k == 1
+        Gm = (G * mask[:, None]).double().to(DEV)
+        want, want_b = (Gm.t() @ X.double().to(DEV)).cpu(), Gm.sum(0).cpu()
+    else:
+        want, want_b = _wgrad_want(G, X, mask, k, TS)
+    assert _rel(res[0], want) <= (1e-6 if plane == "f32" else 2e-5 if plane == "f16" else 2e-4)
+    if plane != "f32":
+        assert _rel(res[1], want_b) <= 2e-6
+
+
+SMALL_CASES = {
+    "colsum-528x8": (_small_colsum, 528, 8),                     # float4 form, 33 partial rows
+    "colsum-1056x6": (_small_colsum, 1056, 6),                   # scalar form, 33 partial rows
+    "colsum-16x4": (_small_colsum, 16, 4),                       # one block, no second level
+    "dwconv-528x8-k3g1s1": (_small_dwconv, 528, 8, 3, 1, 1),
+    "dwconv-1056x8-k3g2s2": (_small_dwconv, 1056, 8, 3, 2, 2),
+    "layernorm-1056x256": (_small_layernorm, 1056, 256),
+    "layernorm-1056x512": (_small_layernorm, 1056, 512),
+    "x3-bf16-192x133x63-k3": (_small_wgrad, "bf16", 192, 133, 63, 3),       # wave kernel + its own column-sum launch
+    "x3-f16-192x133x63-k3": (_small_wgrad, "f16", 192, 133, 63, 3),
+    "x3-bf16-4224x128x128-k1": (_small_wgrad, "bf16", 4224, 128, 128, 1),   # 33 chunks: tiles, bias rows and a two-level bias tree
+    "x3-f16-4224x128x128-k1": (_small_wgrad, "f16", 4224, 128, 128, 1),
+    "x3-f16-65536x256x256-k1": (_small_wgrad, "f16", 65536, 256, 256, 1),   # the 256 x 256 tiles
+    "wgrad-1024x96x40-k3": (_small_wgrad, "f32", 1024, 96, 40, 3),          # two chunks
+}
+
+
+@pytest.mark.parametrize("case", list(SMALL_CASES))
+def test_small_shapes_bits(case):
+    fn, *args = SMALL_CASES[case]
+    fn(*args)
 
 
 # ------------------------------------------------------------------------------------------------------------- model level

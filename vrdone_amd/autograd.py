@@ -1,5 +1,5 @@
 """Differentiable forms of the ops in vrdone_amd.ops: one torch.autograd.Function per kernel family, forward AND
-backward on hand-written HIP kernels (csrc/vrd_backward.hip for the gradients).  The reference gets its gradients from
+backward on hand-written HIP kernels (csrc/vrd_backward.hip, vrd_wgrad.hip and vrd_colsum.hip for the gradients).  The reference gets its gradients from
 autograd over ATen ops (train.py:186, models/maskvrd.py:168-198); this is what makes `loss.backward()` work on the HIP
 path.
 

@@ -7,7 +7,7 @@
 // The kernel is pure HBM streaming: the wide rows (2 x V (+ 2 x Cc) floats per frame) are copied with 16-byte loads and stores,
 // one workgroup per (sequence, GT_FRAMES frames), a wave per frame, the subject's and the object's loads of a frame in flight
 // together; no LDS, no atomics (but the f16 range flag).  Rows that are float4-shaped but not 16-byte aligned are read as
-// four scalar loads (ROWS_UNALIGNED; the ldv4<false> convention of vrd_backward.hip); widths that are no multiple of 4 take the
+// four scalar loads (ROWS_UNALIGNED; the ldv4<false> convention of vrd_colsum.hip); widths that are no multiple of 4 take the
 // scalar form throughout.
 #include "vrd_common.h"
 #include "vrd_box_feats.h"
