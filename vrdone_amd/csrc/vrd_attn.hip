@@ -5,6 +5,7 @@
 //                        HBM-bound: one wavefront per strip of 16 query rows (K / V window rows in a
 //                        register ring) or per query row, covering all heads; window scores in
 //                        registers, head-wise dot products reduced over the 8 or 16 lanes of a head.
+//                        Any odd window from 3 to 19; above 9 local_attn_strip_half_kernel: two waves per strip.
 //  * attn_small_kernel   generic masked attention on the VALU (any Tq/Tk/head_dim <= 128);
 //                        used for the predictor's 9-query decoder.
 //  * attn_flash_kernel   global masked attention (the SOS self/cross attention) on the f32
@@ -210,8 +211,127 @@ __global__ __launch_bounds__(256) void local_attn_strip_kernel(const float* __re
     rt.report(rflag, vrd::RANGE_ATTN_OUT);
 }
 
+// Half-row strip variant for the windows above 9.  The ring of the kernel above costs 16 (W + 1) VGPRs -- 320 at W = 19,
+// more than a wave has -- and its W + 1 unrolled phases of W window slots each outgrow what the compiler will unroll (the
+// ring then lands in scratch).  So here two waves share a strip: wave `half` owns channels [256 half, 256 half + 256),
+// lane l four of them, which halves the registers of a row; and the row loop runs in rounds of U = 4 unrolled phases over
+// W + U slots (phase p: window in slots p .. p + W - 1, the row entering next goes to slot p + W), after which the W live
+// rows move down U slots: W register moves per four query rows.  Heads never straddle the two halves (head_dim 64 or
+// 128), so the waves do not talk to each other; GROUP = head_dim / 4 lanes per head.
+__device__ __forceinline__ float half_group_sum16(float d) { return vrd::group_sum<16>(d); }
+__device__ __forceinline__ float half_group_sum32(float d) {
+    d = vrd::group_sum<16>(d);
+    return d + __shfl_xor(d, 16, 64);
+}
+
+template <int W, int GROUP, int RW, bool REL>
+__global__ __launch_bounds__(256) void local_attn_strip_half_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                    const float* __restrict__ v, int64_t ld,
+                                                                    const uint8_t* __restrict__ mask, const float* __restrict__ rel,
+                                                                    int B, int T_u, int strips_per_seq,
+                                                                    float scale, float* __restrict__ out, int64_t ldo, int pair,
+                                                                    unsigned* rflag, vrd::SegTable sg) {
+    static_assert(GROUP == 16 || GROUP == 32, "lanes per head at four channels a lane");
+    static_assert(RW + 2 * (W / 2) <= 64, "one validity bit per row of the strip and its halo");
+    constexpr int HW = W / 2, U = 2;
+    static_assert(RW % U == 0, "whole rounds");
+    vrd::RangeTrack rt;
+    const int lane = threadIdx.x & 63;
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, qq = nwg >> 3, rem = nwg & 7;
+    const int lid = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + (bid >> 3);
+    const int64_t wv = (int64_t)lid * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t ws = wv >> 1;                       // strip; the two waves of a strip sit in one workgroup
+    const int half = (int)(wv & 1);
+    const int c0 = half * 256 + lane * 4;             // first channel of this lane
+    int T, t0;
+    int64_t row_b;
+    if (sg.count) {
+        int g, b, strip;
+        if (!vrd::seg_find(sg, ws, g, b, strip)) return;
+        T = sg.T[g], t0 = strip * RW, row_b = sg.row[g] + (int64_t)b * T;
+    } else {
+        const int b = (int)(ws / strips_per_seq);
+        if (b >= B) return;
+        T = T_u, t0 = (int)(ws - (int64_t)b * strips_per_seq) * RW, row_b = (int64_t)b * T;
+    }
+    const int t1 = min(t0 + RW, T);
+    // validity of rows t0 - HW .. t0 + RW + HW - 1 as one bit each (bit i = row t0 - HW + i; outside [0, T) = 0)
+    const int tm = t0 - HW + lane;
+    const unsigned long long live = __ballot(lane < RW + 2 * HW && tm >= 0 && tm < T && mask[row_b + (tm >= 0 && tm < T ? tm : 0)] != 0);
+    if (((live >> HW) & ((1ull << (t1 - t0)) - 1ull)) == 0ull) {      // every query row of the strip is padding
+        for (int t = t0; t < t1; ++t) st4(out + (row_b + t) * ldo + c0, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
+    auto load_row = [&](const float* base, int t) {
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t >= 0 && t < T) r = ld4(base + (row_b + t) * ld + c0);
+        return r;
+    };
+    float rb[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) rb[j] = REL ? rel[((half * 64 + lane) / GROUP) * W + j] : 0.f;
+    float4 kr[W + U], vr[W + U];
+#pragma unroll
+    for (int i = 0; i < W; ++i) {          // window of the first query row: rows t0 - HW .. t0 + HW in slots 0 .. W-1
+        kr[i] = load_row(k, t0 - HW + i);
+        vr[i] = load_row(v, t0 - HW + i);
+    }
+    for (int base = 0; t0 + base < t1; base += U) {
+        if (base) {
+#pragma unroll
+            for (int i = 0; i < W; ++i) kr[i] = kr[i + U], vr[i] = vr[i + U];
+        }
+#pragma unroll
+        for (int ph = 0; ph < U; ++ph) {
+            const int t = t0 + base + ph;
+            if (t >= t1) break;
+            kr[ph + W] = load_row(k, t + HW + 1);
+            vr[ph + W] = load_row(v, t + HW + 1);
+            float* o = out + (row_b + t) * ldo + c0;
+            const int bit0 = base + ph;                       // bit of window row j is bit0 + j (row t - HW + j)
+            if (!((live >> (bit0 + HW)) & 1ull)) {            // masked query rows are zeroed after the softmax
+                st4(o, make_float4(0.f, 0.f, 0.f, 0.f));
+                continue;
+            }
+            float4 q0 = ld4(q + (row_b + t) * ld + c0);
+            q0.x *= scale; q0.y *= scale; q0.z *= scale; q0.w *= scale;
+            float sc[W];
+            float m = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const int tj = t + j - HW;
+                if (tj < 0 || tj >= T) { sc[j] = -INFINITY; continue; }
+                float d = dot4(q0, kr[ph + j]);
+                d = GROUP == 32 ? half_group_sum32(d) : half_group_sum16(d);
+                if (REL) d += rb[j];
+                sc[j] = d + (((live >> (bit0 + j)) & 1ull) ? 0.f : -1e4f);
+                m = fmaxf(m, sc[j]);
+            }
+            float den = 0.f;
+#pragma unroll
+            for (int j = 0; j < W; ++j) { sc[j] = __expf(sc[j] - m); den += sc[j]; }
+            const float inv = 1.0f / den;
+            float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const int tj = t + j - HW;
+                if (tj < 0 || tj >= T) continue;
+                const float4 vv = vr[ph + j];
+                const float pj = sc[j] * inv;
+                a0.x += pj * vv.x; a0.y += pj * vv.y; a0.z += pj * vv.z; a0.w += pj * vv.w;
+            }
+            if (pair)
+                vrd::store_pair4(out + (row_b + t) * ldo, c0, 512, a0, pair, &rt);
+            else
+                st4(o, a0);
+        }
+    }
+    rt.report(rflag, vrd::RANGE_ATTN_OUT);
+}
+
 // ------------------------------------------------------------------------------------------
-// generic masked attention on the VALU.  One workgroup per (b, head); each wave walks queries.
+// generic masked attention on the VALU. One workgroup per (b, head); each wave walks queries.
 // ------------------------------------------------------------------------------------------
 constexpr int SM_MAX_TK = 2048, SM_MAX_HD = 128;
 
@@ -528,7 +648,7 @@ static int local_attn_launch(const float* q, const float* k, const float* v, int
     VRD_CHECK_ARG(q && k && v && mask && out, "vrd_local_attn: null pointer");
     VRD_CHECK_ARG(C == 512, "vrd_local_attn: built for C = 512 (got %d)", C);
     VRD_CHECK_ARG(n_head == 4 || n_head == 8, "vrd_local_attn: n_head must be 4 or 8 (got %d)", n_head);
-    VRD_CHECK_ARG(half_win == 3 || half_win == 4, "vrd_local_attn: window must be 7 or 9 (half %d)", half_win);
+    VRD_CHECK_ARG(half_win >= 1 && half_win <= 9, "vrd_local_attn: window must be odd, 3..19 (got %d)", 2 * half_win + 1);
     VRD_CHECK_ARG(ld >= C && ldo >= C && ld % 4 == 0 && ldo % 4 == 0 && aligned16(q) && aligned16(k) &&
                       aligned16(v) && aligned16(out), "vrd_local_attn: bad layout");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -561,10 +681,26 @@ static int local_attn_launch(const float* q, const float* k, const float* v, int
             hipLaunchKernelGGL((local_attn_strip_kernel<Wn, G, RW, false>), grid, block, 0, s, q, k, v, ld, mask, rel_pe,  \
                                B, T, strips, scale, out, ldo, out_pair, rflag, sg);                                              \
     } while (0)
-        if (half_win == 3 && n_head == 4) VRD_LS(7, 16);
-        else if (half_win == 3) VRD_LS(7, 8);
-        else if (n_head == 4) VRD_LS(9, 16);
-        else VRD_LS(9, 8);
+        // windows up to 9: one wave per strip, whole rows in the ring; above: two waves per strip, half a row each
+#define VRD_LH(Wn, G)                                                                                                     \
+    do {                                                                                                                  \
+        grid.x = (unsigned)((2 * (segs ? seg_strips : (int64_t)B * strips) + 3) / 4);                                     \
+        if (rel_pe)                                                                                                       \
+            hipLaunchKernelGGL((local_attn_strip_half_kernel<Wn, G, RW, true>), grid, block, 0, s, q, k, v, ld, mask,     \
+                               rel_pe, B, T, strips, scale, out, ldo, out_pair, rflag, sg);                               \
+        else                                                                                                              \
+            hipLaunchKernelGGL((local_attn_strip_half_kernel<Wn, G, RW, false>), grid, block, 0, s, q, k, v, ld, mask,    \
+                               rel_pe, B, T, strips, scale, out, ldo, out_pair, rflag, sg);                               \
+    } while (0)
+#define VRD_LS_W(Wn) case Wn: if (n_head == 4) VRD_LS(Wn, 16); else VRD_LS(Wn, 8); break
+#define VRD_LH_W(Wn) case Wn: if (n_head == 4) VRD_LH(Wn, 32); else VRD_LH(Wn, 16); break
+        switch (W) {
+            VRD_LS_W(3); VRD_LS_W(5); VRD_LS_W(7); VRD_LS_W(9);
+            VRD_LH_W(11); VRD_LH_W(13); VRD_LH_W(15); VRD_LH_W(17); VRD_LH_W(19);
+        }
+#undef VRD_LS_W
+#undef VRD_LH_W
+#undef VRD_LH
 #undef VRD_LS
         VRD_LAUNCH_CHECK();
         return 0;
@@ -579,10 +715,12 @@ static int local_attn_launch(const float* q, const float* k, const float* v, int
             hipLaunchKernelGGL((local_attn_kernel<Wn, G, false>), grid, block, 0, s, q, k, v, ld, mask, rel_pe, B, T,     \
                                scale, out, ldo, out_pair, rflag);                                                                \
     } while (0)
-    if (half_win == 3 && n_head == 4) VRD_LA(7, 16);
-    else if (half_win == 3) VRD_LA(7, 8);
-    else if (n_head == 4) VRD_LA(9, 16);
-    else VRD_LA(9, 8);
+#define VRD_LA_W(Wn) case Wn: if (n_head == 4) VRD_LA(Wn, 16); else VRD_LA(Wn, 8); break
+    switch (W) {
+        VRD_LA_W(3); VRD_LA_W(5); VRD_LA_W(7); VRD_LA_W(9); VRD_LA_W(11);
+        VRD_LA_W(13); VRD_LA_W(15); VRD_LA_W(17); VRD_LA_W(19);
+    }
+#undef VRD_LA_W
 #undef VRD_LA
     VRD_LAUNCH_CHECK();
     return 0;

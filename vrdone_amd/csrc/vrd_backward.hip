@@ -314,15 +314,18 @@ __device__ __forceinline__ float head_sum(float d) { return vrd::group_sum<GROUP
 __device__ __forceinline__ float dot8(const float4& a0, const float4& a1, const float4& b0, const float4& b1) {
     return (a0.x * b0.x + a0.y * b0.y + a0.z * b0.z + a0.w * b0.w) + (a1.x * b1.x + a1.y * b1.y + a1.z * b1.z + a1.w * b1.w);
 }
-constexpr int LA_WMAX = 9;
-template <int GROUP>
+// WT: the window as a compile-time constant (11 .. 19: the loops unroll and s[] / dp[] stay in registers), or 0 for the
+// run-time windows up to LA_WRT, whose nine-entry arrays the compiler already keeps in registers
+constexpr int LA_WRT = 9, LA_WMAX = 19;
+template <int GROUP, int WT>
 __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                const float* __restrict__ v, int64_t ld,
                                                                const float* __restrict__ dO, int64_t lddo,
                                                                const uint8_t* __restrict__ mask, const float* __restrict__ rel,
-                                                               int B, int T, int W, float scale,
+                                                               int B, int T, int W_rt, float scale,
                                                                float* __restrict__ dq, int64_t lddq, float* __restrict__ P,
                                                                float* __restrict__ dS) {
+    const int W = WT ? WT : W_rt;
     const int HW = W / 2;
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -342,7 +345,7 @@ __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __re
     }
     const float4 q0 = ld4(q + row * ld + lane * 8), q1 = ld4(q + row * ld + lane * 8 + 4);
     const float4 o0 = ld4(dO + row * lddo + lane * 8), o1 = ld4(dO + row * lddo + lane * 8 + 4);
-    float s[LA_WMAX], dp[LA_WMAX];
+    float s[WT ? WT : LA_WRT], dp[WT ? WT : LA_WRT];
     float m = -INFINITY;
     for (int j = 0; j < W; ++j) {
         const int tj = t + j - HW;
@@ -803,7 +806,7 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
     VRD_CHECK_ARG(q && k && v && dO && mask && dq && dk && dv && scratch, "vrd_local_attn_bwd: null pointer");
     VRD_CHECK_ARG(C == 512 && (n_head == 4 || n_head == 8), "vrd_local_attn_bwd: built for C = 512 with 4 or 8 heads");
     const int W = 2 * half_win + 1;
-    VRD_CHECK_ARG(half_win >= 1 && W <= LA_WMAX, "vrd_local_attn_bwd: window %d not supported (max %d)", W, LA_WMAX);
+    VRD_CHECK_ARG(half_win >= 1 && W <= LA_WMAX, "vrd_local_attn_bwd: window must be odd, 3..%d (got %d)", LA_WMAX, W);
     VRD_CHECK_ARG(ld % 4 == 0 && lddo % 4 == 0 && ldd % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(dO) &&
                       aligned16(dq) && aligned16(dk) && aligned16(dv),
                   "vrd_local_attn_bwd: rows must be 16-byte aligned");
@@ -814,13 +817,19 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
     float* dS = scratch + rows * n_head * W;
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * 8);
     dim3 grid((unsigned)((rows + 3) / 4));
-    if (n_head == 4) {
-        hipLaunchKernelGGL(local_attn_bwd_q_kernel<16>, grid, dim3(256), 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, scale, dq, ldd, P, dS);
-        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<16>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
-    } else {
-        hipLaunchKernelGGL(local_attn_bwd_q_kernel<8>, grid, dim3(256), 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, scale, dq, ldd, P, dS);
-        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<8>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
+#define VRD_LB(G, WT)                                                                                                     \
+    hipLaunchKernelGGL((local_attn_bwd_q_kernel<G, WT>), grid, dim3(256), 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, \
+                       scale, dq, ldd, P, dS)
+#define VRD_LB_W(WT) case WT: if (n_head == 4) VRD_LB(16, WT); else VRD_LB(8, WT); break
+    switch (W <= LA_WRT ? 0 : W) {
+        VRD_LB_W(0); VRD_LB_W(11); VRD_LB_W(13); VRD_LB_W(15); VRD_LB_W(17); VRD_LB_W(19);
     }
+#undef VRD_LB_W
+#undef VRD_LB
+    if (n_head == 4)
+        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<16>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
+    else
+        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<8>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
     VRD_LAUNCH_CHECK();
     return 0;
 }

@@ -1022,7 +1022,11 @@ def _rel_pe_ptr(rel_pe, like, n_head, half_win):
 def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, out=None, segs=None):
     """rel_pe: None or the module's (1, 1, n_head, window) relative position bias (reference blocks.py:739-743).
     out: (B, T, C) contiguous rows to write instead of a fresh tensor (inference path).
-    segs (inference path): q / k / v / mask are a ragged row space (1, R, ...): [(first row, sequences, frames)] (vrd_row_segs)."""
+    segs (inference path): q / k / v / mask are a ragged row space (1, R, ...): [(first row, sequences, frames)] (vrd_row_segs).
+    half_win: window // 2 of an odd window from 3 to 19."""
+    if not (isinstance(half_win, int) and 1 <= half_win <= 9):
+        raise ValueError(f"local_attention: the window must be odd, from 3 to 19 (half_win = window // 2 an integer from 1 to 9), "
+                         f"got half_win {half_win!r}")
     if recording(q, k, v, rel_pe):
         from . import autograd
         return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe)
