@@ -407,7 +407,9 @@ int vrd_dwconv_ln(const vrd_dwconv_ln_args* a, void* stream);
 
 /* ---- banded (local-window) attention, models/blocks.py:950-986 ---------------------------
  * query t attends keys j in [t-half_win, t+half_win] within [0,T); masked keys get -1e4,
- * masked query rows give 0.  q is scaled by head_dim^-0.5 inside.  C = n_head*head_dim = 512.
+ * masked query rows give 0.  q is scaled by head_dim^-0.5 inside.  C = n_head*head_dim is 256 or
+ * 512 and head_dim = C / n_head is 32, 64 or 128 (16, 8 or 4 heads at 512; 8, 4 or 2 at 256);
+ * anything else is refused with an error text that names this set and the values it got.
  * Any odd window from 3 to 19 (half_win 1 .. 9), forward and backward (vrd_local_attn_bwd).
  * rel_pe: NULL, or the relative position bias [n_head][2*half_win+1] added to the scaled scores
  * before the key mask (`use_rel_pe`, models/blocks.py:739-743,957-958). */

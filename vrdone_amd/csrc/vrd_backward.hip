@@ -303,7 +303,9 @@ __global__ __launch_bounds__(256) void dwconv_bwd_kernel(DwBwdArgs p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// banded attention backward (C = 512; lane l owns channels [8l, 8l+8); GROUP = head_dim / 8 lanes per head).
+// banded attention backward.  C = 512: lane l owns channels [8l, 8l+8), GROUP = head_dim / 8 lanes per head (4, 8, 16);
+// C = 256 (CPL = 4): lane l owns channels [4l, 4l+4), GROUP = head_dim / 4 (8, 16, 32), the second float4 of every row
+// dropped at compile time.  Either way 64 / GROUP heads, and the scratch is rows x heads x W.
 // Pass 1, one wave per query row t: recompute the window probabilities P[t, j] (models/blocks.py:950-986: masked keys
 // -1e4, out-of-range -inf, masked query rows all zero), dP = dO . v, dS = P * (dP - sum_j P dP); dq = scale * sum_j dS k;
 // P and dS of the row go to scratch (rows x heads x W).  Pass 2, one wave per key row j: dk_j = scale * sum_t dS[t, j] q_t,
@@ -314,10 +316,26 @@ __device__ __forceinline__ float head_sum(float d) { return vrd::group_sum<GROUP
 __device__ __forceinline__ float dot8(const float4& a0, const float4& a1, const float4& b0, const float4& b1) {
     return (a0.x * b0.x + a0.y * b0.y + a0.z * b0.z + a0.w * b0.w) + (a1.x * b1.x + a1.y * b1.y + a1.z * b1.z + a1.w * b1.w);
 }
+__device__ __forceinline__ float la_dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+// a lane's CPL channels of a row: .a alone at CPL = 4
+struct LaRow {
+    float4 a, b;
+};
+template <int CPL>
+__device__ __forceinline__ LaRow la_load(const float* p) {
+    LaRow r;
+    r.a = ld4(p);
+    r.b = CPL == 8 ? ld4(p + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    return r;
+}
+template <int CPL>
+__device__ __forceinline__ float la_dot(const LaRow& x, const LaRow& y) {
+    return CPL == 8 ? dot8(x.a, x.b, y.a, y.b) : la_dot4(x.a, y.a);
+}
 // WT: the window as a compile-time constant (11 .. 19: the loops unroll and s[] / dp[] stay in registers), or 0 for the
 // run-time windows up to LA_WRT, whose nine-entry arrays the compiler already keeps in registers
 constexpr int LA_WRT = 9, LA_WMAX = 19;
-template <int GROUP, int WT>
+template <int GROUP, int WT, int CPL = 8>
 __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                const float* __restrict__ v, int64_t ld,
                                                                const float* __restrict__ dO, int64_t lddo,
@@ -339,12 +357,11 @@ __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __re
     if (!mask[row]) {
         if (lane % GROUP == 0)
             for (int j = 0; j < W; ++j) Pr[j] = 0.f, dSr[j] = 0.f;
-        st4(dq + row * lddq + lane * 8, g0);
-        st4(dq + row * lddq + lane * 8 + 4, g0);
+        st4(dq + row * lddq + lane * CPL, g0);
+        if (CPL == 8) st4(dq + row * lddq + lane * CPL + 4, g0);
         return;
     }
-    const float4 q0 = ld4(q + row * ld + lane * 8), q1 = ld4(q + row * ld + lane * 8 + 4);
-    const float4 o0 = ld4(dO + row * lddo + lane * 8), o1 = ld4(dO + row * lddo + lane * 8 + 4);
+    const LaRow qv = la_load<CPL>(q + row * ld + lane * CPL), ov = la_load<CPL>(dO + row * lddo + lane * CPL);
     float s[WT ? WT : LA_WRT], dp[WT ? WT : LA_WRT];
     float m = -INFINITY;
     for (int j = 0; j < W; ++j) {
@@ -352,10 +369,10 @@ __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __re
         s[j] = -INFINITY;
         dp[j] = 0.f;
         if (tj < 0 || tj >= T) continue;
-        const float* kr = k + (row + j - HW) * ld + lane * 8;
-        const float* vr = v + (row + j - HW) * ld + lane * 8;
-        const float d = head_sum<GROUP>(dot8(q0, q1, ld4(kr), ld4(kr + 4))) * scale;
-        dp[j] = head_sum<GROUP>(dot8(o0, o1, ld4(vr), ld4(vr + 4)));
+        const float* kr = k + (row + j - HW) * ld + lane * CPL;
+        const float* vr = v + (row + j - HW) * ld + lane * CPL;
+        const float d = head_sum<GROUP>(la_dot<CPL>(qv, la_load<CPL>(kr))) * scale;
+        dp[j] = head_sum<GROUP>(la_dot<CPL>(ov, la_load<CPL>(vr)));
         s[j] = (rel ? d + rel[head * W + j] : d) + (mask[row + j - HW] ? 0.f : -1e4f);
         m = fmaxf(m, s[j]);
     }
@@ -369,16 +386,19 @@ __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __re
         if (lane % GROUP == 0) Pr[j] = s[j], dSr[j] = ds;
         const int tj = t + j - HW;
         if (tj < 0 || tj >= T) continue;
-        const float* kr = k + (row + j - HW) * ld + lane * 8;
-        const float4 k0 = ld4(kr), k1 = ld4(kr + 4);
+        const float* kr = k + (row + j - HW) * ld + lane * CPL;
+        const float4 k0 = ld4(kr);
         const float f = ds * scale;
         g0.x = fmaf(f, k0.x, g0.x); g0.y = fmaf(f, k0.y, g0.y); g0.z = fmaf(f, k0.z, g0.z); g0.w = fmaf(f, k0.w, g0.w);
-        g1.x = fmaf(f, k1.x, g1.x); g1.y = fmaf(f, k1.y, g1.y); g1.z = fmaf(f, k1.z, g1.z); g1.w = fmaf(f, k1.w, g1.w);
+        if (CPL == 8) {
+            const float4 k1 = ld4(kr + 4);
+            g1.x = fmaf(f, k1.x, g1.x); g1.y = fmaf(f, k1.y, g1.y); g1.z = fmaf(f, k1.z, g1.z); g1.w = fmaf(f, k1.w, g1.w);
+        }
     }
-    st4(dq + row * lddq + lane * 8, g0);
-    st4(dq + row * lddq + lane * 8 + 4, g1);
+    st4(dq + row * lddq + lane * CPL, g0);
+    if (CPL == 8) st4(dq + row * lddq + lane * CPL + 4, g1);
 }
-template <int GROUP>
+template <int GROUP, int CPL = 8>
 __global__ __launch_bounds__(256) void local_attn_bwd_kv_kernel(const float* __restrict__ q, int64_t ld,
                                                                 const float* __restrict__ dO, int64_t lddo, int B, int T, int W,
                                                                 float scale, const float* __restrict__ P,
@@ -397,17 +417,19 @@ __global__ __launch_bounds__(256) void local_attn_bwd_kv_kernel(const float* __r
         if (t < 0 || t >= T) continue;
         const int64_t qr = row + HW - i;
         const float p = P[(qr * H + head) * W + i], ds = dS[(qr * H + head) * W + i] * scale;
-        const float4 q0 = ld4(q + qr * ld + lane * 8), q1 = ld4(q + qr * ld + lane * 8 + 4);
-        const float4 o0 = ld4(dO + qr * lddo + lane * 8), o1 = ld4(dO + qr * lddo + lane * 8 + 4);
+        const float4 q0 = ld4(q + qr * ld + lane * CPL), o0 = ld4(dO + qr * lddo + lane * CPL);
         a0.x = fmaf(ds, q0.x, a0.x); a0.y = fmaf(ds, q0.y, a0.y); a0.z = fmaf(ds, q0.z, a0.z); a0.w = fmaf(ds, q0.w, a0.w);
-        a1.x = fmaf(ds, q1.x, a1.x); a1.y = fmaf(ds, q1.y, a1.y); a1.z = fmaf(ds, q1.z, a1.z); a1.w = fmaf(ds, q1.w, a1.w);
         c0.x = fmaf(p, o0.x, c0.x); c0.y = fmaf(p, o0.y, c0.y); c0.z = fmaf(p, o0.z, c0.z); c0.w = fmaf(p, o0.w, c0.w);
-        c1.x = fmaf(p, o1.x, c1.x); c1.y = fmaf(p, o1.y, c1.y); c1.z = fmaf(p, o1.z, c1.z); c1.w = fmaf(p, o1.w, c1.w);
+        if (CPL == 8) {
+            const float4 q1 = ld4(q + qr * ld + lane * CPL + 4), o1 = ld4(dO + qr * lddo + lane * CPL + 4);
+            a1.x = fmaf(ds, q1.x, a1.x); a1.y = fmaf(ds, q1.y, a1.y); a1.z = fmaf(ds, q1.z, a1.z); a1.w = fmaf(ds, q1.w, a1.w);
+            c1.x = fmaf(p, o1.x, c1.x); c1.y = fmaf(p, o1.y, c1.y); c1.z = fmaf(p, o1.z, c1.z); c1.w = fmaf(p, o1.w, c1.w);
+        }
     }
-    st4(dk + row * lddkv + lane * 8, a0);
-    st4(dk + row * lddkv + lane * 8 + 4, a1);
-    st4(dv + row * lddkv + lane * 8, c0);
-    st4(dv + row * lddkv + lane * 8 + 4, c1);
+    st4(dk + row * lddkv + lane * CPL, a0);
+    if (CPL == 8) st4(dk + row * lddkv + lane * CPL + 4, a1);
+    st4(dv + row * lddkv + lane * CPL, c0);
+    if (CPL == 8) st4(dv + row * lddkv + lane * CPL + 4, c1);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -804,7 +826,10 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
                        const uint8_t* mask, const float* rel_pe, int B, int T, int C, int n_head, int half_win,
                        float* dq, float* dk, float* dv, int64_t ldd, float* scratch, void* stream) {
     VRD_CHECK_ARG(q && k && v && dO && mask && dq && dk && dv && scratch, "vrd_local_attn_bwd: null pointer");
-    VRD_CHECK_ARG(C == 512 && (n_head == 4 || n_head == 8), "vrd_local_attn_bwd: built for C = 512 with 4 or 8 heads");
+    VRD_CHECK_ARG((C == 256 || C == 512) && n_head > 0 && C % n_head == 0 &&
+                      (C / n_head == 32 || C / n_head == 64 || C / n_head == 128),
+                  "vrd_local_attn_bwd: built for C = 256 or 512 with head_dim = C / n_head of 32, 64 or 128 (got C = %d, n_head = %d)", C,
+                  n_head);
     const int W = 2 * half_win + 1;
     VRD_CHECK_ARG(half_win >= 1 && W <= LA_WMAX, "vrd_local_attn_bwd: window must be odd, 3..%d (got %d)", LA_WMAX, W);
     VRD_CHECK_ARG(ld % 4 == 0 && lddo % 4 == 0 && ldd % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(dO) &&
@@ -817,19 +842,25 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
     float* dS = scratch + rows * n_head * W;
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * 8);
     dim3 grid((unsigned)((rows + 3) / 4));
-#define VRD_LB(G, WT)                                                                                                     \
-    hipLaunchKernelGGL((local_attn_bwd_q_kernel<G, WT>), grid, dim3(256), 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, \
+    const int hd = C / n_head;
+#define VRD_LB(G, WT, CPL)                                                                                                \
+    hipLaunchKernelGGL((local_attn_bwd_q_kernel<G, WT, CPL>), grid, dim3(256), 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, \
                        scale, dq, ldd, P, dS)
-#define VRD_LB_W(WT) case WT: if (n_head == 4) VRD_LB(16, WT); else VRD_LB(8, WT); break
+#define VRD_LB_W(WT)                                                                                                      \
+    case WT:                                                                                                              \
+        if (C == 512) { if (hd == 128) VRD_LB(16, WT, 8); else if (hd == 64) VRD_LB(8, WT, 8); else VRD_LB(4, WT, 8); }   \
+        else { if (hd == 128) VRD_LB(32, WT, 4); else if (hd == 64) VRD_LB(16, WT, 4); else VRD_LB(8, WT, 4); }           \
+        break
     switch (W <= LA_WRT ? 0 : W) {
         VRD_LB_W(0); VRD_LB_W(11); VRD_LB_W(13); VRD_LB_W(15); VRD_LB_W(17); VRD_LB_W(19);
     }
 #undef VRD_LB_W
 #undef VRD_LB
-    if (n_head == 4)
-        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<16>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
-    else
-        hipLaunchKernelGGL(local_attn_bwd_kv_kernel<8>, grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd);
+#define VRD_LK(G, CPL)                                                                                                    \
+    hipLaunchKernelGGL((local_attn_bwd_kv_kernel<G, CPL>), grid, dim3(256), 0, s, q, ld, dO, lddo, B, T, W, scale, P, dS, dk, dv, ldd)
+    if (C == 512) { if (hd == 128) VRD_LK(16, 8); else if (hd == 64) VRD_LK(8, 8); else VRD_LK(4, 8); }
+    else { if (hd == 128) VRD_LK(32, 4); else if (hd == 64) VRD_LK(16, 4); else VRD_LK(8, 4); }
+#undef VRD_LK
     VRD_LAUNCH_CHECK();
     return 0;
 }

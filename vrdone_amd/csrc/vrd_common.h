@@ -131,23 +131,27 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-// Sum over aligned groups of G = 8 or 16 lanes, every lane of a group receiving the group's sum: the first steps of wave_sum
-// (three or four v_add_f32 with a DPP operand).  __shfl_xor compiles to ds_bpermute_b32 plus its address arithmetic, seven
-// instructions and an LDS round trip per step; the banded attention spends 28 of those per query row on its dot products.
+// Sum over aligned groups of G = 4, 8, 16 or 32 lanes, every lane of a group receiving the group's sum: the first steps of
+// wave_sum (two to four v_add_f32 with a DPP operand).  __shfl_xor compiles to ds_bpermute_b32 plus its address arithmetic,
+// seven instructions and an LDS round trip per step; the banded attention spends 28 of those per query row on its dot
+// products.  G = 32 spans two DPP rows, which no DPP control exchanges both ways: that one step is a __shfl_xor.
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
-    static_assert(G == 8 || G == 16, "lanes per group");
+    static_assert(G == 4 || G == 8 || G == 16 || G == 32, "lanes per group");
     float t;
     t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]
     v += t;
     t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));      // quad_perm [2,3,0,1]
     v += t;
-    t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));     // row_half_mirror
-    v += t;
-    if (G == 16) {
+    if (G >= 8) {
+        t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)); // row_half_mirror
+        v += t;
+    }
+    if (G >= 16) {
         t = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)); // row_mirror
         v += t;
     }
+    if (G == 32) v += __shfl_xor(v, 16, 64);
     return v;
 }
 

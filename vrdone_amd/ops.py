@@ -1027,6 +1027,10 @@ def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, ou
     if not (isinstance(half_win, int) and 1 <= half_win <= 9):
         raise ValueError(f"local_attention: the window must be odd, from 3 to 19 (half_win = window // 2 an integer from 1 to 9), "
                          f"got half_win {half_win!r}")
+    width = q.shape[-1]
+    if not (width in (256, 512) and isinstance(n_head, int) and n_head > 0 and width % n_head == 0 and width // n_head in (32, 64, 128)):
+        raise ValueError(f"local_attention: built for width 256 or 512 with head_dim = width / n_head of 32, 64 or 128 "
+                         f"(16, 8 or 4 heads at 512; 8, 4 or 2 at 256), got width {width}, n_head {n_head!r}")
     if recording(q, k, v, rel_pe):
         from . import autograd
         return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe)
