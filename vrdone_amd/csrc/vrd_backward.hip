@@ -832,6 +832,7 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
                   n_head);
     const int W = 2 * half_win + 1;
     VRD_CHECK_ARG(half_win >= 1 && W <= LA_WMAX, "vrd_local_attn_bwd: window must be odd, 3..%d (got %d)", LA_WMAX, W);
+    VRD_CHECK_ARG(ld >= C && lddo >= C && ldd >= C, "vrd_local_attn_bwd: leading dimension too small");
     VRD_CHECK_ARG(ld % 4 == 0 && lddo % 4 == 0 && ldd % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(dO) &&
                       aligned16(dq) && aligned16(dk) && aligned16(dv),
                   "vrd_local_attn_bwd: rows must be 16-byte aligned");
@@ -871,6 +872,8 @@ int vrd_attn_bwd_probs(const float* q, int64_t ldq, const float* k, const float*
     VRD_CHECK_ARG(B > 0 && Tq > 0 && Tk > 0 && Tk <= AB_TK_MAX && n_head > 0 && head_dim > 0 && head_dim <= AB_HD_MAX && head_dim % 4 == 0,
                   "vrd_attn_bwd_probs: Tk <= %d, head_dim <= %d and %% 4 == 0 (got Tk %d, head_dim %d)", AB_TK_MAX, AB_HD_MAX, Tk, head_dim);
     VRD_CHECK_ARG(ldkv % 4 == 0 && aligned16(k) && aligned16(v), "vrd_attn_bwd_probs: k / v rows must be 16-byte aligned");
+    VRD_CHECK_ARG(ldq >= (int64_t)n_head * head_dim && ldkv >= (int64_t)n_head * head_dim && lddo >= (int64_t)n_head * head_dim,
+                  "vrd_attn_bwd_probs: leading dimension too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n = (int64_t)B * n_head * Tq;
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 4.0 * (double)n * Tk * head_dim, 8.0 * (double)n * Tk);

@@ -885,7 +885,7 @@ int vrd_dwconv_ln(const vrd_dwconv_ln_args* a, void* stream) {
     VRD_CHECK_ARG((a->pre_gamma == nullptr) == (a->pre_beta == nullptr) && (!a->pre_gamma || (a->group_in == 1 && !a->x_up)),
                   "vrd_dwconv_ln: input LayerNorm needs gamma and beta, group_in == 1 and no x_up");
     VRD_CHECK_ARG(a->ldx >= (int64_t)a->C * a->group_in && a->ldx % 4 == 0 && aligned16(a->x), "vrd_dwconv_ln: bad x layout");
-    VRD_CHECK_ARG(!a->x_up || (a->Tin % 2 == 0 && a->ldx_up % 4 == 0 && aligned16(a->x_up)), "vrd_dwconv_ln: bad x_up layout");
+    VRD_CHECK_ARG(!a->x_up || (a->Tin % 2 == 0 && a->ldx_up >= (int64_t)a->C * a->group_in && a->ldx_up % 4 == 0 && aligned16(a->x_up)), "vrd_dwconv_ln: bad x_up layout");
     for (int o = 0; o < a->n_out; ++o) {
         VRD_CHECK_ARG((a->w[o] || a->packed[o]) && a->y[o] && aligned16(a->w[o]) && aligned16(a->packed[o]) && aligned16(a->y[o]) &&
                           a->ldy[o] % 4 == 0 && a->ldy[o] >= a->C,
