@@ -1048,6 +1048,106 @@ def test_extension_is_loaded_and_profiled():
     assert prof["local_attn"]["launches"] == 5
 
 
+def _prefix_masks(lens, T):
+    return (torch.arange(T)[None, :] < torch.tensor(lens)[:, None])[:, None, :]
+
+
+def launch_cases():
+    """{name: run() -> outputs}: the smallest calls that reach every operation of the network that needs the (sequences, frames)
+    structure, in the batch form, in the row space (global and banded subject-object attention, forward_test with the shared
+    tracklet rows) and as one training step."""
+    from oracle.synth import synth_relations
+    from vrdone_amd import synth
+    from vrdone_amd.proposals import prepare_test_proposal
+
+    def mask_vrd(name, T, lens, min_rows, want_plan, **kw):
+        model, mc, _, _ = get_model(name)
+        x, m = O.synth_pairs(len(lens), c_in(mc), T, lens, seed=41)
+        xd, md = x.to(DEV), m.to(DEV)
+
+        def run():
+            try:
+                if min_rows:
+                    model.ROWS_MIN_ROWS = min_rows
+                plan = model._tight_plan(md, md.reshape(len(lens), T))
+                assert (plan and [(t, n, flat) for t, _, n, flat in plan["buckets"]]) == want_plan, plan
+                assert plan is None or plan["rows"]
+                return model._mask_vrd(xd, md, **kw)
+            finally:
+                model.__dict__.pop("ROWS_MIN_ROWS", None)
+        return run
+
+    def forward_test():
+        model, mc, ic, _ = get_model("vidvrd")
+        raw = synth.synth_raw_video(8, mc["visual_dim"], 60, 250, seed=11)
+        prop = prepare_test_proposal(raw, ic["feat_stride"], 0, 2, torch.device(DEV))
+        try:
+            model.ROWS_MIN_PAIRS = 8
+            assert model._eval_rows_form(len(prop["pair_source"])) and model.share_tracklets
+            return model(prop)
+        finally:
+            del model.ROWS_MIN_PAIRS
+
+    def train_step():
+        model, mc, _, _ = get_model("vidvrd")
+        lens = [96, 60, 17, 41]
+        x, _ = O.synth_pairs(len(lens), c_in(mc), 96, lens, seed=43)
+        gp, gm, gs = synth_relations(lens, 96, mc["num_classes"], max_rel=4, seed=44)
+        data = {"so_features_list": [x[i, :, :n].contiguous() for i, n in enumerate(lens)], "preds_list": gp, "masks_list": gm,
+                "segs_list": gs}
+        model.train()
+        try:
+            with torch.enable_grad():
+                model.zero_grad(set_to_none=True)
+                torch.manual_seed(45)
+                losses = model(data)
+                losses["total_loss"].backward()
+            return ({k: v.detach().clone() for k, v in losses.items()}, {n: p.grad.clone() for n, p in model.named_parameters()})
+        finally:
+            model.zero_grad(set_to_none=True)
+            model.eval()
+
+    return {
+        "batch": mask_vrd("vidvrd", 96, [96] * 4, None, None, with_aux=False),
+        "rows_global": mask_vrd("vidvrd", 96, [5, 17, 24, 24, 25, 40, 56, 33, 57, 94, 95, 96], 64,
+                                [(32, 4, True), (64, 4, True), (96, 2, True), (96, 2, False)]),
+        "rows_banded": mask_vrd("vidor_local", 512, [5, 24, 25, 56, 57, 120, 121, 400, 510, 511, 512, 300], 64,
+                                [(32, 2, True), (64, 2, True), (96, 1, True), (128, 1, True), (160, 1, True), (320, 1, True),
+                                 (416, 1, True), (512, 1, True), (512, 2, False)]),
+        "forward_test_rows": forward_test,
+        "train_step": train_step,
+    }
+
+
+# Launches per kernel family of launch_cases(), measured at the commit BEFORE the modules' `cl` methods took layouts (the network
+# then written out twice, once per form); the single composition has to issue exactly these.  A change that alters a count on
+# purpose updates the literal.
+LAUNCHES = {
+    "batch": {"attn_flash": 16, "dwconv_ln": 34, "gemm_x3_mfma": 118, "layernorm": 32, "local_attn": 5, "mask_head": 1, "maxpool_mask": 3,
+              "transpose": 5},
+    "rows_global": {"attn_flash": 52, "dwconv_ln": 34, "gemm_x3_mfma": 136, "layernorm": 39, "local_attn": 5, "mask_head": 16,
+                    "maxpool_mask": 12, "transpose": 20},
+    "rows_banded": {"attn_small": 40, "dwconv_ln": 34, "gemm_x3_mfma": 136, "layernorm": 39, "local_attn": 13, "mask_head": 36,
+                    "maxpool_mask": 27, "transpose": 45},
+    "forward_test_rows": {"attn_flash": 64, "dwconv_ln": 35, "gemm_x3_dma": 1, "gemm_x3_mfma": 127, "layernorm": 37, "local_attn": 6,
+                          "mask_head": 5, "maxpool_mask": 15, "postprocess": 5, "transpose": 12},
+    "train_step": {"attn_flash": 16, "backward": 581, "dwconv_ln": 34, "gemm_f32_mfma": 6, "gemm_x3_mfma": 254, "layernorm": 102,
+                   "local_attn": 5, "mask_head": 4, "maxpool_mask": 3, "transpose": 5},
+}
+
+
+def test_network_launch_counts():
+    """The batch form, the row-space form and a training step issue the same launches per kernel family as before the two
+    forms shared one composition: no structure-dependent operation gained or lost a launch (e.g. the stacked [subject | object]
+    halves of a one-bucket layout are one launch)."""
+    from test_gpu_f16_range import launches
+    for name, run in launch_cases().items():
+        run()                                       # (the first call of a model also builds the per-weight operand caches)
+        got = launches(run)
+        print(name, got)
+        assert got == LAUNCHES[name], (name, got)
+
+
 def test_pack_pairs_equals_padded_batch(precision):
     """Batching straight from the frame-major per-pair matrices == zero-padded (B, C_in, T) batch + unpack."""
     from vrdone_amd import ops

@@ -295,6 +295,26 @@ def test_row_space_layout_and_filler_buckets():
     assert ragged.filler_buckets(4096 + 32, 288) == [] and ragged.filler_buckets(65536 + 48, 40) == []
     segs = _hip.RowSegs.of(lay.twice())
     assert segs.count == 6 and list(segs.row)[:6] == [0, 96, 288, 336, 432, 624] and list(segs.T)[:3] == [32, 96, 48]
+    # the stacked [subject | object] rows as a layout of their own, every second frame, the predictor's 10 queries per sequence
+    assert lay.stacked().segs == lay.twice() and lay.stacked().tail_rows(1, "cpu").tolist() == lay.tail_rows(2, "cpu").tolist()
+    assert lay.strided(2).segs == [(0, 3, 16), (48, 2, 48), (144, 1, 24)] and lay.queries(10).segs == [(0, 3, 10), (30, 2, 10), (50, 1, 10)]
+    assert lay.min_frames() == 32
+    with torch.no_grad():
+        assert lay.new(4, torch.zeros(1)).shape == (1, 336, 4)
+    with torch.enable_grad(), __import__("pytest").raises(AssertionError):
+        lay.new(4, torch.zeros(1))                                # the row space is an inference form
+    s, o = lay.halves(torch.arange(672.0).view(1, 672, 1))
+    assert s.shape == o.shape == (1, 336, 1) and float(o[0, 0]) == 336.0
+    # the batch form: one bucket, the tensor is (sequences, frames, channels); its two stacked halves are one bucket of twice the sequences
+    one = ragged.Layout.of(None, torch.zeros(4, 96, dtype=torch.bool))
+    assert one is ragged.Layout.batch(4, 96) and one.segs == [(0, 4, 96)] and one.rows == 384 and one.rows_flat == 0
+    assert one.twice() == [(0, 4, 96), (384, 4, 96)] and one.tail_rows(1, "cpu") is None and one.tail_rows(2, "cpu") is None
+    assert one.stacked() is ragged.Layout.batch(8, 96) and one.strided(2) is ragged.Layout.batch(4, 48) and one.queries(10).segs == [(0, 4, 10)]
+    assert ragged.Layout.of(lay, torch.zeros(4, 96)) is lay and one.new(4, torch.zeros(1)).shape == (4, 96, 4)
+    x = torch.arange(8 * 96.0).view(8, 96, 1)
+    s, o = one.halves(x)
+    assert torch.equal(s, x[:4]) and torch.equal(o, x[4:]) and one.part(x, one.stacked().segs[0]) is x and one.whole(x) is x
+    assert lay.part(torch.arange(336.0).view(1, 336), (96, 2, 96)).shape == (2, 96) and lay.whole(torch.zeros(7, 48, 2)).shape == (1, 336, 2)
 
 
 def test_flat_k3_conv_with_zeroed_tails_equals_the_per_sequence_conv_on_valid_rows():

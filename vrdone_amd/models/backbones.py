@@ -10,7 +10,8 @@ materialised -- producers write into column slabs of the consumer's input buffer
 import torch
 from torch import nn
 
-from .blocks import ConvMLP, LayerNorm, MaskedConv1D, TransformerBlock, _from_cl, _mask2d, _ops, get_sinusoid_encoding
+from . import ragged
+from .blocks import ConvMLP, LayerNorm, Layout, MaskedConv1D, TransformerBlock, _from_cl, _mask2d, _ops, get_sinusoid_encoding
 from .local_transformer import MaskedConvTransformerDecoderLayer
 
 
@@ -105,18 +106,16 @@ class MaskConvTransformerBackbone(nn.Module):
         return (stacked(0, V, pair), stacked(2 * V, Cc, pair) if Cc else None, so_box, stacked(o0 + S, E, False))
 
     @staticmethod
-    def _embed(h, convs, norms, mask2, out, post_add=None):
-        """k=3 conv * mask -> LN -> ReLU stack on 2B stacked sequences; the last LN writes into `out`, a column
+    def _embed(h, convs, norms, mask2, out, lay, post_add=None):
+        """k=3 conv * mask -> LN -> ReLU stack on the stacked sequences of `lay`; the last LN writes into `out`, a column
         slab of the consumer GEMM's input buffer (pair rows in bf16x3 mode)."""
         ops = _ops()
         last = len(convs) - 1
         if last == 0 and post_add is None and ops.conv_ln_ok(h, convs[0].conv.weight, convs[0].conv.bias, norms[0].weight, norms[0].bias):
-            # few input channels (the box features): conv, mask, LayerNorm and ReLU as one row kernel
-            c, nm = convs[0].conv, norms[0]
-            return ops.conv_ln(h, c.weight, c.bias, row_mask=mask2, gamma=nm.weight.reshape(-1), beta=nm.bias.reshape(-1), relu=True,
-                               out=out, pair=ops.pair_mode())
+            # few input channels (the box features): conv, mask, LayerNorm and ReLU as one row kernel, straight into the consumer's slab
+            return ragged.conv3(lay, h, convs[0].conv, mask2, out=out, out_pair=ops.pair_mode(), norm=norms[0])
         for i, (conv, norm) in enumerate(zip(convs, norms)):
-            h = ops.conv_gemm(h, conv.conv.weight, conv.conv.bias, row_mask=mask2)
+            h = ragged.conv3(lay, h, conv.conv, mask2)
             h = norm.cl(h, relu=True, out=out if i == last else None, pair=ops.pair_mode(), post_add=post_add if i == last else None)
         return h
 
@@ -153,16 +152,17 @@ class MaskConvTransformerBackbone(nn.Module):
         rows = pe[0, :, :T].t()                                              # (T, D)
         return (rows[None] * mask2[..., None].to(rows.dtype)).reshape(n * T, -1).contiguous()
 
-    def entity_stage(self, vis, clip, ent, mask2):
+    def entity_stage(self, vis, clip, ent, mask2, lay=None):
         """Everything that sees ONE entity's frames only -- embeddings, visual/box fusion and the first stem block, all
         with weights shared between subject and object (reference backbones.py:172-214): n sequences in, (n, T, D) out.
         Every op in it is local in time (see entity_reach), which is what lets forward_test run it once per tracklet
-        instead of once per pair."""
+        instead of once per pair.  lay: the layout of the rows (default: the batch form of n sequences)."""
         ops = _ops()
-        n, T = mask2.shape
+        lay = Layout.of(lay, mask2)
+        assert not self.use_abs_pe or lay.axis == 0, "absolute position rows are laid out per padded length: such models run bucket by bucket"
         Cc = self.n_clip
         D = self.s_fuse_norm.num_channels
-        new = lambda *shape: torch.empty(*shape, device=mask2.device, dtype=torch.float32)   # noqa: E731
+        new = lambda width: lay.new(width, mask2)          # noqa: E731
 
         # concatenation buffers hold two D-wide slabs; in bf16x3 mode both slabs are pair rows (width D)
         pair = ops.pair_mode()
@@ -170,56 +170,55 @@ class MaskConvTransformerBackbone(nn.Module):
 
         # [visual (+clip) | entity box] -> visual_bbox_fuse
         # (ops.join: the slab-filled buffer, or -- under autograd, where ops return fresh tensors -- the concatenation)
-        fuse_in = new(n, T, 2 * D)
+        fuse_in = new(2 * D)
         pe = self._position_rows(mask2) if self.use_abs_pe else None        # (n * T, D): pe[t] on valid frames, 0 on padded ones
         if Cc:
-            vc = new(n, T, 2 * D)
-            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, vc[..., :D])
-            b = self._embed(clip, self.clip_embd, self.clip_embd_norm, mask2, vc[..., D:])
+            vc = new(2 * D)
+            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, vc[..., :D], lay)
+            b = self._embed(clip, self.clip_embd, self.clip_embd_norm, mask2, vc[..., D:], lay)
             # (CLIP variant: the position rows are added behind the visual / CLIP fusion, backbones.py:362-384)
             a = self.visual_clip_fuse.cl(cat(ops.join(vc, (a, b))), row_mask=mask2, out=fuse_in[..., :D], out_pair=pair, res=pe)
         else:
-            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, fuse_in[..., :D], post_add=pe)
-        b = self._embed(ent, [self.bbox_entity_embd], [self.bbox_entity_norm], mask2, fuse_in[..., D:])
+            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, fuse_in[..., :D], lay, post_add=pe)
+        b = self._embed(ent, [self.bbox_entity_embd], [self.bbox_entity_norm], mask2, fuse_in[..., D:], lay)
         so = self.visual_bbox_fuse.cl(cat(ops.join(fuse_in, (a, b))), row_mask=mask2)
-        so, _ = self.stem[0].cl(so, mask2)
+        so, _ = self.stem[0].cl(so, mask2, lay=lay)
         return so
 
-    def pair_stage(self, so, so_box, mask):
-        """so: (2B, T, D) entity-stage output, subject rows then object rows; from the first subject<->object attention on."""
+    def pair_stage(self, so, so_box, mask, lay=None):
+        """so: (2B, T, D) entity-stage output, subject rows then object rows; from the first subject<->object attention on.
+        lay: the layout of the pairs' rows (of so_box and mask; so is in lay.stacked()); default: the batch form."""
         ops = _ops()
-        B, T = mask.shape
+        lay = Layout.of(lay, mask)
+        lay2 = lay.stacked()
         D = self.s_fuse_norm.num_channels
-        dev = mask.device
-        mask2 = torch.cat([mask, mask], dim=0)
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)   # noqa: E731
+        mask2 = torch.cat([mask, mask], dim=lay.axis)
         pair = ops.pair_mode()
         cat = (lambda t: ops.Pair(t, D)) if pair else (lambda t: t)          # noqa: E731
 
         for i, (s_attn, o_attn) in enumerate(zip(self.s_attn, self.o_attn)):
             if i:
-                so, _ = self.stem[i].cl(so, mask2)
-            s, o = so[:B], so[B:]
-            nxt = new(2 * B, T, D)
-            s2, _ = s_attn.cl(s, o, mask, mask, stream_add=s, out=nxt[:B])         # s + s_attn(s, o)
-            o2, _ = o_attn.cl(o, s, mask, mask, stream_add=o, out=nxt[B:])         # uses the pre-update s
-            so = ops.join(nxt, (s2, o2), dim=0)
+                so, _ = self.stem[i].cl(so, mask2, lay=lay2)
+            s, o = lay.halves(so)
+            nxt = lay2.new(D, mask)
+            out_s, out_o = lay.halves(nxt)
+            s2, _ = s_attn.cl(s, o, mask, mask, stream_add=s, out=out_s, qlay=lay, klay=lay)      # s + s_attn(s, o)
+            o2, _ = o_attn.cl(o, s, mask, mask, stream_add=o, out=out_o, qlay=lay, klay=lay)      # uses the pre-update s
+            so = ops.join(nxt, (s2, o2), dim=lay.axis)
 
-        so_in = new(B, T, 2 * D)
-        a = self.s_fuse_norm.cl(so[:B], out=so_in[..., :D], pair=pair)
-        b = self.o_fuse_norm.cl(so[B:], out=so_in[..., D:], pair=pair)
-        pair_box = new(B, T, 2 * D)
+        s, o = lay.halves(so)
+        so_in = lay.new(2 * D, mask)
+        a = self.s_fuse_norm.cl(s, out=so_in[..., :D], pair=pair)
+        b = self.o_fuse_norm.cl(o, out=so_in[..., D:], pair=pair)
+        pair_box = lay.new(2 * D, mask)
         a = self.so_fuse.cl(cat(ops.join(so_in, (a, b))), row_mask=mask, out=pair_box[..., :D], out_pair=pair)
-        conv = self.bbox_so_embd.conv
-        if ops.conv_ln_ok(so_box, conv.weight, conv.bias):
-            b = ops.conv_ln(so_box, conv.weight, conv.bias, row_mask=mask, out=pair_box[..., D:], pair=pair)
-        else:
-            b = ops.conv_gemm(so_box, conv.weight, conv.bias, row_mask=mask, out=pair_box[..., D:], out_pair=pair)
+        b = ragged.conv3(lay, so_box, self.bbox_so_embd.conv, mask, out=pair_box[..., D:], out_pair=pair)
         e = self.so_visual_bbox_fuse.cl(cat(ops.join(pair_box, (a, b))), row_mask=mask)
 
         feats, masks = [e], [mask]
         for blk in self.branch:
-            e, mask = blk.cl(e, mask)
+            e, mask = blk.cl(e, mask, lay=lay)
+            lay = lay.strided(blk.attn.n_kv_stride)
             feats.append(e)
             masks.append(mask)
         return feats, masks

@@ -7,7 +7,10 @@ Two call forms per module:
   * ``forward(...)``  the reference's signature on ``(B, C, T)`` tensors / ``(B, 1, T)`` bool
     masks (a layout change is done around the channels-last core; used by module-level tests),
   * ``cl(...)``       the channels-last core on ``(B, T, C)`` tensors / ``(B, T)`` masks that
-    MaskVRD chains end to end without any transposes.
+    MaskVRD chains end to end without any transposes.  It is the ONE composition of the module: it also takes a
+    ``ragged.Layout`` saying where the sequences lie in the rows (default: the batch form read from the tensors' shape;
+    otherwise a row space ``(1, R, C)`` of several buckets of sequences, inference only) and passes it to the few operations
+    that need the (sequences, frames) structure (models/ragged.py); everything else works row by row.
 Under torch.no_grad() (eval, validation) the modules run the fused inference kernels; with autograd recording
 they run the differentiable composition of vrdone_amd/autograd.py (HIP forward and backward kernels, plain f32 rows),
 and in training mode AffineDropPath samples its per-sample keep factors (reference blocks.py:1107-1120).
@@ -17,12 +20,9 @@ import math
 import torch
 from torch import nn
 
+from . import ragged
+from .ragged import Layout, _ops
 from .transformer import _get_activation_fn  # noqa: F401  (re-exported like the reference)
-
-
-def _ops():
-    from .. import ops      # deferred: constructing / loading a model needs no GPU
-    return ops
 
 
 def _mask2d(mask):
@@ -211,6 +211,7 @@ class Scale(nn.Module):
 class _ConvAttention(nn.Module):
     """Parameter tree shared by the conv-attention modules: depthwise conv + LayerNorm per
     q/k/v branch, then 1x1 projections (creation order = reference state_dict order)."""
+    _half_win = None                # half the window of the banded forms; None = global attention
 
     def _build(self, n_embd, n_head, q_kernel, kv_kernel, stride):
         assert n_embd % n_head == 0
@@ -248,14 +249,13 @@ class _ConvAttention(nn.Module):
                 groups.append((x, m, use_ln, ks, [name]))
         return groups
 
-    def _prep(self, q_in, k_in, v_in, q_mask, kv_mask, stride=1, pre_ln=None, pre_ln_on="qkv"):
+    def _prep(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv"):
         """dwconv * mask -> LN for the three branches (one launch per group of _groups).
         pre_ln (gamma, beta): inputs named in pre_ln_on ('q', 'k', 'v') are LayerNorm'ed as they are read."""
-        ops = _ops()
         outs = {}
         for x, m, use_ln, _, names in self._groups(q_in, k_in, v_in, q_mask, kv_mask, pre_ln, pre_ln_on):
-            res = ops.dwconv_ln(x, [self._branch_set(n) for n in names], mask_out=m, stride=stride,
-                                pre_ln=pre_ln if use_ln else None)
+            res = ragged.dwconv_ln(qlay if x is q_in else klay, x, [self._branch_set(n) for n in names], m, stride=stride,
+                                   pre_ln=pre_ln if use_ln else None)
             outs.update(zip(names, res))
         return outs["query"], outs["key"], outs["value"]
 
@@ -267,6 +267,28 @@ class _ConvAttention(nn.Module):
             ((q, self.query.weight, self.query.bias), dict(out_pair=out_pair, skip_rows=q_mask)),
             ((k, self.key.weight, self.key.bias), dict(out_pair=out_pair, skip_rows=kv_mask)),
             ((v, self.value.weight, self.value.bias), dict(out_pair=out_pair, skip_rows=kv_mask))]))
+
+    def _attend(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", **epilogue):
+        """The module's forward: the queries q_in in the layout qlay attend to the keys / values k_in / v_in in klay; q_mask /
+        kv_mask are the masks behind the depthwise convs' stride; epilogue kwargs go to the output-projection GEMM."""
+        ops = _ops()
+        q, k, v = self._prep(q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=stride, pre_ln=pre_ln, pre_ln_on=pre_ln_on)
+        qlay, klay = qlay.strided(stride), klay.strided(stride)
+        # global attention on the split-precision flash kernel consumes q/k/v as pair rows (one choice for all buckets)
+        qkv_pair = self._half_win is None and ops.flash_pair_ok(self.n_head, self.n_embd, qlay.min_frames())
+        q, k, v = self._project(q, k, v, out_pair=qkv_pair, q_mask=q_mask, kv_mask=kv_mask)
+        att = ragged.attention(q, k, v, kv_mask, q_mask, self.n_head, qlay, klay, half_win=self._half_win,
+                               rel_pe=getattr(self, "rel_pe", None), pair=ops.pair_mode())
+        return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=q_mask, **epilogue), q_mask
+
+    def _cl_strided(self, x, mask, mask_out=None, pre_ln=None, lay=None, **epilogue):
+        """x = LN1 output (B, T, C), or the block input with pre_ln = (ln1.weight, ln1.bias) applied inside the
+        depthwise-conv kernel; epilogue kwargs go to the output-projection GEMM."""
+        s = self.n_kv_stride
+        if mask_out is None:
+            mask_out = mask if s == 1 else mask[:, ::s].contiguous()
+        lay = Layout.of(lay, mask)
+        return self._attend(x, x, x, mask_out, mask_out, lay, lay, stride=s, pre_ln=pre_ln, **epilogue)
 
 
 def make_rel_pe(n_embd, n_head, window_size):
@@ -287,26 +309,16 @@ class LocalMaskedMHCA(_ConvAttention):
         assert n_qx_stride == n_kv_stride and n_kv_stride in (1, 2)
         assert attn_pdrop == 0.0 and proj_pdrop == 0.0
         self.window_size, self.window_overlap = window_size, window_size // 2
+        self._half_win = self.window_overlap
         self.use_rel_pe = use_rel_pe
         self.n_qx_stride, self.n_kv_stride = n_qx_stride, n_kv_stride
         ks = n_kv_stride + 1 if n_kv_stride > 1 else 3
         self._build(n_embd, n_head, ks, ks, n_kv_stride)
         self.rel_pe = make_rel_pe(n_embd, n_head, window_size) if use_rel_pe else None
 
-    def cl(self, x, mask, mask_out=None, pre_ln=None, **epilogue):
-        """x = LN1 output (B, T, C), or the block input with pre_ln = (ln1.weight, ln1.bias) applied inside the
-        depthwise-conv kernel; epilogue kwargs go to the output-projection GEMM."""
-        ops = _ops()
-        s = self.n_kv_stride
-        if mask_out is None:
-            mask_out = mask if s == 1 else mask[:, ::s].contiguous()
-        # (the reference's sliding-chunk form needs T / s to be a multiple of 2 * window_overlap, blocks.py:828, and its callers
-        # pad for that; the banded kernel here does not: MaskVRD's tight padding runs pairs at shorter padded lengths)
-        q, k, v = self._prep(x, x, x, mask_out, mask_out, stride=s, pre_ln=pre_ln)
-        q, k, v = self._project(q, k, v, q_mask=mask_out, kv_mask=mask_out)
-        att = ops.local_attention(q, k, v, mask_out, self.n_head, self.window_overlap, pair=ops.pair_mode(),
-                                  rel_pe=self.rel_pe)
-        return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=mask_out, **epilogue), mask_out
+    # (the reference's sliding-chunk form needs T / s to be a multiple of 2 * window_overlap, blocks.py:828, and its callers
+    # pad for that; the banded kernel here does not: MaskVRD's tight padding runs pairs at shorter padded lengths)
+    cl = _ConvAttention._cl_strided
 
     def forward(self, x, mask):
         assert (x.shape[-1] // self.n_kv_stride) % (2 * self.window_overlap) == 0      # reference blocks.py:828
@@ -327,16 +339,7 @@ class MaskedMHCA(_ConvAttention):
         ks = n_kv_stride + 1 if n_kv_stride > 1 else 3
         self._build(n_embd, n_head, ks, ks, n_kv_stride)
 
-    def cl(self, x, mask, mask_out=None, pre_ln=None, **epilogue):
-        ops = _ops()
-        s = self.n_kv_stride
-        if mask_out is None:
-            mask_out = mask if s == 1 else mask[:, ::s].contiguous()
-        q, k, v = self._prep(x, x, x, mask_out, mask_out, stride=s, pre_ln=pre_ln)
-        qkv_pair = ops.flash_pair_ok(self.n_head, self.n_embd, q.shape[1])
-        q, k, v = self._project(q, k, v, out_pair=qkv_pair, q_mask=mask_out, kv_mask=mask_out)
-        att = ops.attention(q, k, v, mask_out, self.n_head, pair=ops.pair_mode(), q_mask=mask_out)
-        return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=mask_out, **epilogue), mask_out
+    cl = _ConvAttention._cl_strided
 
     def forward(self, x, mask):
         y, m = self.cl(_to_cl(x), _mask2d(mask))
@@ -358,12 +361,12 @@ class MaskedMHA(nn.Module):
         self.attn_drop, self.proj_drop = nn.Dropout(0.0), nn.Dropout(0.0)
         self.proj = nn.Conv1d(n_embd, n_embd, 1)
 
-    def cl_qkv(self, q_in, k_in, v_in, q_mask, kv_mask, **epilogue):
+    def cl_qkv(self, q_in, k_in, v_in, q_mask, kv_mask, qlay=None, klay=None, **epilogue):
         ops = _ops()
         q = ops.conv_gemm(q_in, self.query.weight, self.query.bias)
         k = ops.conv_gemm(k_in, self.key.weight, self.key.bias)
         v = ops.conv_gemm(v_in, self.value.weight, self.value.bias)
-        att = ops.attention(q, k, v, kv_mask, self.n_head)
+        att = ragged.attention(q, k, v, kv_mask, None, self.n_head, Layout.of(qlay, q_in), Layout.of(klay, k_in))
         return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=q_mask, **epilogue), q_mask
 
     def forward(self, x, mask):
@@ -412,14 +415,16 @@ class TransformerBlock(nn.Module):
         """Per-row stochastic-depth factors of a branch whose rows follow `mask` (B, T'), or None."""
         return dp.row_factors(mask.shape[0], mask.shape[1], mask.device) if isinstance(dp, AffineDropPath) else None
 
-    def cl(self, x, mask, out=None):
+    def cl(self, x, mask, out=None, lay=None):
+        """lay: the layout of x's rows (default: the batch form); the result's is lay.strided(self.attn.n_kv_stride)"""
         ops = _ops()
+        lay = Layout.of(lay, mask)
         if self.attn.n_kv_stride > 1:
-            skip, m_out = ops.maxpool_mask(x, mask)
+            skip, m_out = ragged.maxpool_mask(lay, x, mask)
         else:
             skip, m_out = x, mask
         # ln1 is applied to the rows inside the depthwise-conv kernel (its only consumer)
-        y, _ = self.attn.cl(x, mask, m_out, pre_ln=(self.ln1.weight, self.ln1.bias),
+        y, _ = self.attn.cl(x, mask, m_out, pre_ln=(self.ln1.weight, self.ln1.bias), lay=lay,
                             scale=self._scale(self.drop_path_attn), row_scale=self._drop(self.drop_path_attn, m_out),
                             res=skip, res_masked=True)
         h = self.ln2.cl(y, pair=ops.pair_mode())

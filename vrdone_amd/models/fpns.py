@@ -8,7 +8,8 @@ mask-feature map.  Same constructor and parameter tree as the reference's FPN1D_
 """
 from torch import nn
 
-from .blocks import LayerNorm, MaskedConv1D, _from_cl, _mask2d, _ops, _to_cl
+from . import ragged
+from .blocks import LayerNorm, Layout, MaskedConv1D, _from_cl, _mask2d, _ops, _to_cl
 
 
 class FPN1D_Fuse(nn.Module):
@@ -38,21 +39,23 @@ class FPN1D_Fuse(nn.Module):
             self.fpn_norms.append(LayerNorm(out_channel))
         self.mask_features = MaskedConv1D(out_channel, out_channel, 3, padding=1, groups=out_channel)
 
-    def cl(self, feats, masks):
+    def cl(self, feats, masks, lays=None):
+        """lays: the layout of every level's rows (default: the batch form)"""
         ops = _ops()
+        lays = [Layout.of(lays and lays[l], m) for l, m in enumerate(masks)]
         y = None
         for l in range(len(self.lateral_convs) - 1, -1, -1):
             # below the top level the normalised input feeds only the lateral 1x1 GEMM
             x = self.input_norms[l].cl(feats[l], pair=ops.pair_mode() and self.lateral_convs[l] is not None)
             fpn = dict(weight=self.fpn_convs[l].conv.weight, gamma=self.fpn_norms[l].weight, beta=self.fpn_norms[l].bias)
             if self.lateral_convs[l] is None:
-                y, = ops.dwconv_ln(x, [fpn], mask_out=masks[l])
+                y, = ragged.dwconv_ln(lays[l], x, [fpn], masks[l])
             else:
                 c = ops.conv_gemm(x, self.lateral_convs[l].conv.weight, None, row_mask=masks[l])
                 c = self.lateral_norms[l].cl(c)
-                y, = ops.dwconv_ln(c, [fpn], mask_out=masks[l], x_up=y)
+                y, = ragged.dwconv_ln(lays[l], c, [fpn], masks[l], x_up=y)
         mf = self.mask_features.conv
-        out, = ops.dwconv_ln(y, [dict(weight=mf.weight, bias=mf.bias)], mask_out=masks[0])
+        out, = ragged.dwconv_ln(lays[0], y, [dict(weight=mf.weight, bias=mf.bias)], masks[0])
         return out, masks[0]
 
     def forward(self, inputs, fpn_masks):

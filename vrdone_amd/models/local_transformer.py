@@ -4,10 +4,9 @@ arguments and parameter trees follow the reference's models/local_transformer.py
 HIP kernels (see models/blocks.py for the two call forms)."""
 from typing import Optional
 
-import torch
 from torch import nn, Tensor
 
-from .blocks import (make_rel_pe, AffineDropPath, LayerNorm, MaskedMHA, _ConvAttention, _from_cl, _mask2d, _ops,
+from .blocks import (make_rel_pe, AffineDropPath, LayerNorm, Layout, MaskedMHA, _ConvAttention, _from_cl, _mask2d, _ops,
                      _to_cl)
 from .transformer import _get_clones
 
@@ -29,7 +28,6 @@ def _qkv_kernel(stride):
 class MaskedMHCA_QKV(_ConvAttention):
     """Conv attention with separate q/k/v inputs and full (global) masked attention;
     reference models/local_transformer.py:69-187."""
-    _half_win = None
 
     def __init__(self, n_embd, n_head, n_qx_stride=0, n_kv_stride=1, attn_pdrop=0.0, proj_pdrop=0.0):
         super().__init__()
@@ -37,21 +35,12 @@ class MaskedMHCA_QKV(_ConvAttention):
         self.n_qx_stride, self.n_kv_stride = n_qx_stride, n_kv_stride
         self._build(n_embd, n_head, _qkv_kernel(n_qx_stride), _qkv_kernel(n_kv_stride), 1)
 
-    def cl_qkv(self, q_in, k_in, v_in, q_mask, kv_mask, pre_ln=None, pre_ln_on="", **epilogue):
+    def cl_qkv(self, q_in, k_in, v_in, q_mask, kv_mask, pre_ln=None, pre_ln_on="", qlay=None, klay=None, **epilogue):
         """pre_ln = (gamma, beta) with pre_ln_on naming the inputs ('q', 'k', 'v') that are passed un-normalised and
-        get that LayerNorm inside the depthwise-conv kernel (the decoder layer's ln1 / ln2)."""
-        ops = _ops()
-        q, k, v = self._prep(q_in, k_in, v_in, q_mask, kv_mask, pre_ln=pre_ln, pre_ln_on=pre_ln_on)
-        # global attention on the split-precision flash kernel consumes q/k/v as pair rows
-        qkv_pair = self._half_win is None and ops.flash_pair_ok(self.n_head, self.n_embd, q.shape[1])
-        q, k, v = self._project(q, k, v, out_pair=qkv_pair, q_mask=q_mask, kv_mask=kv_mask)
-        if self._half_win is None:
-            att = ops.attention(q, k, v, kv_mask, self.n_head, pair=ops.pair_mode(), q_mask=q_mask)
-        else:
-            assert q.shape[1] == k.shape[1]
-            att = ops.local_attention(q, k, v, kv_mask, self.n_head, self._half_win, pair=ops.pair_mode(),
-                                      rel_pe=getattr(self, "rel_pe", None))
-        return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=q_mask, **epilogue), q_mask
+        get that LayerNorm inside the depthwise-conv kernel (the decoder layer's ln1 / ln2).
+        qlay / klay: the layouts of the query and the key / value rows (default: the batch form)."""
+        return self._attend(q_in, k_in, v_in, q_mask, kv_mask, Layout.of(qlay, q_in), Layout.of(klay, k_in), pre_ln=pre_ln,
+                            pre_ln_on=pre_ln_on, **epilogue)
 
     def forward(self, q, k, v, _qx_mask, _kv_mask, _attn_mask=None):
         assert _attn_mask is None
@@ -129,11 +118,14 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         """Per-row stochastic-depth factors for a branch shaped like tgt (B, Tq, C), or None."""
         return dp.row_factors(tgt.shape[0], tgt.shape[1], tgt.device) if isinstance(dp, AffineDropPath) else None
 
-    def cl(self, tgt, memory, tgt_mask, memory_mask, query_pos=None, stream_add=None, out=None):
+    def cl(self, tgt, memory, tgt_mask, memory_mask, query_pos=None, stream_add=None, out=None, qlay=None, klay=None):
         """tgt (B, Tq, C), memory (B, Tk, C); masks (B, T) or None (= all valid).  query_pos: (Tq, C)
         rows added to the normalised target.  stream_add: extra tensor added to the cross-attention
-        output (the SOS update s + s_mutual of reference backbones.py:220-221), fused into the GEMM."""
+        output (the SOS update s + s_mutual of reference backbones.py:220-221), fused into the GEMM.
+        qlay / klay: the layouts of the rows of tgt and of memory (default: the batch form)."""
         ops = _ops()
+        qlay, klay = Layout.of(qlay, tgt), Layout.of(klay, memory)
+        self_lays, cross_lays = dict(qlay=qlay, klay=qlay), dict(qlay=qlay, klay=klay)
         # without query_pos (the SOS layers) ln1 / ln2 feed only the depthwise-conv branches of the attention modules
         # and are applied inside that kernel; with query_pos (predictor) they stay separate kernels
         fuse1 = query_pos is None and isinstance(self.self_attn, MaskedMHCA_QKV)
@@ -142,13 +134,13 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         if fuse1:
             tgt, _ = self.self_attn.cl_qkv(tgt, tgt, tgt, tgt_mask, tgt_mask, pre_ln=(self.ln1.weight, self.ln1.bias),
                                            pre_ln_on="qk", scale=self._scale(self.drop_path_attn1),
-                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True)
+                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True, **self_lays)
         else:
             t2 = self.ln1.cl(tgt, post_add=query_pos)
             tgt, _ = self.self_attn.cl_qkv(t2, t2, tgt, tgt_mask, tgt_mask, scale=self._scale(self.drop_path_attn1),
-                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True)
+                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True, **self_lays)
         kw = dict(scale=self._scale(self.drop_path_attn2), row_scale=self._drop(self.drop_path_attn2, tgt), res=tgt,
-                  res_masked=True, res2=stream_add if last else None, out=out if last else None)
+                  res_masked=True, res2=stream_add if last else None, out=out if last else None, **cross_lays)
         if fuse2:
             tgt, _ = self.multihead_attn.cl_qkv(tgt, memory, memory, tgt_mask, memory_mask,
                                                 pre_ln=(self.ln2.weight, self.ln2.bias), pre_ln_on="q", **kw)
@@ -192,11 +184,11 @@ class MaskedConvTransformerDecoder(nn.Module):
         self.norm = norm
         self.return_intermediate = return_intermediate
 
-    def cl(self, tgt, memory, memory_mask, query_pos, all_layers):
+    def cl(self, tgt, memory, memory_mask, query_pos, all_layers, qlay=None, klay=None):
         """Returns the normalised output of every layer (all_layers) or of the last one only."""
         outs = []
         for i, layer in enumerate(self.layers):
-            tgt, _ = layer.cl(tgt, memory, None, memory_mask, query_pos=query_pos)
+            tgt, _ = layer.cl(tgt, memory, None, memory_mask, query_pos=query_pos, qlay=qlay, klay=klay)
             if all_layers or i == self.num_layers - 1:
                 outs.append(self.norm.cl(tgt))
         return outs
@@ -220,8 +212,10 @@ class MaskedConvTransformerDecoderOnly(nn.Module):
             if isinstance(m, (nn.Linear, nn.Conv1d)) and m.bias is not None:
                 nn.init.zeros_(m.bias)
 
-    def cl(self, src, src_mask, query_embed, all_layers):
-        """src (B, Tk, C), query_embed (Q, C) -> list of (B, Q, C) normalised layer outputs."""
-        B = src.shape[0]
-        tgt = torch.zeros(B, query_embed.shape[0], query_embed.shape[1], device=src.device, dtype=torch.float32)
-        return self.decoder.cl(tgt, src, src_mask, query_embed, all_layers)
+    def cl(self, src, src_mask, query_embed, all_layers, klay=None):
+        """src (B, Tk, C) in the layout klay, query_embed (Q, C) -> list of normalised layer outputs, Q rows per sequence of src
+        (klay.queries(Q); in the batch form (B, Q, C))."""
+        klay = Layout.of(klay, src)
+        qlay = klay.queries(query_embed.shape[0])
+        tgt = qlay.new(query_embed.shape[1], src, zeros=True)
+        return self.decoder.cl(tgt, src, src_mask, query_embed, all_layers, qlay, klay)

@@ -360,9 +360,14 @@ class MaskVRD(nn.Module):
         out = self._heads(*bb.cl_parts(*parts, m2), False)
         return ops.postprocess(out["pred_logits"].contiguous(), out["pred_masks"].contiguous(), lens_dev, k)
 
-    def _heads(self, feats, masks, with_aux):
-        fpn_feat, _ = self.neck.cl(feats, masks)
-        return self.predictor.cl(feats[-1], fpn_feat, masks[-1], masks[0], with_aux=with_aux)
+    def _heads(self, feats, masks, with_aux, lay=None):
+        """neck + predictor.  lay: the layout of the full-resolution rows; without one the batch form and the reference's dict,
+        with one the predictor's per-bucket heads (predictor.py `heads`: buckets differ in length)."""
+        lays = lay and [lay.strided(self.scale_factor ** l) for l in range(len(feats))]
+        fpn_feat, _ = self.neck.cl(feats, masks, lays)
+        if lay is None:
+            return self.predictor.cl(feats[-1], fpn_feat, masks[-1], masks[0], with_aux=with_aux)
+        return self.predictor.heads(feats[-1], fpn_feat, masks[-1], masks[0], with_aux, klay=lays[-1], lay0=lay)
 
     @staticmethod
     def _merge(outs):
@@ -965,7 +970,7 @@ class MaskVRD(nn.Module):
                     flat_rows = torch.cat([h.reshape(-1, h.shape[-1]) for h in halves]).view(1, 2 * lay_e.rows, -1)
                     return ops.Pair(flat_rows, ts[0].width, ts[0].fmt) if isinstance(ts[0], ops.Pair) else flat_rows
                 m_e = torch.cat([g[-1].reshape(-1) for _, g in ent_b]).view(1, lay_e.rows)
-                so_e = ragged.entity_rows(bb, stacked(1), stacked(2), stacked(4), torch.cat([m_e, m_e], dim=1), lay_e)
+                so_e = bb.entity_stage(stacked(1), stacked(2), stacked(4), torch.cat([m_e, m_e], dim=1), lay_e.stacked())
             # the joint entity-stage rows: every bucket's subject rows, then every bucket's object rows
             halves, e_at = ([], []), 0
             for (T, c0, c1, flat), g in zip(wave, got):
@@ -979,7 +984,7 @@ class MaskVRD(nn.Module):
                     e_at += n * T
             so = torch.cat(halves[0] + halves[1]).view(1, 2 * lay.rows, -1)
             del got, so_e, halves
-            heads = ragged.heads_rows(self, *ragged.pair_rows(bb, so, so_box, mask, lay), False)
+            heads = self._heads(*bb.pair_stage(so, so_box, mask, lay), False, lay)
             logits, segs = heads[-1]
             p = 0
             for (T, c0, c1, flat), seg in zip(wave, segs):

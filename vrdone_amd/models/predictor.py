@@ -5,7 +5,8 @@ import math
 
 from torch import nn
 
-from .blocks import ConvMLP, LayerNorm, _mask2d, _ops, _to_cl
+from . import ragged
+from .blocks import ConvMLP, LayerNorm, Layout, _mask2d, _ops, _to_cl
 from .local_transformer import MaskedConvTransformerDecoderOnly
 
 
@@ -30,29 +31,38 @@ class MaskedTransformerPredictor(nn.Module):
         nn.init.constant_(self.class_embed.bias, -math.log((1 - cls_prior_prob) / cls_prior_prob))
         self.mask_embed = ConvMLP(n_embd, n_embd, n_embd, 3)
 
-    def _heads(self, hs, mask_features, output_mask, fill):
+    def heads(self, x, mask_features, mask, output_mask, with_aux=None, fill=-10.0, klay=None, lay0=None):
+        """x, mask: the coarsest level's rows in the layout klay; mask_features, output_mask: the full-resolution rows in lay0
+        (default: the batch form, x (B, T/8, D), mask_features (B, T, Dp), mask (B, T/8), output_mask (B, T)).
+        -> [(logits (B, Q, K+1), [mask logits (n_i, Q, T_i) per bucket of lay0])] for the last decoder layer, preceded by the
+        other layers' when with_aux asks for them."""
         ops = _ops()
-        logits = ops.conv_gemm(hs, self.class_embed.weight, self.class_embed.bias)      # (B, Q, K+1)
-        seg = ops.mask_head(self.mask_embed.cl(hs), mask_features, output_mask, fill)   # (B, Q, T)
-        return logits, seg
-
-    def cl(self, x, mask_features, mask, output_mask, with_aux=None, non_attn_const=-10):
-        """x (B, T/8, D), mask_features (B, T, Dp), mask (B, T/8), output_mask (B, T).
-        with_aux=None follows the reference (all decoder layers' heads when deep_supervision);
-        with_aux=False computes the last layer only (what forward_test reads, maskvrd.py:206)."""
-        ops = _ops()
-        if with_aux is None:
-            with_aux = self.aux_loss
+        klay, lay0 = Layout.of(klay, mask), Layout.of(lay0, output_mask)
         src = self.input_norm.cl(x, pair=ops.pair_mode() and self.input_proj is not None)
         if self.input_proj is not None:
             src = ops.conv_gemm(src, self.input_proj.weight, self.input_proj.bias, row_mask=mask)
-        hs = self.transformer.cl(src, mask, self.query_embed.weight, all_layers=with_aux and self.aux_loss)
-        logits, seg = self._heads(hs[-1], mask_features, output_mask, float(non_attn_const))
-        out = {"pred_logits": logits, "pred_masks": seg}
-        if with_aux and self.aux_loss:
-            out["aux_outputs"] = [dict(zip(("pred_logits", "pred_masks"),
-                                           self._heads(h, mask_features, output_mask, float(non_attn_const))))
-                                  for h in hs[:-1]]
+        qlay = klay.queries(self.num_queries)
+        hs = self.transformer.cl(src, mask, self.query_embed.weight, self._with_aux(with_aux), klay)
+        out = []
+        # (the last layer's head first: under autograd the order of the heads is the order in which the gradients of their shared
+        # weights and of mask_features are summed)
+        for h in hs[-1:] + hs[:-1]:
+            h = qlay.part(h, (0, qlay.rows // self.num_queries, self.num_queries))      # (B, Q, C)
+            logits = ops.conv_gemm(h, self.class_embed.weight, self.class_embed.bias)
+            out.append((logits, ragged.mask_head(lay0, self.mask_embed.cl(h), mask_features, output_mask, fill)))
+        return out[1:] + out[:1]
+
+    def _with_aux(self, with_aux):
+        """with_aux=None follows the reference (all decoder layers' heads when deep_supervision);
+        with_aux=False computes the last layer only (what forward_test reads, maskvrd.py:206)."""
+        return bool((self.aux_loss if with_aux is None else with_aux) and self.aux_loss)
+
+    def cl(self, x, mask_features, mask, output_mask, with_aux=None, non_attn_const=-10):
+        """The batch form: x (B, T/8, D), mask_features (B, T, Dp), mask (B, T/8), output_mask (B, T) -> the reference's dict."""
+        heads = [(logits, seg) for logits, (seg,) in self.heads(x, mask_features, mask, output_mask, with_aux, float(non_attn_const))]
+        out = dict(zip(("pred_logits", "pred_masks"), heads[-1]))
+        if self._with_aux(with_aux):
+            out["aux_outputs"] = [dict(zip(("pred_logits", "pred_masks"), h)) for h in heads[:-1]]
         out["output_mask"] = output_mask[:, None, :]
         return out
 

@@ -1,60 +1,121 @@
-"""A ragged batch in ONE row space (inference only).
+"""Layouts: where the sequences of an activation lie in its rows, and the operations that need to know.
 
-`MaskVRD._mask_vrd` computes the pairs of a batch at the shortest padded lengths that give the reference's outputs
-(`tight padding`, models/maskvrd.py), pairs of equal padded length as one bucket.  Run bucket by bucket, every launch of
-the network shrinks with its bucket, and below ~260 k rows a bucket's GEMMs fall off the 256 x 256 kernel; so the
-buckets stayed few and coarse.  Here all buckets lie back to back in one row buffer per activation -- bucket i = rows
-[off_i, off_i + n_i * T_i) as n_i sequences of T_i frames -- and
+The network is composed once, in the modules' `cl` methods (blocks.py, local_transformer.py, backbones.py, fpns.py,
+predictor.py).  Most of it works row by row -- LayerNorm, every k = 1 conv GEMM with its epilogue (bias, GELU, channel scale,
+residuals, row mask), which is the bulk of the FLOPs -- and does not care which rows share a launch.  The rest needs the
+(sequences, frames) structure: depthwise conv + LayerNorm (stride 1 / 2, FPN upsample-add), the banded and the global
+attention, the pyramid's max-pool, the dense k = 3 convs, the mask head, and taking the subject / object halves of a stacked
+buffer.  Those operations live here and take a `Layout`; the `cl` methods pass their layout(s) on to them.  Two forms exist:
 
-  * everything that works row by row -- LayerNorm, every k = 1 conv GEMM with its epilogue (bias, GELU, channel scale,
-    residuals, row mask), which is the bulk of the FLOPs -- runs ONCE over all rows, whatever the bucket structure: a row's
-    result does not depend on which rows share its launch;
-  * the dense k = 3 convs of the embedding stage run once over all rows too: a k = 3 conv reads its two neighbour rows, and
-    in a flat row space frame 0 of a sequence would read the last frame of the sequence before it, where the reference's
-    Conv1d(padding=1) reads zero.  That last frame is zeroed in the conv's input.  It is read by itself, by the frame before
-    it and by the next sequence's first frame: the first two are padded frames here (tight padding keeps a coarsest-level
-    stride of padded frames behind every pair it shortens; pairs within one frame of their padded length are bucketed apart,
-    behind the others, and their buckets' k = 3 convs run one by one) whose outputs the row mask zeroes, which makes the flat
-    conv equal to the per-sequence one on every valid row;
-  * only the kernels that need the (sequences, frames) structure loop over the buckets' views: depthwise conv + LayerNorm
-    (stride 1 / 2, FPN upsample-add), the banded and the global attention, the pyramid's max-pool, the boundary transpose and
-    the mask head.
+  * the batch form (`Layout.batch`, what a `cl` method reads from its tensors' shape when no layout is given): B sequences of
+    T frames as a (B, T, C) tensor.  Every operation here is then the one `ops.*` call on that tensor, and under autograd its
+    result is the tensor the op recorded.  Training runs in this form only.
+  * the row space (inference only): `MaskVRD._mask_vrd` computes the pairs of a batch at the shortest padded lengths that give
+    the reference's outputs (`tight padding`, models/maskvrd.py), pairs of equal padded length as one bucket.  Run bucket by
+    bucket, every launch of the network shrinks with its bucket, and below ~260 k rows a bucket's GEMMs fall off the 256 x 256
+    kernel.  So all buckets lie back to back in one (1, R, C) buffer per activation -- bucket i = rows [off_i, off_i + n_i * T_i)
+    as n_i sequences of T_i frames --, the row-by-row kernels run ONCE over all rows, and only the operations here walk the
+    buckets (or hand them to a kernel as its row groups, vrd_row_segs).
 
-Subject and object rows of the shared-weight stages are stacked as [all subject buckets | all object buckets], so that
-either half is a contiguous row range with the same bucket layout.
+The dense k = 3 convs of the embedding stage run once over the rows of a row space too: a k = 3 conv reads its two neighbour rows,
+and in a flat row space frame 0 of a sequence would read the last frame of the sequence before it, where the reference's
+Conv1d(padding=1) reads zero.  That last frame is zeroed in the conv's input.  It is read by itself, by the frame before it and by
+the next sequence's first frame: the first two are padded frames here (tight padding keeps a coarsest-level stride of padded
+frames behind every pair it shortens; pairs within one frame of their padded length are bucketed apart, behind the others, and
+their buckets' k = 3 convs run one by one) whose outputs the row mask zeroes, which makes the flat conv equal to the per-sequence
+one on every valid row.
 
-The composition below follows the modules' own `cl` paths line by line (backbones.py `entity_stage` / `pair_stage`,
-blocks.py `TransformerBlock.cl`, local_transformer.py `MaskedConvTransformerDecoderLayer.cl`, fpns.py, predictor.py) and
-uses their parameters; reference: models/maskvrd.py:363-414 pads every pair to one length and computes every padded frame.
+Subject and object rows of the shared-weight stages are stacked as [all subject buckets | all object buckets] (`stacked`), so
+that either half is a contiguous range with the same bucket layout; in the batch form that is one bucket of 2B sequences.
+Reference: models/maskvrd.py:363-414 pads every pair to one length and computes every padded frame.
 """
+from contextlib import nullcontext
+
 import torch
 
-from .blocks import _ConvAttention, _ops
+
+def _ops():
+    from .. import ops      # deferred: constructing / loading a model needs no GPU
+    return ops
 
 
 _MAX_SEGS = 32          # _hip.MAX_SEGS: groups of sequences one launch takes
 
 
 class Layout:
-    """Where the buckets lie in the row space of one pyramid level: segs = [(first row, sequences, frames)].
+    """Where the buckets lie in the rows of one pyramid level: segs = [(first row, sequences, frames)].
     Buckets whose sequences all end in two padded frames (`flat`) come first: over their rows [0, rows_flat) the dense k = 3
-    convs run as one flat launch (see the module text); the others' k = 3 convs run bucket by bucket."""
+    convs run as one flat launch (see the module text); the others' k = 3 convs run bucket by bucket.
+    axis: the tensor axis the sequences are stacked along -- 1 in the row space (1, R, C), 0 in the batch form (B, T, C)."""
 
-    def __init__(self, buckets):
+    def __init__(self, buckets, axis=1):
         """buckets: [(sequences, frames, flat)]"""
-        self.segs, self.flat, off = [], [], 0
-        self._tails = {}
-        for n, T, flat in buckets:
-            self.segs.append((off, n, T))
-            self.flat.append(bool(flat))
+        segs, flat, off = [], [], 0
+        for n, T, f in buckets:
+            segs.append((off, n, T))
+            flat.append(bool(f))
             off += n * T
-        assert self.flat == sorted(self.flat, reverse=True), "buckets that take the flat k = 3 convs come first"
-        self.rows = off
-        self.rows_flat = sum(n * T for (_, n, T), f in zip(self.segs, self.flat) if f)
+        assert flat == sorted(flat, reverse=True), "buckets that take the flat k = 3 convs come first"
+        self._set(segs, flat, axis)
+
+    def _set(self, segs, flat, axis):
+        assert axis == 1 or len(segs) == 1
+        self.segs, self.flat, self.axis = segs, flat, axis
+        self.rows = sum(n * T for _, n, T in segs)
+        self.rows_flat = sum(n * T for (_, n, T), f in zip(segs, flat) if f)
+        self.lead = (1, self.rows) if axis else segs[0][1:]           # a tensor's shape in front of its channels
+        self._tails, self._stacked = {}, None
+
+    @classmethod
+    def _of_segs(cls, segs, flat, axis):
+        lay = cls.__new__(cls)
+        lay._set(segs, flat, axis)
+        return lay
+
+    _batches = {}
+
+    @classmethod
+    def batch(cls, n, T):
+        """the batch form: one bucket of n sequences of T frames, as an (n, T, C) tensor"""
+        lay = cls._batches.get((n, T))
+        if lay is None:
+            lay = cls._batches[(n, T)] = cls([(n, T, False)], axis=0)
+        return lay
+
+    @classmethod
+    def of(cls, lay, x):
+        """`lay`, or without one the batch form of the (B, T, ...) tensor / mask x"""
+        return lay if lay is not None else cls.batch(x.shape[0], x.shape[1])
 
     def twice(self):
         """segs of the stacked [subject | object] rows"""
         return self.segs + [(self.rows + off, n, T) for off, n, T in self.segs]
+
+    def stacked(self):
+        """the layout of the stacked [subject | object] rows; the two halves of one bucket are one bucket of twice the sequences"""
+        if self._stacked is None:
+            if self.axis == 0:
+                self._stacked = Layout.batch(2 * self.segs[0][1], self.segs[0][2])
+            else:
+                self._stacked = Layout._of_segs(self.twice(), self.flat * 2, 1)
+        return self._stacked
+
+    def strided(self, s):
+        """the layout of the same sequences at every s-th frame"""
+        if s == 1:
+            return self
+        if self.axis == 0:
+            return Layout.batch(self.segs[0][1], self.segs[0][2] // s)
+        return Layout._of_segs([(off // s, n, T // s) for off, n, T in self.segs], self.flat, 1)
+
+    def queries(self, Q):
+        """Q rows per sequence (the predictor's queries), the sequences in the same order"""
+        if self.axis == 0:
+            return Layout.batch(self.segs[0][1], Q)
+        return Layout([(n, Q, False) for _, n, _ in self.segs])
+
+    def min_frames(self):
+        return min(T for _, _, T in self.segs)
 
     def tail_rows(self, halves, device):
         """last row of every sequence of the flat buckets (of both halves of a stacked row space), built ON the device: a table
@@ -66,9 +127,33 @@ class Layout:
             self._tails[key] = (torch.cat(idx) if len(idx) > 1 else idx[0]) if idx else None
         return self._tails[key]
 
+    def new(self, width, like, zeros=False):
+        """a fresh f32 activation of `width` channels in this layout, on the device of `like`"""
+        assert self.axis == 0 or not torch.is_grad_enabled(), "the row space is an inference form: training runs in the batch form"
+        return (torch.zeros if zeros else torch.empty)(*self.lead, width, device=_raw(like).device, dtype=torch.float32)
+
+    def halves(self, x):
+        """the subject and the object half of the tensor x of self.stacked()"""
+        at, R = (slice(None),) * self.axis, self.lead[self.axis]
+        return x[at + (slice(None, R),)], x[at + (slice(R, None),)]
+
+    def part(self, x, seg):
+        """the rows of the group seg = (first row, sequences, frames) of x (tensor, mask, Pair or None) as (sequences, frames, ...);
+        in the batch form the one bucket is the tensor itself"""
+        return x if self.axis == 0 else _part(x, *seg)
+
+    def whole(self, y):
+        """the (sequences, frames, ...) result y of a launch over all rows, in this layout's own form"""
+        if self.axis == 0:
+            return y
+        ops = _ops()
+        if isinstance(y, ops.Pair):
+            return ops.Pair(self.whole(y.t), y.width, y.fmt)
+        return y.view(1, y.shape[0] * y.shape[1], *y.shape[2:])
+
 
 def _part(x, off, n, T):
-    """rows [off, off + n T) of the flat (1, R, C) operand x (tensor, Pair or None) as (n, T, C)"""
+    """rows [off, off + n T) of the flat (1, R, ...) operand x (tensor, mask, Pair or None) as (n, T, ...)"""
     if x is None:
         return None
     ops = _ops()
@@ -77,12 +162,8 @@ def _part(x, off, n, T):
     return x[0, off:off + n * T].unflatten(0, (n, T))
 
 
-def _mpart(m, off, n, T):
-    return None if m is None else m[0, off:off + n * T].view(n, T)
-
-
 def _merged(segs):
-    """buckets of one frame count (the predictor's queries) are one launch"""
+    """buckets of one frame count (the two halves of one bucket, the predictor's queries) are one launch"""
     if len(segs) > 1 and all(T == segs[0][2] for _, _, T in segs):
         return [(segs[0][0], sum(n for _, n, _ in segs), segs[0][2])]
     return segs
@@ -92,52 +173,62 @@ def _raw(x):
     return x.t if isinstance(x, _ops().Pair) else x
 
 
-def _zero_rows(x, rows):
-    """the listed rows of a flat operand (f32 rows or pair rows: all-zero bits are the value zero in both) := 0"""
-    _raw(x)[0].index_fill_(0, rows, 0.0)
-
-
-def _dwconv_rows(x, sets, mask_out, segs, *, stride=1, x_up=None, pre_ln=None):
-    """ops.dwconv_ln over all buckets into joint output buffers; x (1, R, C) f32 rows, x_up the rows of the coarser level.
-    One launch with the buckets as the kernel's row groups (vrd_row_segs)."""
+def _rows_of(x, sl):
     ops = _ops()
-    Cout = sets[0]["weight"].shape[0]
-    rows_out = sum(n * (T // stride) for _, n, T in segs)
-    bufs = [torch.empty(1, rows_out, Cout, device=x.device, dtype=torch.float32) for _ in sets]
-    segs = _merged(segs)
+    return ops.Pair(x.t[:, sl], x.width, x.fmt) if isinstance(x, ops.Pair) else x[:, sl]
+
+
+def dwconv_ln(lay, x, sets, mask_out, *, stride=1, x_up=None, pre_ln=None):
+    """ops.dwconv_ln over the buckets of x's layout `lay`: outputs and mask_out at every stride-th frame, x_up the rows of the
+    coarser level.  One launch: a single group of sequences in the kernel's own form, several as its row groups (vrd_row_segs)."""
+    ops = _ops()
+    segs = _merged(lay.segs)
     if len(segs) == 1:
         off, n, T = segs[0]
-        oo, To = off // stride, T // stride
-        ops.dwconv_ln(_part(x, off, n, T), [dict(st, out=_part(b, oo, n, To)) for st, b in zip(sets, bufs)],
-                      mask_out=_mpart(mask_out, oo, n, To), stride=stride, x_up=_part(x_up, off // 2, n, T // 2), pre_ln=pre_ln)
-    else:
-        for g0 in range(0, len(segs), _MAX_SEGS):
-            part = segs[g0:g0 + _MAX_SEGS]
-            r0, r1 = part[0][0], part[-1][0] + part[-1][1] * part[-1][2]
-            rel = [(off - r0, n, T) for off, n, T in part]
-            ops.dwconv_ln(x[:, r0:r1], [dict(st, out=b[:, r0 // stride:r1 // stride]) for st, b in zip(sets, bufs)],
-                          mask_out=None if mask_out is None else mask_out[:, r0 // stride:r1 // stride], stride=stride,
-                          x_up=None if x_up is None else x_up[:, r0 // 2:r1 // 2], pre_ln=pre_ln, segs=rel)
+        res = ops.dwconv_ln(lay.part(x, segs[0]), sets, mask_out=lay.part(mask_out, (off // stride, n, T // stride)), stride=stride,
+                            x_up=lay.part(x_up, (off // 2, n, T // 2)), pre_ln=pre_ln)
+        return [lay.whole(r) for r in res]
+    Cout = sets[0]["weight"].shape[0]
+    bufs = [torch.empty(1, lay.rows // stride, Cout, device=x.device, dtype=torch.float32) for _ in sets]
+    for g0 in range(0, len(segs), _MAX_SEGS):
+        part = segs[g0:g0 + _MAX_SEGS]
+        r0, r1 = part[0][0], part[-1][0] + part[-1][1] * part[-1][2]
+        rel = [(off - r0, n, T) for off, n, T in part]
+        ops.dwconv_ln(x[:, r0:r1], [dict(st, out=b[:, r0 // stride:r1 // stride]) for st, b in zip(sets, bufs)],
+                      mask_out=None if mask_out is None else mask_out[:, r0 // stride:r1 // stride], stride=stride,
+                      x_up=None if x_up is None else x_up[:, r0 // 2:r1 // 2], pre_ln=pre_ln, segs=rel)
     return [ops.Pair(b, Cout) if ops._fmt(st.get("pair")) else b for st, b in zip(sets, bufs)]
 
 
-def _attention_rows(q, k, v, kv_mask, q_mask, n_head, qsegs, ksegs, *, half_win=None, rel_pe=None, pair=False, plain=False):
-    """global (half_win None) or banded attention bucket by bucket; plain: MaskedMHA's call form (f32 rows in and out)."""
+def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False):
+    """Global (half_win None) or banded attention of the queries in `qlay` over the keys in `klay`, bucket by bucket.
+    q_mask: rows the caller masks afterwards (global attention only)."""
     ops = _ops()
-    Cc = q.shape[-1]
-    out = torch.empty(1, sum(n * T for _, n, T in qsegs), Cc, device=_raw(q).device, dtype=torch.float32)
-    r = None
-    # buckets of one frame count on both sides (the predictor's query self-attention: every segment is n x Q rows) are one launch
-    if len(qsegs) > 1 and len(_merged(qsegs)) == 1 and len(_merged(ksegs)) == 1:
+    qsegs, ksegs = qlay.segs, klay.segs
+    # buckets of one frame count on both sides (the predictor's query self-attention: every bucket is n x Q rows) are one launch
+    if len(_merged(qsegs)) == 1 and len(_merged(ksegs)) == 1:
         qsegs, ksegs = _merged(qsegs), _merged(ksegs)
-    if half_win is not None and 1 < len(qsegs) <= _MAX_SEGS:      # banded attention: the buckets as the kernel's row groups
+
+    def one(qs, ks, out=None):
+        assert qs[1] == ks[1]
+        qp, kp, vp, mp = qlay.part(q, qs), klay.part(k, ks), klay.part(v, ks), klay.part(kv_mask, ks)
+        if half_win is not None:
+            assert qs[2] == ks[2]
+            return ops.local_attention(qp, kp, vp, mp, n_head, half_win, pair=pair, rel_pe=rel_pe, out=out)
+        return ops.attention(qp, kp, vp, mp, n_head, pair=pair, q_mask=qlay.part(q_mask, qs), out=out)
+
+    if len(qsegs) == 1:
+        return qlay.whole(one(qsegs[0], ksegs[0]))
+    Cc = q.shape[-1]
+    dev = _raw(q).device
+    out = torch.empty(1, qlay.rows, Cc, device=dev, dtype=torch.float32)
+    if half_win is not None and len(qsegs) <= _MAX_SEGS:      # banded attention: the buckets as the kernel's row groups
         assert list(qsegs) == list(ksegs)
         r = ops.local_attention(q, k, v, kv_mask, n_head, half_win, pair=pair, rel_pe=rel_pe, out=out, segs=list(qsegs))
         return ops.Pair(out, Cc, r.fmt) if isinstance(r, ops.Pair) else out
     # global attention walks the buckets; a bucket's launch is n x heads x query blocks workgroups of one per CU -- 4.02 rounds
     # of the chip for 257 pairs x 4 heads take five --, so the buckets' launches alternate between ATTN_LANES streams and fill
     # each other's last rounds
-    dev = _raw(q).device
     lanes = _lanes(dev) if half_win is None and len(qsegs) > 2 else None
     if lanes:
         main = torch.cuda.current_stream(dev)
@@ -145,35 +236,14 @@ def _attention_rows(q, k, v, kv_mask, q_mask, n_head, qsegs, ksegs, *, half_win=
         ready.record(main)
         for lane in lanes:
             lane.wait_event(ready)
-    for i, ((qo, n, Tq), (ko, nk, Tk)) in enumerate(zip(qsegs, ksegs)):
-        assert n == nk
-        o = _part(out, qo, n, Tq)
-        if lanes and i % (len(lanes) + 1):
-            with torch.cuda.stream(lanes[i % (len(lanes) + 1) - 1]):
-                r = _attention_one(q, k, v, kv_mask, q_mask, n_head, (qo, n, Tq), (ko, nk, Tk), o, pair, plain)
-            continue
-        if half_win is not None:
-            assert Tq == Tk
-            r = ops.local_attention(_part(q, qo, n, Tq), _part(k, ko, n, Tk), _part(v, ko, n, Tk), _mpart(kv_mask, ko, n, Tk),
-                                    n_head, half_win, pair=pair, rel_pe=rel_pe, out=o)
-        elif plain:
-            r = ops.attention(_part(q, qo, n, Tq), _part(k, ko, n, Tk), _part(v, ko, n, Tk), _mpart(kv_mask, ko, n, Tk), n_head, out=o)
-        else:
-            r = ops.attention(_part(q, qo, n, Tq), _part(k, ko, n, Tk), _part(v, ko, n, Tk), _mpart(kv_mask, ko, n, Tk), n_head,
-                              pair=pair, q_mask=_mpart(q_mask, qo, n, Tq), out=o)
+    for i, (qs, ks) in enumerate(zip(qsegs, ksegs)):
+        at = i % (len(lanes) + 1) if lanes else 0
+        with torch.cuda.stream(lanes[at - 1]) if at else nullcontext():
+            r = one(qs, ks, _part(out, *qs))
     if lanes:
         for lane in lanes:
             main.wait_stream(lane)
     return ops.Pair(out, Cc, r.fmt) if isinstance(r, ops.Pair) else out
-
-
-def _attention_one(q, k, v, kv_mask, q_mask, n_head, qseg, kseg, o, pair, plain):
-    ops = _ops()
-    (qo, n, Tq), (ko, _, Tk) = qseg, kseg
-    if plain:
-        return ops.attention(_part(q, qo, n, Tq), _part(k, ko, n, Tk), _part(v, ko, n, Tk), _mpart(kv_mask, ko, n, Tk), n_head, out=o)
-    return ops.attention(_part(q, qo, n, Tq), _part(k, ko, n, Tk), _part(v, ko, n, Tk), _mpart(kv_mask, ko, n, Tk), n_head,
-                         pair=pair, q_mask=_mpart(q_mask, qo, n, Tq), out=o)
 
 
 ATTN_LANES = int(__import__("os").environ.get("VRDONE_ROWS_ATTN_STREAMS", "2"))      # streams the buckets' global attention alternates between
@@ -190,138 +260,66 @@ def _lanes(dev):
     return _side_streams[key]
 
 
-def _attn_rows(mod, q_in, k_in, v_in, q_mask, kv_mask, qsegs, ksegs, *, stride=1, pre_ln=None, pre_ln_on="", **epilogue):
-    """An attention module's cl / cl_qkv on flat rows (blocks.py LocalMaskedMHCA.cl / MaskedMHCA.cl with stride, q_mask =
-    kv_mask = the strided mask; local_transformer.py MaskedMHCA_QKV.cl_qkv; blocks.py MaskedMHA.cl_qkv)."""
+def maxpool_mask(lay, x, mask):
+    """ops.maxpool_mask (the pyramid's stride-2 skip path) bucket by bucket -> (pooled rows, mask) in lay.strided(2)"""
     ops = _ops()
-    if stride > 1:
-        qsegs_o = ksegs_o = [(off // stride, n, T // stride) for off, n, T in qsegs]
-    else:
-        qsegs_o, ksegs_o = qsegs, ksegs
-    if isinstance(mod, _ConvAttention):
-        outs = {}
-        for x, m, use_ln, _, names in mod._groups(q_in, k_in, v_in, q_mask, kv_mask, pre_ln, pre_ln_on):
-            res = _dwconv_rows(x, [mod._branch_set(nm) for nm in names], m, qsegs if x is q_in else ksegs, stride=stride,
-                               pre_ln=pre_ln if use_ln else None)
-            outs.update(zip(names, res))
-        q, k, v = outs["query"], outs["key"], outs["value"]
-        half_win = getattr(mod, "_half_win", None)
-        if half_win is None and hasattr(mod, "window_overlap"):
-            half_win = mod.window_overlap                                              # blocks.py LocalMaskedMHCA
-        # (the flash kernel's pair-row q / k / v: one choice for all buckets)
-        qkv_pair = half_win is None and ops.flash_pair_ok(mod.n_head, mod.n_embd, min(T for _, _, T in qsegs_o))
-        q, k, v = mod._project(q, k, v, out_pair=qkv_pair, q_mask=q_mask, kv_mask=kv_mask)
-        att = _attention_rows(q, k, v, kv_mask, q_mask, mod.n_head, qsegs_o, ksegs_o, half_win=half_win,
-                              rel_pe=getattr(mod, "rel_pe", None), pair=ops.pair_mode())
-    else:                                                                              # blocks.py MaskedMHA.cl_qkv
-        q = ops.conv_gemm(q_in, mod.query.weight, mod.query.bias)
-        k = ops.conv_gemm(k_in, mod.key.weight, mod.key.bias)
-        v = ops.conv_gemm(v_in, mod.value.weight, mod.value.bias)
-        att = _attention_rows(q, k, v, kv_mask, None, mod.n_head, qsegs_o, ksegs_o, plain=True)
-    return ops.conv_gemm(att, mod.proj.weight, mod.proj.bias, row_mask=q_mask, **epilogue)
+    if len(lay.segs) == 1:
+        y, m_out = ops.maxpool_mask(lay.part(x, lay.segs[0]), lay.part(mask, lay.segs[0]))
+        return lay.whole(y), lay.whole(m_out)
+    y = torch.empty(1, lay.rows // 2, x.shape[-1], device=x.device, dtype=torch.float32)
+    m_out = torch.empty(1, lay.rows // 2, device=x.device, dtype=torch.bool)
+    for off, n, T in lay.segs:
+        ops.maxpool_mask(_part(x, off, n, T), _part(mask, off, n, T), out=(_part(y, off // 2, n, T // 2), _part(m_out, off // 2, n, T // 2)))
+    return y, m_out
 
 
-def _block(blk, x, mask, segs, out=None):
-    """blocks.py TransformerBlock.cl (eval: no stochastic depth) -> (y, mask_out, segs_out)"""
-    ops = _ops()
-    s = blk.attn.n_kv_stride
-    if s > 1:
-        assert s == 2
-        rows_o = sum(n * (T // 2) for _, n, T in segs)
-        skip = torch.empty(1, rows_o, x.shape[-1], device=x.device, dtype=torch.float32)
-        m_out = torch.empty(1, rows_o, device=x.device, dtype=torch.bool)
-        for off, n, T in segs:
-            ops.maxpool_mask(_part(x, off, n, T), _mpart(mask, off, n, T), out=(_part(skip, off // 2, n, T // 2), _mpart(m_out, off // 2, n, T // 2)))
-        segs_o = [(off // 2, n, T // 2) for off, n, T in segs]
-    else:
-        skip, m_out, segs_o = x, mask, segs
-    y = _attn_rows(blk.attn, x, x, x, m_out, m_out, segs, segs, stride=s, pre_ln=(blk.ln1.weight, blk.ln1.bias), pre_ln_on="qkv",
-                   scale=blk._scale(blk.drop_path_attn), res=skip, res_masked=True)
-    h = blk.ln2.cl(y, pair=ops.pair_mode())
-    h = ops.conv_gemm(h, blk.mlp[0].weight, blk.mlp[0].bias, act=ops.ACT_GELU, out_pair=ops.pair_mode(), skip_rows=m_out)
-    y = ops.conv_gemm(h, blk.mlp[3].weight, blk.mlp[3].bias, row_mask=m_out, scale=blk._scale(blk.drop_path_mlp), res=y, out=out)
-    return y, m_out, segs_o
-
-
-def _decoder_layer(layer, tgt, memory, tgt_mask, memory_mask, qsegs, ksegs, *, query_pos=None, stream_add=None, out=None):
-    """local_transformer.py MaskedConvTransformerDecoderLayer.cl (eval) on flat rows"""
-    ops = _ops()
-    from .local_transformer import MaskedMHCA_QKV
-    fuse1 = query_pos is None and isinstance(layer.self_attn, MaskedMHCA_QKV)
-    fuse2 = query_pos is None and isinstance(layer.multihead_attn, MaskedMHCA_QKV)
-    last = not layer.with_ffn
-    kw1 = dict(scale=layer._scale(layer.drop_path_attn1), res=tgt, res_masked=True)
-    if fuse1:
-        tgt = _attn_rows(layer.self_attn, tgt, tgt, tgt, tgt_mask, tgt_mask, qsegs, qsegs, pre_ln=(layer.ln1.weight, layer.ln1.bias),
-                         pre_ln_on="qk", **kw1)
-    else:
-        t2 = layer.ln1.cl(tgt, post_add=query_pos)
-        tgt = _attn_rows(layer.self_attn, t2, t2, tgt, tgt_mask, tgt_mask, qsegs, qsegs, **kw1)
-    kw = dict(scale=layer._scale(layer.drop_path_attn2), res=tgt, res_masked=True, res2=stream_add if last else None,
-              out=out if last else None)
-    if fuse2:
-        tgt = _attn_rows(layer.multihead_attn, tgt, memory, memory, tgt_mask, memory_mask, qsegs, ksegs,
-                         pre_ln=(layer.ln2.weight, layer.ln2.bias), pre_ln_on="q", **kw)
-    else:
-        t2 = layer.ln2.cl(tgt, post_add=query_pos)
-        tgt = _attn_rows(layer.multihead_attn, t2, memory, memory, tgt_mask, memory_mask, qsegs, ksegs, **kw)
-    if layer.with_ffn:
-        assert stream_add is None
-        t2 = layer.ln3.cl(tgt)
-        h = ops.conv_gemm(t2, layer.mlp[0].weight, layer.mlp[0].bias, act=ops.ACT_GELU)
-        tgt = ops.conv_gemm(h, layer.mlp[3].weight, layer.mlp[3].bias, row_mask=tgt_mask, scale=layer._scale(layer.drop_path_mlp),
-                            res=tgt, out=out)
-    return tgt
-
-
-def _rows_of(x, sl):
-    ops = _ops()
-    return ops.Pair(x.t[:, sl], x.width, x.fmt) if isinstance(x, ops.Pair) else x[:, sl]
-
-
-def _conv3_rows(h, conv, row_mask, lay, halves, tails, out=None, out_pair=False, norm=None):
-    """A dense k = 3 conv * mask over the row space: one flat launch per half over the rows of the buckets whose sequences end
-    in two padded frames (their last rows zeroed in the input first), bucket by bucket for the others.
+def conv3(lay, h, conv, row_mask, *, out=None, out_pair=False, norm=None):
+    """A dense k = 3 conv * mask over the sequences of `lay`.  In a row space: one flat launch per run of buckets whose sequences
+    end in two padded frames (their last rows zeroed in the input first), bucket by bucket for the others.
     norm: the LayerNorm (+ ReLU) behind a few-channel conv, fused into the same launches (ops.conv_ln); with few input channels
     and no norm the conv alone runs as that row kernel."""
     ops = _ops()
     assert conv.kernel_size[0] == 3
-    N = conv.weight.shape[0]
-    if out is None:
-        out = torch.empty(1, halves * lay.rows, N, device=_raw(h).device, dtype=torch.float32)
-    if tails is not None:
-        _zero_rows(h, tails)
+    ln = {} if norm is None else dict(gamma=norm.weight.reshape(-1), beta=norm.bias.reshape(-1), relu=True)
     small = ops.conv_ln_ok(h, conv.weight, conv.bias, *((norm.weight, norm.bias) if norm is not None else ()))
     assert small or norm is None
 
     def one(x, m, o):
         if small:
-            ops.conv_ln(x, conv.weight, conv.bias, row_mask=m, out=o, pair=out_pair, relu=norm is not None,
-                        gamma=None if norm is None else norm.weight.reshape(-1), beta=None if norm is None else norm.bias.reshape(-1))
-        else:
-            ops.conv_gemm(x, conv.weight, conv.bias, row_mask=m, out=o, out_pair=out_pair)
-    for hf in range(halves):
-        base = hf * lay.rows
-        if lay.rows_flat:
-            sl = slice(base, base + lay.rows_flat)
+            return ops.conv_ln(x, conv.weight, conv.bias, row_mask=m, out=o, pair=out_pair, **ln)
+        return ops.conv_gemm(x, conv.weight, conv.bias, row_mask=m, out=o, out_pair=out_pair)
+    if lay.axis == 0:
+        return one(h, row_mask, out)
+    N = conv.weight.shape[0]
+    if out is None:
+        out = lay.new(N, h)
+    tails = lay.tail_rows(1, _raw(h).device)
+    if tails is not None:
+        _raw(h)[0].index_fill_(0, tails, 0.0)            # (f32 rows or pair rows: all-zero bits are the value zero in both)
+    at = 0
+    while at < len(lay.segs):
+        off, n, T = lay.segs[at]
+        if lay.flat[at]:
+            while at + 1 < len(lay.segs) and lay.flat[at + 1]:
+                at += 1
+            sl = slice(off, lay.segs[at][0] + lay.segs[at][1] * lay.segs[at][2])
             one(_rows_of(h, sl), row_mask[:, sl], out[:, sl])
-        for (off, n, T), flat in zip(lay.segs, lay.flat):
-            if not flat:
-                one(_part(h, base + off, n, T), _mpart(row_mask, base + off, n, T), _part(out, base + off, n, T))
+        else:
+            one(_part(h, off, n, T), _part(row_mask, off, n, T), _part(out, off, n, T))
+        at += 1
     return ops.Pair(out, N) if out_pair else out
 
 
-def _embed(h, convs, norms, mask2, out, lay, tails2):
-    """backbones.py _embed on the stacked rows: k = 3 conv * mask -> LN -> ReLU"""
+def mask_head(lay, emb, feat, out_mask, fill):
+    """ops.mask_head bucket by bucket: emb (B, Q, Dp) of all pairs in bucket order -> [mask logits (n_i, Q, T_i) per bucket]"""
     ops = _ops()
-    last = len(convs) - 1
-    if last == 0 and ops.conv_ln_ok(h, convs[0].conv.weight, convs[0].conv.bias, norms[0].weight, norms[0].bias):
-        # few input channels (the box features): conv, mask, LayerNorm and ReLU as one row kernel, straight into the consumer's slab
-        return _conv3_rows(h, convs[0].conv, mask2, lay, 2, tails2, out=out, out_pair=bool(ops.pair_mode()), norm=norms[0])
-    for i, (conv, norm) in enumerate(zip(convs, norms)):
-        h = _conv3_rows(h, conv.conv, mask2, lay, 2, tails2)
-        h = norm.cl(h, relu=True, out=out if i == last else None, pair=ops.pair_mode())
-    return h
+    if len(lay.segs) == 1:
+        return [ops.mask_head(emb, lay.part(feat, lay.segs[0]), lay.part(out_mask, lay.segs[0]), fill)]
+    segs_out, p = [], 0
+    for off, n, T in lay.segs:
+        segs_out.append(ops.mask_head(emb[p:p + n], _part(feat, off, n, T), _part(out_mask, off, n, T), fill))
+        p += n
+    return segs_out
 
 
 def unpack_rows(bb, x, plan, lay):
@@ -331,10 +329,9 @@ def unpack_rows(bb, x, plan, lay):
     R = lay.rows
     V, Cc, S, E = bb.n_visual, bb.n_clip, bb.n_bbox_so, bb.n_bbox_entity
     pair = ops.pair_mode()
-    new = lambda rows, width: torch.empty(1, rows, width, device=x.device, dtype=torch.float32)      # noqa: E731
 
     def stacked(c0, width, as_pair):
-        h = new(2 * R, width)
+        h = lay.stacked().new(width, x)
         for (off, n, T), bucket in zip(lay.segs, plan):
             t2, idx = bucket[0], bucket[1]
             ops.bct_to_btc(x, c0, width, _part(h, off, n, T), pair=as_pair, frames=t2, index=idx)
@@ -342,141 +339,17 @@ def unpack_rows(bb, x, plan, lay):
         return ops.Pair(h, width) if as_pair else h
 
     o0 = 2 * V + 2 * Cc
-    so_box = new(R, S)
+    so_box = lay.new(S, x)
     for (off, n, T), bucket in zip(lay.segs, plan):
         ops.bct_to_btc(x, o0, S, _part(so_box, off, n, T), frames=bucket[0], index=bucket[1])
     return stacked(0, V, pair), (stacked(2 * V, Cc, pair) if Cc else None), so_box, stacked(o0 + S, E, False)
 
 
-def entity_rows(bb, vis, clip, ent, mask2, lay):
-    """backbones.py entity_stage on the stacked rows (1, 2R, .) -> so (1, 2R, D)"""
-    ops = _ops()
-    assert not bb.use_abs_pe, "absolute position rows are laid out per padded length: such models run bucket by bucket"
-    dev = mask2.device
-    R = lay.rows
-    D = bb.s_fuse_norm.num_channels
-    pair = ops.pair_mode()
-    new = lambda rows, width: torch.empty(1, rows, width, device=dev, dtype=torch.float32)      # noqa: E731
-    cat = (lambda t: ops.Pair(t, D)) if pair else (lambda t: t)                                   # noqa: E731
-    tails2 = lay.tail_rows(2, dev)
-    fuse_in = new(2 * R, 2 * D)
-    if bb.n_clip:
-        vc = new(2 * R, 2 * D)
-        _embed(vis, bb.visual_embd, bb.visual_embd_norm, mask2, vc[..., :D], lay, tails2)
-        _embed(clip, bb.clip_embd, bb.clip_embd_norm, mask2, vc[..., D:], lay, tails2)
-        bb.visual_clip_fuse.cl(cat(vc), row_mask=mask2, out=fuse_in[..., :D], out_pair=pair)
-    else:
-        _embed(vis, bb.visual_embd, bb.visual_embd_norm, mask2, fuse_in[..., :D], lay, tails2)
-    _embed(ent, [bb.bbox_entity_embd], [bb.bbox_entity_norm], mask2, fuse_in[..., D:], lay, tails2)
-    so = bb.visual_bbox_fuse.cl(cat(fuse_in), row_mask=mask2)
-    so, _, _ = _block(bb.stem[0], so, mask2, lay.twice())
-    return so
-
-
-def pair_rows(bb, so, so_box, mask, lay):
-    """backbones.py pair_stage: so (1, 2R, D) entity-stage rows [subject | object], so_box (1, R, S), mask (1, R)
-    -> feats, masks, segs per pyramid level"""
-    ops = _ops()
-    dev = mask.device
-    R = lay.rows
-    D = bb.s_fuse_norm.num_channels
-    pair = ops.pair_mode()
-    segs, segs2 = lay.segs, lay.twice()
-    new = lambda rows, width: torch.empty(1, rows, width, device=dev, dtype=torch.float32)      # noqa: E731
-    cat = (lambda t: ops.Pair(t, D)) if pair else (lambda t: t)                                   # noqa: E731
-    mask2 = torch.cat([mask, mask], dim=1)
-    for i, (s_attn, o_attn) in enumerate(zip(bb.s_attn, bb.o_attn)):
-        if i:
-            so, _, _ = _block(bb.stem[i], so, mask2, segs2)
-        s, o = so[:, :R], so[:, R:]
-        nxt = new(2 * R, D)
-        _decoder_layer(s_attn, s, o, mask, mask, segs, segs, stream_add=s, out=nxt[:, :R])        # s + s_attn(s, o)
-        _decoder_layer(o_attn, o, s, mask, mask, segs, segs, stream_add=o, out=nxt[:, R:])        # uses the pre-update s
-        so = nxt
-    so_in = new(R, 2 * D)
-    bb.s_fuse_norm.cl(so[:, :R], out=so_in[..., :D], pair=pair)
-    bb.o_fuse_norm.cl(so[:, R:], out=so_in[..., D:], pair=pair)
-    pair_box = new(R, 2 * D)
-    bb.so_fuse.cl(cat(so_in), row_mask=mask, out=pair_box[..., :D], out_pair=pair)
-    _conv3_rows(so_box, bb.bbox_so_embd.conv, mask, lay, 1, lay.tail_rows(1, dev), out=pair_box[..., D:], out_pair=pair)
-    e = bb.so_visual_bbox_fuse.cl(cat(pair_box), row_mask=mask)
-
-    feats, masks, lays = [e], [mask], [segs]
-    for blk in bb.branch:
-        e, mask, segs = _block(blk, e, mask, segs)
-        feats.append(e)
-        masks.append(mask)
-        lays.append(segs)
-    return feats, masks, lays
-
-
 def backbone_rows(bb, x, plan, lay, mask):
     """backbones.py cl for the buckets of `plan` over the caller's batch x (B, C_in, T); mask: flat (1, R) validity of the rows"""
     vis, clip, so_box, ent = unpack_rows(bb, x, plan, lay)
-    so = entity_rows(bb, vis, clip, ent, torch.cat([mask, mask], dim=1), lay)
-    return pair_rows(bb, so, so_box, mask, lay)
-
-
-def neck_rows(neck, feats, masks, lays):
-    """fpns.py FPN1D_Fuse.cl"""
-    ops = _ops()
-    y = None
-    for l in range(len(neck.lateral_convs) - 1, -1, -1):
-        x = neck.input_norms[l].cl(feats[l], pair=ops.pair_mode() and neck.lateral_convs[l] is not None)
-        fpn = dict(weight=neck.fpn_convs[l].conv.weight, gamma=neck.fpn_norms[l].weight, beta=neck.fpn_norms[l].bias)
-        if neck.lateral_convs[l] is None:
-            y, = _dwconv_rows(x, [fpn], masks[l], lays[l])
-        else:
-            c = ops.conv_gemm(x, neck.lateral_convs[l].conv.weight, None, row_mask=masks[l])
-            c = neck.lateral_norms[l].cl(c)
-            y, = _dwconv_rows(c, [fpn], masks[l], lays[l], x_up=y)
-    mf = neck.mask_features.conv
-    out, = _dwconv_rows(y, [dict(weight=mf.weight, bias=mf.bias)], masks[0], lays[0])
-    return out
-
-
-def predictor_rows(pred, x, mask_features, mask, output_mask, ksegs, segs0, with_aux, fill=-10.0):
-    """predictor.py MaskedTransformerPredictor.cl: the queries of all pairs are one (B, Q, C) tensor (pairs in bucket
-    order); the decoder's cross attention and the mask head walk the buckets.  -> [(logits (B, Q, K+1), [seg_i (n_i, Q, T_i)])]
-    for the last decoder layer, preceded by the auxiliary layers' when asked for."""
-    ops = _ops()
-    if with_aux is None:
-        with_aux = pred.aux_loss
-    src = pred.input_norm.cl(x, pair=ops.pair_mode() and pred.input_proj is not None)
-    if pred.input_proj is not None:
-        src = ops.conv_gemm(src, pred.input_proj.weight, pred.input_proj.bias, row_mask=mask)
-    qe = pred.query_embed.weight
-    Q, Cq = qe.shape
-    B = sum(n for _, n, _ in ksegs)
-    qsegs, p = [], 0
-    for _, n, _ in ksegs:
-        qsegs.append((p * Q, n, Q))
-        p += n
-    dec = pred.transformer.decoder
-    tgt = torch.zeros(1, B * Q, Cq, device=_raw(src).device, dtype=torch.float32)
-    hs = []
-    all_layers = with_aux and pred.aux_loss
-    for i, layer in enumerate(dec.layers):
-        tgt = _decoder_layer(layer, tgt, src, None, mask, qsegs, ksegs, query_pos=qe)
-        if all_layers or i == dec.num_layers - 1:
-            hs.append(dec.norm.cl(tgt))
-    heads = []
-    for h in hs:
-        h3 = h.view(B, Q, Cq)
-        logits = ops.conv_gemm(h3, pred.class_embed.weight, pred.class_embed.bias)
-        emb = pred.mask_embed.cl(h3)
-        segs_out, p = [], 0
-        for off, n, T in segs0:
-            segs_out.append(ops.mask_head(emb[p:p + n], _part(mask_features, off, n, T), _mpart(output_mask, off, n, T), fill))
-            p += n
-        heads.append((logits, segs_out))
-    return heads
-
-
-def heads_rows(model, feats, masks, lays, with_aux):
-    """neck + predictor over the row space -> [(logits (B, Q, K+1), [mask logits (n_i, Q, T_i) per bucket])] per decoder layer asked for"""
-    mask_features = neck_rows(model.neck, feats, masks, lays)
-    return predictor_rows(model.predictor, feats[-1], mask_features, masks[-1], masks[0], lays[-1], lays[0], with_aux)
+    so = bb.entity_stage(vis, clip, ent, torch.cat([mask, mask], dim=1), lay.stacked())
+    return bb.pair_stage(so, so_box, mask, lay)
 
 
 def filler_buckets(rows, t_max):
@@ -520,7 +393,7 @@ def mask_vrd_rows(model, x, masks2d, plan, with_aux, out=None):
     idx64 = [b[1].long() for b in plan]
     mask = torch.cat([masks2d[i64, :b[0]].reshape(-1) if j not in filler else torch.zeros(b[2] * b[0], dtype=torch.bool, device=dev)
                       for j, (b, i64) in enumerate(zip(plan, idx64))]).view(1, lay.rows)
-    heads = heads_rows(model, *backbone_rows(model.backbone, x, plan, lay, mask), with_aux)
+    heads = model._heads(*backbone_rows(model.backbone, x, plan, lay, mask), with_aux, lay)
     fill = -10.0                                        # the predictor's value on padded frames (predictor.py:39)
     if out is None:
         Q, K1 = heads[-1][0].shape[1:]
