@@ -1,9 +1,10 @@
 """Lab aid: what one bucket of forward_test costs eagerly and as a recorded HIP graph (vrdone_amd/eval_graph.py):
-wall time per call of MaskVRD._bucket_candidates for a few (T, pairs), eager against graph.replay(), and the graphs' node counts."""
+wall time per call of eval_batches.bucket_candidates for a few (T, pairs), eager against graph.replay(), and the graphs' node counts."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from vrdone_amd import configs, eval_graph, ops, synth
+from vrdone_amd.models import eval_batches
 from vrdone_amd.models.maskvrd import MaskVRD
 
 dev = torch.device("cuda:0")
@@ -28,7 +29,7 @@ with torch.no_grad():
                 fn()
             torch.cuda.synchronize()
             return 1e3 * (time.perf_counter() - t0) / reps
-        eager = timed(lambda: model._bucket_candidates(table, lens, T, k))
+        eager = timed(lambda: eval_batches.bucket_candidates(model, table, lens, T, k))
         rec = eval_graph._Recording(model, T, eval_graph.pad_size(n), k, c_in)
         replay = timed(lambda: rec(table, lens))
         bare = timed(lambda: rec.graph.replay())
@@ -42,10 +43,10 @@ with torch.no_grad():
     mats = [torch.randn(T - 3 - i % 7, c_in, device=dev, generator=g) for i in range(n)]
     table = torch.tensor([m.data_ptr() for m in mats], dtype=torch.int64, device=dev)
     lens = torch.tensor([m.shape[0] for m in mats], dtype=torch.int32, device=dev)
-    model._bucket_candidates(table, lens, T, k)
+    eval_batches.bucket_candidates(model, table, lens, T, k)
     torch.cuda.synchronize()
     _hip.prof_enable(True); _hip.prof_reset()
-    model._bucket_candidates(table, lens, T, k)
+    eval_batches.bucket_candidates(model, table, lens, T, k)
     torch.cuda.synchronize()
     _hip.prof_enable(False)
     pr = _hip.prof_read()

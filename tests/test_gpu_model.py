@@ -1055,7 +1055,9 @@ def _prefix_masks(lens, T):
 def launch_cases():
     """{name: run() -> outputs}: the smallest calls that reach every operation of the network that needs the (sequences, frames)
     structure, in the batch form, in the row space (global and banded subject-object attention, forward_test with the shared
-    tracklet rows) and as one training step."""
+    tracklet rows) and as one training step; and every eval batching path (models/eval_batches.py): forward_test bucket by
+    bucket and in the row space, from per-pair matrices and from tracklets (entity stage shared or not), in waves that cut
+    through buckets, _mask_vrd bucket by bucket, and forward_test_videos."""
     from oracle.synth import synth_relations
     from vrdone_amd import synth
     from vrdone_amd.proposals import prepare_test_proposal
@@ -1077,16 +1079,46 @@ def launch_cases():
                 model.__dict__.pop("ROWS_MIN_ROWS", None)
         return run
 
-    def forward_test():
+    def mask_vrd_tight():
+        model, mc, _, _ = get_model("vidvrd")
+        lens = [5, 17, 24, 24, 25, 40, 56, 33, 57, 94, 95, 96]
+        x, m = O.synth_pairs(len(lens), c_in(mc), 96, lens, seed=41)
+        xd, md = x.to(DEV), m.to(DEV)
+
+        def run():
+            try:
+                model.row_space, model.TIGHT_MIN_ROWS = False, 64           # (buckets this small only here)
+                plan = model._tight_plan(md, md.reshape(len(lens), 96))
+                assert not plan["rows"] and [(t, n) for t, _, n, _ in plan["buckets"]] == [(32, 4), (64, 4), (96, 4)], plan
+                return model._mask_vrd(xd, md)
+            finally:
+                del model.row_space, model.TIGHT_MIN_ROWS
+        return run
+
+    def forward_test(tracklets, min_pairs=None, chunk=None, share=True, videos=False, min_rows=None):
         model, mc, ic, _ = get_model("vidvrd")
-        raw = synth.synth_raw_video(8, mc["visual_dim"], 60, 250, seed=11)
-        prop = prepare_test_proposal(raw, ic["feat_stride"], 0, 2, torch.device(DEV))
-        try:
-            model.ROWS_MIN_PAIRS = 8
-            assert model._eval_rows_form(len(prop["pair_source"])) and model.share_tracklets
-            return model(prop)
-        finally:
-            del model.ROWS_MIN_PAIRS
+        if tracklets:
+            data = [prepare_test_proposal(synth.synth_raw_video(8, mc["visual_dim"], 60, 250, seed=seed), ic["feat_stride"], 0, 2,
+                                          torch.device(DEV)) for seed in ((11, 13) if videos else (11,))]
+        else:
+            data = [synth.synth_video(8, c_in(mc), 10, 60, seed=3, device=DEV)]
+            assert len(data[0]["sids"]) == 48
+
+        def run():
+            old_chunk = model.pair_chunk
+            try:
+                if min_pairs:
+                    model.ROWS_MIN_PAIRS = min_pairs
+                if min_rows:
+                    model.ROWS_MIN_ROWS = min_rows
+                model.pair_chunk, model.share_tracklets = chunk or old_chunk, share
+                assert model._eval_rows_form(len(data[0]["sids"])) == bool(min_pairs)
+                return model.forward_test_videos(data) if videos else model(data[0])
+            finally:
+                model.__dict__.pop("ROWS_MIN_PAIRS", None)
+                model.__dict__.pop("ROWS_MIN_ROWS", None)
+                model.pair_chunk, model.share_tracklets = old_chunk, True
+        return run
 
     def train_step():
         model, mc, _, _ = get_model("vidvrd")
@@ -1114,8 +1146,17 @@ def launch_cases():
         "rows_banded": mask_vrd("vidor_local", 512, [5, 24, 25, 56, 57, 120, 121, 400, 510, 511, 512, 300], 64,
                                 [(32, 2, True), (64, 2, True), (96, 1, True), (128, 1, True), (160, 1, True), (320, 1, True),
                                  (416, 1, True), (512, 1, True), (512, 2, False)]),
-        "forward_test_rows": forward_test,
+        "forward_test_rows": forward_test(True, min_pairs=8),
         "train_step": train_step,
+        "forward_test_buckets": forward_test(False),
+        "forward_test_matrices_rows": forward_test(False, min_pairs=8),
+        "forward_test_matrices_waves": forward_test(False, min_pairs=8, chunk=24),        # two waves of 24, one padded length
+        # 24 pairs at 32 frames and 24 at 64 in three waves of 16: the second wave takes the end of one bucket and the start of the next
+        "forward_test_matrices_cut_buckets": forward_test(False, min_pairs=8, chunk=20, min_rows=64),
+        "forward_test_tracklets_buckets": forward_test(True),
+        "forward_test_tracklets_unshared": forward_test(True, share=False),
+        "mask_vrd_tight": mask_vrd_tight(),
+        "forward_test_videos": forward_test(True, videos=True),
     }
 
 
@@ -1133,6 +1174,23 @@ LAUNCHES = {
                           "mask_head": 5, "maxpool_mask": 15, "postprocess": 5, "transpose": 12},
     "train_step": {"attn_flash": 16, "backward": 581, "dwconv_ln": 34, "gemm_f32_mfma": 6, "gemm_x3_mfma": 254, "layernorm": 102,
                    "local_attn": 5, "mask_head": 4, "maxpool_mask": 3, "transpose": 5},
+    # the eval batching paths, measured at the commit BEFORE they moved to models/eval_batches.py
+    "forward_test_buckets": {"attn_flash": 16, "dwconv_ln": 34, "gemm_x3_mfma": 118, "layernorm": 32, "local_attn": 5, "mask_head": 1,
+                             "maxpool_mask": 3, "postprocess": 1, "transpose": 1},
+    "forward_test_matrices_rows": {"attn_flash": 16, "dwconv_ln": 34, "gemm_x3_mfma": 118, "layernorm": 32, "local_attn": 5, "mask_head": 1,
+                                   "maxpool_mask": 3, "postprocess": 1, "transpose": 1},
+    "forward_test_matrices_waves": {"attn_flash": 32, "dwconv_ln": 68, "gemm_x3_mfma": 236, "layernorm": 64, "local_attn": 10, "mask_head": 2,
+                                    "maxpool_mask": 6, "postprocess": 2, "transpose": 2},
+    "forward_test_matrices_cut_buckets": {"attn_flash": 60, "dwconv_ln": 102, "gemm_x3_mfma": 354, "layernorm": 96, "local_attn": 15,
+                                          "mask_head": 4, "maxpool_mask": 12, "postprocess": 4, "transpose": 4},
+    "forward_test_tracklets_buckets": {"attn_flash": 32, "dwconv_ln": 69, "gemm_x3_big": 1, "gemm_x3_mfma": 245, "layernorm": 68,
+                                       "local_attn": 11, "mask_head": 2, "maxpool_mask": 6, "postprocess": 2, "transpose": 7},
+    "forward_test_tracklets_unshared": {"attn_flash": 32, "dwconv_ln": 68, "gemm_x3_big": 2, "gemm_x3_mfma": 234, "layernorm": 64,
+                                        "local_attn": 10, "mask_head": 2, "maxpool_mask": 6, "postprocess": 2, "transpose": 2},
+    "mask_vrd_tight": {"attn_flash": 48, "dwconv_ln": 102, "gemm_x3_mfma": 390, "layernorm": 105, "local_attn": 15, "mask_head": 12,
+                       "maxpool_mask": 9, "transpose": 15},
+    "forward_test_videos": {"attn_flash": 32, "dwconv_ln": 69, "gemm_x3_big": 1, "gemm_x3_dma": 6, "gemm_x3_mfma": 239, "layernorm": 68,
+                            "local_attn": 11, "mask_head": 2, "maxpool_mask": 6, "postprocess": 3, "transpose": 7},
 }
 
 

@@ -29,6 +29,7 @@ import weakref
 import torch
 
 from . import ops
+from .models import eval_batches
 
 ENABLED = os.environ.get("VRDONE_EVAL_GRAPHS", "0") != "0"
 MAX_PAIRS = 256                     # larger buckets keep the GPU busy on their own
@@ -66,7 +67,7 @@ class _Recording:
         self.lens = torch.ones(n_pad, dtype=torch.int32, device=dev)
 
         def network():
-            return model._bucket_candidates(self.table, self.lens, T, k)
+            return eval_batches.bucket_candidates(model, self.table, self.lens, T, k)
 
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
@@ -94,7 +95,7 @@ class _Recording:
 
 
 def bucket_candidates(model, table, lens, T, k, c_in, storage=None):
-    """`model._bucket_candidates(table, lens, T, k)` through a recorded graph, or None when this bucket runs eagerly (replay
+    """`eval_batches.bucket_candidates(model, table, lens, T, k)` through a recorded graph, or None when this bucket runs eagerly (replay
     switched off, bucket too large, recording budget used up, the shape failed to record before).
     storage: storage_key(model), if the caller has it (one walk over the parameters per video instead of one per bucket)."""
     n = int(table.numel())

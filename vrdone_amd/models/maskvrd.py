@@ -18,7 +18,7 @@ from torch import nn
 from .backbones import MaskConvTransformerBackbone, MaskConvTransformerBackboneWithCLIP
 from .blocks import _factor_pool, _ops
 from .. import train_graph
-from . import losses
+from . import eval_batches, losses
 from .fpns import FPN1D_Fuse
 from .predictor import MaskedTransformerPredictor
 
@@ -85,7 +85,7 @@ class MaskVRD(nn.Module):
         # 2*chunk*T*2048 floats = 9.7 GB at 2048 pairs x 288 frames, of 288 GB).  Measured: 256 -> 1024 pairs +15 %,
         # 1024 -> 2048 +2.5 % (fewer launches of the small predictor / pyramid GEMMs, longer tile runs)
         self.pair_chunk = 2048
-        self.share_tracklets = True     # forward_test from a PairSource: entity stage once per tracklet (_entity_streams)
+        self.share_tracklets = True     # forward_test from a PairSource: entity stage once per tracklet (eval_batches.SharedStreams)
         self.device_matching = True       # Hungarian assignment on the device (vrd_assign); False: scipy on the host
         self.device_criterion = True      # ... and the losses straight from its result, no trip to the host (_criterion_on_device)
 
@@ -156,8 +156,8 @@ class MaskVRD(nn.Module):
                 flexible.setdefault(nxt, []).extend(moved)
         return out
 
-    # One row space for all buckets (models/ragged.py): the row-by-row kernels -- LayerNorm, every dense conv GEMM -- run once
-    # over all rows, so a bucket no longer has to fill the chip on its own and the buckets can be as fine as TIGHT_UNIT allows;
+    # One row space for all buckets (models/ragged.py; the drivers: models/eval_batches.py): the row-by-row kernels -- LayerNorm,
+    # every dense conv GEMM -- run once over all rows, so a bucket no longer has to fill the chip on its own and the buckets can be as fine as TIGHT_UNIT allows;
     # only the kernels that need (sequences, frames) structure walk the buckets.  ROWS_MIN_ROWS: below this a bucket's own
     # launches (depthwise convs, attention) are too small to be worth a launch each.
     row_space = os.environ.get("VRDONE_ROW_SPACE", "1") != "0"
@@ -171,8 +171,8 @@ class MaskVRD(nn.Module):
         return self.row_space and not self.use_abs_pe and n_pairs >= self.ROWS_MIN_PAIRS
 
     def _tight_plan(self, batched_masks, masks2d):
-        """{"buckets": [(T', pair indices (n,) int32 on the device, n)], "rows": the buckets can share one row space} for a
-        batch whose masks are prefixes (t < len), or None when the batch runs as it is (nothing to gain, masks with holes).
+        """{"buckets": [eval_batches.Bucket(T', pair indices (n,) int32 on the device, n, flat)], "rows": the buckets can share one
+        row space} for a batch whose masks are prefixes (t < len), or None when the batch runs as it is (nothing to gain, masks with holes).
         One small device-to-host copy per mask tensor (cached on it)."""
         key = (batched_masks.data_ptr(), batched_masks._version, tuple(batched_masks.shape), self.row_space, self.TIGHT_MIN_ROWS,
                self.ROWS_MIN_ROWS)
@@ -203,33 +203,11 @@ class MaskVRD(nn.Module):
                 buckets, at = [], 0
                 for flat, t2 in order:
                     n = len(want[(flat, t2)])
-                    buckets.append((t2, every[at:at + n], n, flat))
+                    buckets.append(eval_batches.Bucket(t2, every[at:at + n], n, flat))
                     at += n
                 plan = {"buckets": buckets, "rows": rows}
         batched_masks._vrd_tight_plan = (key, plan)
         return plan
-
-    def _mask_vrd_rows(self, x, masks2d, plan, with_aux):
-        """_mask_vrd with all buckets in one row space (models/ragged.py), in waves of at most ~pair_chunk pairs."""
-        from . import ragged
-        buckets = plan["buckets"]
-        B = masks2d.shape[0]
-        step = self._chunk_size(B)
-        out, wave, room = None, [], step
-        for t2, idx, n, flat in buckets:
-            at = 0
-            while at < n:
-                take = min(n - at, room)
-                wave.append((t2, idx[at:at + take].contiguous(), take, flat))
-                at += take
-                room -= take
-                if room == 0:
-                    out = ragged.mask_vrd_rows(self, x, masks2d, wave, with_aux, out)
-                    wave, room = [], step
-        if wave:
-            out = ragged.mask_vrd_rows(self, x, masks2d, wave, with_aux, out)
-        out["output_mask"] = masks2d[:, None, :]
-        return out
 
     # buckets side by side: a bucket's launches are a fraction of the batch's, and from the third pyramid level on they no longer
     # fill the chip (a 256 x 256 GEMM tile per CU needs 65 k rows); buckets are independent, so they run on TIGHT_STREAMS HIP
@@ -252,7 +230,6 @@ class MaskVRD(nn.Module):
         B, T = masks2d.shape
         dev = x.device
         out = None
-        fill = -10.0                                    # the predictor's value on padded frames (predictor.py:39)
         main = torch.cuda.current_stream(dev)
         plan = plan["buckets"]
         side = self._tight_side_streams(dev) if len(plan) > 1 and not torch.cuda.is_current_stream_capturing() else None
@@ -271,18 +248,12 @@ class MaskVRD(nn.Module):
                     m = m_all[c0:c0 + step]
                     o = self._heads(*self.backbone.cl_parts(*self.backbone._unpack(x, frames=t2, index=sel), m), with_aux)
                     if out is None:
-                        Q, K1 = o["pred_logits"].shape[1:]
-                        new = lambda: {"pred_logits": torch.empty(B, Q, K1, device=dev),                       # noqa: E731
-                                       "pred_masks": torch.full((B, Q, T), fill, device=dev)}
-                        out = new()
-                        if "aux_outputs" in o:
-                            out["aux_outputs"] = [new() for _ in o["aux_outputs"]]
+                        out = eval_batches.new_outputs(B, T, *o["pred_logits"].shape[1:], len(o.get("aux_outputs", ())), dev)
                         if len(lanes) > 1:
                             fork = torch.cuda.Event()
                             fork.record(main)            # the output buffers (and everything before this call) exist from here on
                     for dst, src in [(out, o)] + list(zip(out.get("aux_outputs", []), o.get("aux_outputs", []))):
-                        dst["pred_logits"][sel64] = src["pred_logits"]
-                        dst["pred_masks"][sel64, :, :t2] = src["pred_masks"]
+                        eval_batches.scatter_heads(dst, sel64, t2, src["pred_logits"], src["pred_masks"])
         for lane in lanes[1:]:
             main.wait_stream(lane)
         out["output_mask"] = masks2d[:, None, :]
@@ -299,7 +270,7 @@ class MaskVRD(nn.Module):
             plan = self._tight_plan(batched_masks, masks2d)
             if plan is not None:
                 if plan["rows"]:
-                    return self._mask_vrd_rows(batched_inputs, masks2d, plan, with_aux)
+                    return eval_batches.mask_vrd_rows(self, batched_inputs, masks2d, plan["buckets"], with_aux)
                 return self._mask_vrd_tight(batched_inputs, masks2d, plan, with_aux)
         if self.training and torch.is_grad_enabled():
             # a training step: the split-precision operands of all dense conv weights (forward and input-gradient form) in one
@@ -349,16 +320,6 @@ class MaskVRD(nn.Module):
             return max(n, 1)
         waves = -(-n // self.pair_chunk)
         return -(-n // waves)
-
-    def _bucket_candidates(self, table, lens_dev, T, k):
-        """The device side of one bucket of forward_test: the pairs `table` (device pointers to their (L, C_in) matrices) /
-        `lens_dev` at padded length T -> vrd_postprocess's (top scores, top classes, first, last frame).  No host read-back,
-        shapes fixed by (T, number of pairs): what eval_graph.py records."""
-        ops = _ops()
-        bb = self.backbone
-        *parts, m2 = ops.pack_pairs(table, lens_dev, T, bb.n_visual, bb.n_clip, bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())
-        out = self._heads(*bb.cl_parts(*parts, m2), False)
-        return ops.postprocess(out["pred_logits"].contiguous(), out["pred_masks"].contiguous(), lens_dev, k)
 
     def _heads(self, feats, masks, with_aux, lay=None):
         """neck + predictor.  lay: the layout of the full-resolution rows; without one the batch form and the reference's dict,
@@ -708,8 +669,7 @@ class MaskVRD(nn.Module):
         max_seq_len), and dealing that order round-robin gives every rank of a sharded run the same mix of lengths.
         Returns (order: list of pair ids, t_pad: padded length per pair id)."""
         # (the reference's padded length of every pair; then the shortest ones that give the same results: `tight padding`)
-        t_pad = self.tight_buckets(lens, self._reference_pad(lens), self.ROWS_MIN_ROWS if self._eval_rows_form(len(lens)) else None)
-        return sorted(range(len(lens)), key=lambda i: (t_pad[i], lens[i], i)), t_pad
+        return eval_batches.pair_order(self, lens, self._reference_pad(lens))
 
     def _reference_pad(self, lens):
         """The padded length the reference gives each pair of one video: max_seq_len, or its max_so_pair slice's longest rounded up."""
@@ -723,279 +683,20 @@ class MaskVRD(nn.Module):
         return t_pad
 
     def _entity_streams(self, source, ids):
-        """The backbone's entity stage run ONCE PER TRACKLET (per sub-sampling phase) for the pairs `ids` of a
-        proposals.PairSource: (rows (n_streams * Ts, D), stream_row (2, len(ids)) int64 device = row of frame 0 of each
-        pair's subject / object, (piece length, piece buffer length), reach).  None when the stage cannot be shared: no tracklet table, or
-        global attention in the first stem block (backbones.entity_reach)."""
-        import numpy as np
-        bb = self.backbone
-        reach = bb.entity_reach()
-        if not self.share_tracklets or reach is None or source.first_row is None:
-            return None
-        ops = _ops()
-        dev = self.device
-        start, length, stream, j0 = source.stream_plan(ids)
-        chunk = 2 * (bb.mha_win_size[0] // 2)                  # the local attention takes whole chunks (blocks.py:828)
-        unit = math.lcm(32, chunk)
-        Ts = -(-int(length.max()) // unit) * unit
-        stream_row = torch.from_numpy(stream.astype(np.int64) * Ts + j0).to(dev)       # uploads first, kernels after
-        starts, lengths = torch.from_numpy(start).to(dev), torch.from_numpy(length).to(dev)
-        wh = source.rows_wh(start)                             # (a source of several videos: each stream's own frame size)
-        wh = None if wh is None else torch.from_numpy(wh).to(dev)
-        n = len(start)
-        D = bb.s_fuse_norm.num_channels
-        rows = torch.empty(n, Ts, D, device=dev, dtype=torch.float32)
-        step = max(1, (2 * self.pair_chunk * 288) // Ts)
-        for c0 in range(0, n, step):
-            c1 = min(c0 + step, n)
-            # (the gather writes a subject and an object half; a stream is both)
-            vis, clip, _, ent, m = ops.gather_rows(source, starts[c0:c1], starts[c0:c1], lengths[c0:c1], Ts, bb.n_bbox_so,
-                                                   bb.n_bbox_entity, ops.pair_mode(), seq_wh=None if wh is None else wh[c0:c1])
-            h = c1 - c0
-            rows[c0:c1] = bb.entity_stage(vis[:h], clip[:h] if clip is not None else None, ent[:h], m)
-        piece = -(-2 * reach // chunk) * chunk
-        return rows, stream_row, (piece, piece + chunk), reach
-
-    def _shared_pieces(self, source, sel, shared, T):
-        """The window-edge pieces of the pairs `sel` (device indices) through the entity stage: (4B, L, D) = [subject start |
-        subject end | object start | object end] pieces.  T: the pairs' padded length (an int, or one per pair as a device
-        tensor: the pairs of several buckets in one batch)."""
-        ops = _ops()
-        bb = self.backbone
-        _, _, (piece, L), _ = shared
-        s_row, o_row, lens = source.s_row[sel], source.o_row[sel], source.lens_dev[sel].contiguous()
-        # start pieces: the first `piece` frames.  End pieces: the last `piece` frames followed by padding, as in the pair's
-        # own rows -- or, for a pair that fills its T frames, the last L frames filling the buffer (vrd_assemble_args)
-        end_len = torch.where(lens == T, L, piece).to(torch.int32)
-        end_len = torch.where(lens > piece, end_len, torch.zeros_like(end_len))
-        tail = (lens - end_len).clamp(min=0).long() * source.stride
-        piece_s = torch.cat([s_row, s_row + tail])                  # [start pieces | end pieces]
-        piece_o = torch.cat([o_row, o_row + tail])
-        piece_len = torch.cat([lens.clamp(max=piece), end_len])
-        wh = source.pair_wh_of(sel)
-        vis, clip, _, ent, m = ops.gather_rows(source, piece_s, piece_o, piece_len, L, bb.n_bbox_so, bb.n_bbox_entity,
-                                               ops.pair_mode(), seq_wh=None if wh is None else torch.cat([wh, wh]))
-        return bb.entity_stage(vis, clip, ent, torch.cat([m, m], dim=0))                   # (4B, L, D)
+        return eval_batches.SharedStreams.streams(self, source, ids)
 
     def _shared_entity_rows(self, source, sel, shared, at, T, pieces=None):
-        """(2B, T, D) entity-stage rows of the pairs `sel` (device indices; positions at.. of the id list the streams were
-        planned for), the pairs' box features (B, T, S) and mask: frames further than `reach` from both window edges come
-        from the per-tracklet rows, the rest from L-frame pieces at the edges run through the same stage (`pieces`: those,
-        when the caller has them already -- _shared_pieces over the pairs of several buckets at once)."""
-        ops = _ops()
-        bb = self.backbone
-        rows, stream_row, (piece, L), reach = shared
-        B = sel.shape[0]
-        s_row, o_row, lens = source.s_row[sel], source.o_row[sel], source.lens_dev[sel].contiguous()
-        if pieces is None:
-            pieces = self._shared_pieces(source, sel, shared, T)
-        _, _, so_box, _, mask = ops.gather_rows(source, s_row.contiguous(), o_row.contiguous(), lens, T, bb.n_bbox_so,
-                                                bb.n_bbox_entity, False, boxes_only=True, seq_wh=source.pair_wh_of(sel))
-        so = ops.assemble_pairs(rows, pieces, stream_row[:, at:at + B].reshape(-1), lens, T, piece, reach)
-        return so, so_box, mask
+        return eval_batches.SharedStreams(self, source, None, shared).entity_rows(sel, at, T, pieces)
 
     def pair_candidates(self, feats, lens, ids, t_pad, k, source=None):
-        """Network + per-(pair, query) post-processing kernel for the pairs `ids` (already grouped by padded length).
+        """Network + per-(pair, query) post-processing kernel for the pairs `ids` (already grouped by padded length), bucket by
+        bucket or, from _eval_rows_form's size on, all padded lengths of a launch wave in one row space (models/eval_batches.py).
         source: a proposals.PairSource -- pair rows are then gathered on the device from the per-tracklet features
         (vrd_gather_pairs) and `feats` is not used; with its tracklet table the entity stage of the backbone runs once
-        per tracklet instead of twice per pair (_entity_streams).
+        per tracklet instead of twice per pair (eval_batches.SharedStreams).
         Returns ONE float32 tensor (len(ids), Q, 2k + 2) = [top-k scores | top-k class ids | first | last frame], the
         three integer fields bit-cast: the compact candidate record that sharded runs exchange (SURVEY 8e option i)."""
-        ops = _ops()
-        dev = self.device
-        Q = self.predictor.num_queries
-        cand = torch.empty(len(ids), Q, 2 * k + 2, device=dev, dtype=torch.float32)
-        if not ids:
-            return cand
-        ints = cand.view(torch.int32)
-        # every host->device table goes up before the first kernel is queued (such a copy waits for the queue)
-        lens_dev = torch.tensor([lens[i] for i in ids], dtype=torch.int32, device=dev)
-        shared = None
-        if source is not None:
-            ids_dev = torch.tensor(ids, dtype=torch.int64, device=dev)
-            local, tables = None, None
-            shared = self._entity_streams(source, ids)
-        else:
-            local = [feats[i] for i in ids]
-            tables = ops.pair_table(local)      # None unless the features are the dataloader's frame-major matrices
-        bb = self.backbone
-        if self._eval_rows_form(len(lens)) and (source is not None or tables is not None):
-            # all padded lengths of the video in one row space (models/ragged.py), in waves of ~pair_chunk pairs
-            self._candidates_rows(cand, lens, ids, t_pad, k, source, tables, shared, lens_dev,
-                                  ids_dev if source is not None else None)
-            return cand
-        from .. import eval_graph
-        storage = None
-        at = 0
-        while at < len(ids):
-            T = t_pad[ids[at]]
-            n = 1
-            while at + n < len(ids) and t_pad[ids[at + n]] == T:
-                n += 1
-            replayed = None
-            if tables is not None and source is None and n <= eval_graph.MAX_PAIRS:
-                # a small bucket of the dataloader's per-pair matrices: its whole device side as one recorded graph (eval_graph.py)
-                if storage is None:
-                    storage = eval_graph.storage_key(self)
-                replayed = eval_graph.bucket_candidates(self, tables[0][at:at + n], tables[1][at:at + n], T, k,
-                                                        int(local[0].shape[0]), storage)
-            if replayed is not None:
-                ts, tc, sf, sl_ = replayed
-                cand[at:at + n, :, :k] = ts
-                ints[at:at + n, :, k:2 * k] = tc
-                ints[at:at + n, :, 2 * k] = sf
-                ints[at:at + n, :, 2 * k + 1] = sl_
-                at += n
-                continue
-            if source is not None or tables is not None:
-                # per-tracklet rows (gathered, box features computed on the device) or the dataloader's (L, C_in)
-                # matrices go straight into the backbone's operand buffers
-                outs = []
-                step = self._chunk_size(n)
-                for c0 in range(at, at + n, step):
-                    c1 = min(c0 + step, at + n)
-                    if shared is not None and T > 2 * shared[2][1]:
-                        fm = bb.pair_stage(*self._shared_entity_rows(source, ids_dev[c0:c1], shared, c0, T))
-                    elif source is not None:
-                        assert (source.n_visual, source.n_clip) == (bb.n_visual, bb.n_clip)
-                        *parts, m2 = ops.gather_pairs(source, ids_dev[c0:c1], T, bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())
-                        fm = bb.cl_parts(*parts, m2)
-                    else:
-                        *parts, m2 = ops.pack_pairs(tables[0][c0:c1], tables[1][c0:c1], T, bb.n_visual, bb.n_clip,
-                                                    bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())
-                        fm = bb.cl_parts(*parts, m2)
-                    outs.append(self._heads(*fm, False))
-                out = self._merge(outs)
-            else:
-                x, m = self._batch(local, range(at, at + n), T)
-                out = self._mask_vrd(x, m, with_aux=False)
-            ts, tc, sf, sl_ = ops.postprocess(out["pred_logits"].contiguous(), out["pred_masks"].contiguous(),
-                                              lens_dev[at:at + n], k)
-            cand[at:at + n, :, :k] = ts
-            ints[at:at + n, :, k:2 * k] = tc
-            ints[at:at + n, :, 2 * k] = sf
-            ints[at:at + n, :, 2 * k + 1] = sl_
-            at += n
-        return cand
-
-    def _candidates_rows(self, cand, lens, ids, t_pad, k, source, tables, shared, lens_dev, ids_dev):
-        """pair_candidates with the buckets (runs of one padded length in `ids`) of a wave in ONE row space: the entity stage
-        of the buckets that do not take it from the per-tracklet rows, then the pair stage, neck and predictor once over all
-        rows (models/ragged.py).  A bucket's pairs within one frame of its padded length (no two padded frames behind them)
-        are a bucket of their own, behind the others (they are the longest of their run: `ids` is sorted by length)."""
-        from . import ragged
-        ops = _ops()
-        bb = self.backbone
-        ints = cand.view(torch.int32)
-        runs, at = [], 0                                      # (T, first position, end position, flat)
-        while at < len(ids):
-            T = t_pad[ids[at]]
-            n = 1
-            while at + n < len(ids) and t_pad[ids[at + n]] == T:
-                n += 1
-            cut = at
-            while cut < at + n and lens[ids[cut]] <= T - 2:
-                cut += 1
-            if cut > at:
-                runs.append((T, at, cut, True))
-            if cut < at + n:
-                runs.append((T, cut, at + n, False))
-            at += n
-        step = self._chunk_size(len(ids))
-        waves, wave, room = [], [], step
-        for T, c0, c1, flat in runs:
-            while c0 < c1:
-                take = min(c1 - c0, room)
-                wave.append((T, c0, c0 + take, flat))
-                c0 += take
-                room -= take
-                if room == 0:
-                    waves.append(wave)
-                    wave, room = [], step
-        if wave:
-            waves.append(wave)
-        rows2 = lambda t: (t.t if isinstance(t, ops.Pair) else t)                                 # noqa: E731
-        for wave in waves:
-            wave.sort(key=lambda b: not b[3])                 # (stable: the flat buckets first, each kind by padded length)
-            # (filler buckets of all-padding sequences round the row count: ragged.filler_buckets; positions c0 < 0)
-            at_fill = sum(1 for b in wave if b[3])
-            wave[at_fill:at_fill] = [(T, -n, 0, True) for n, T in ragged.filler_buckets(sum((c1 - c0) * T for T, c0, c1, _ in wave), 1 << 30)]
-            lay = ragged.Layout([(c1 - c0, T, flat) for T, c0, c1, flat in wave])
-            got = []                                          # per bucket ("so", so, box, mask) | ("parts", vis, clip, box, ent, mask)
-            # the window-edge pieces of all buckets that take their entity rows from the per-tracklet streams: ONE pass through
-            # the entity stage (they are L frames long whatever the bucket)
-            from_streams = [(T, c0, c1) for T, c0, c1, _ in wave if c0 >= 0 and shared is not None and T > 2 * shared[2][1]]
-            pieces_all, n_all, q0 = None, sum(c1 - c0 for _, c0, c1 in from_streams), 0
-            if len(from_streams) > 1:
-                sel_all = torch.cat([ids_dev[c0:c1] for _, c0, c1 in from_streams])
-                t_all = torch.cat([torch.full((c1 - c0,), T, dtype=torch.int32, device=sel_all.device) for T, c0, c1 in from_streams])
-                pieces_all = self._shared_pieces(source, sel_all, shared, t_all)
-            for T, c0, c1, flat in wave:
-                if c0 < 0:                                    # the filler: zero rows under an all-false mask
-                    n, dev = c1 - c0, cand.device
-                    zeros = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)               # noqa: E731
-                    no_mask = torch.zeros(n, T, dtype=torch.bool, device=dev)
-                    if len(from_streams) == sum(1 for b in wave if b[1] >= 0):    # ... entity rows, when every bucket brings those
-                        got.append(("so", zeros(2 * n, T, bb.s_fuse_norm.num_channels), zeros(n, T, bb.n_bbox_so), no_mask))
-                    else:                                     # ... raw features: the entity stage's row space is rounded too
-                        wide = (lambda t, w: ops.Pair(t, w)) if ops.pair_mode() else (lambda t, w: t)         # noqa: E731
-                        got.append(("parts", wide(zeros(2 * n, T, bb.n_visual), bb.n_visual),
-                                    wide(zeros(2 * n, T, bb.n_clip), bb.n_clip) if bb.n_clip else None,
-                                    zeros(n, T, bb.n_bbox_so), zeros(2 * n, T, bb.n_bbox_entity), no_mask))
-                elif shared is not None and T > 2 * shared[2][1]:
-                    pieces = None
-                    if pieces_all is not None:
-                        pieces = torch.cat([pieces_all[j * n_all + q0:j * n_all + q0 + c1 - c0] for j in range(4)])
-                        q0 += c1 - c0
-                    got.append(("so",) + tuple(self._shared_entity_rows(source, ids_dev[c0:c1], shared, c0, T, pieces)))
-                elif source is not None:
-                    assert (source.n_visual, source.n_clip) == (bb.n_visual, bb.n_clip)
-                    got.append(("parts",) + tuple(ops.gather_pairs(source, ids_dev[c0:c1], T, bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())))
-                else:
-                    got.append(("parts",) + tuple(ops.pack_pairs(tables[0][c0:c1], tables[1][c0:c1], T, bb.n_visual, bb.n_clip,
-                                                                 bb.n_bbox_so, bb.n_bbox_entity, ops.pair_mode())))
-            mask = torch.cat([g[-1].reshape(-1) for g in got]).view(1, lay.rows)
-            so_box = torch.cat([g[2 if g[0] == "so" else 3].reshape(-1, bb.n_bbox_so) for g in got]).view(1, lay.rows, -1)
-            # entity stage of the buckets that bring raw features: a row space of their own, [subject | object] like the joint one
-            ent_b = [(b, g) for b, g in zip(wave, got) if g[0] == "parts"]
-            so_e, lay_e = None, None
-            if ent_b:
-                lay_e = ragged.Layout([(c1 - c0, T, flat) for (T, c0, c1, flat), _ in ent_b])
-
-                def stacked(j):
-                    ts = [g[j] for _, g in ent_b]
-                    if ts[0] is None:
-                        return None
-                    halves = [rows2(t)[:t.shape[0] // 2] for t in ts] + [rows2(t)[t.shape[0] // 2:] for t in ts]
-                    flat_rows = torch.cat([h.reshape(-1, h.shape[-1]) for h in halves]).view(1, 2 * lay_e.rows, -1)
-                    return ops.Pair(flat_rows, ts[0].width, ts[0].fmt) if isinstance(ts[0], ops.Pair) else flat_rows
-                m_e = torch.cat([g[-1].reshape(-1) for _, g in ent_b]).view(1, lay_e.rows)
-                so_e = bb.entity_stage(stacked(1), stacked(2), stacked(4), torch.cat([m_e, m_e], dim=1), lay_e.stacked())
-            # the joint entity-stage rows: every bucket's subject rows, then every bucket's object rows
-            halves, e_at = ([], []), 0
-            for (T, c0, c1, flat), g in zip(wave, got):
-                n = c1 - c0
-                if g[0] == "so":
-                    halves[0].append(g[1][:n].reshape(n * T, -1))
-                    halves[1].append(g[1][n:].reshape(n * T, -1))
-                else:
-                    halves[0].append(so_e[0, e_at:e_at + n * T])
-                    halves[1].append(so_e[0, lay_e.rows + e_at:lay_e.rows + e_at + n * T])
-                    e_at += n * T
-            so = torch.cat(halves[0] + halves[1]).view(1, 2 * lay.rows, -1)
-            del got, so_e, halves
-            heads = self._heads(*bb.pair_stage(so, so_box, mask, lay), False, lay)
-            logits, segs = heads[-1]
-            p = 0
-            for (T, c0, c1, flat), seg in zip(wave, segs):
-                n = c1 - c0
-                if c0 >= 0:
-                    ts, tc, sf, sl_ = ops.postprocess(logits[p:p + n].contiguous(), seg, lens_dev[c0:c1], k)
-                    cand[c0:c1, :, :k] = ts
-                    ints[c0:c1, :, k:2 * k] = tc
-                    ints[c0:c1, :, 2 * k] = sf
-                    ints[c0:c1, :, 2 * k + 1] = sl_
-                p += n
+        return eval_batches.pair_candidates(self, feats, lens, ids, t_pad, k, source)
 
     @torch.no_grad()
     def forward_test(self, input_data):
@@ -1155,9 +856,7 @@ class MaskVRD(nn.Module):
         lens = [L for lv in lens_v for L in lv]
         P = len(lens)
         # the reference's padded lengths video by video, then one tight-padding plan over all pairs of the call
-        t_pad = self.tight_buckets(lens, [t for lv in lens_v for t in self._reference_pad(lv)],
-                                   self.ROWS_MIN_ROWS if self._eval_rows_form(P) else None)
-        order = sorted(range(P), key=lambda i: (t_pad[i], lens[i], i))
+        order, t_pad = eval_batches.pair_order(self, lens, [t for lv in lens_v for t in self._reference_pad(lv)])
 
         # per-pair tables on the host, in one upload: [s score | o score | so_offset | so_start | so_end | video pair offsets]
         base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)

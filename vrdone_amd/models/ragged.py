@@ -5,7 +5,9 @@ predictor.py).  Most of it works row by row -- LayerNorm, every k = 1 conv GEMM 
 residuals, row mask), which is the bulk of the FLOPs -- and does not care which rows share a launch.  The rest needs the
 (sequences, frames) structure: depthwise conv + LayerNorm (stride 1 / 2, FPN upsample-add), the banded and the global
 attention, the pyramid's max-pool, the dense k = 3 convs, the mask head, and taking the subject / object halves of a stacked
-buffer.  Those operations live here and take a `Layout`; the `cl` methods pass their layout(s) on to them.  Two forms exist:
+buffer.  Those operations live here and take a `Layout`; the `cl` methods pass their layout(s) on to them.  Nothing here takes a
+model or a backbone: which pairs share a row space, where their operands come from and where the heads' outputs go is
+models/eval_batches.py (it builds the layouts; `filler_buckets` here tells it how to round their row count).  Two forms exist:
 
   * the batch form (`Layout.batch`, what a `cl` method reads from its tensors' shape when no layout is given): B sequences of
     T frames as a (B, T, C) tensor.  Every operation here is then the one `ops.*` call on that tensor, and under autograd its
@@ -322,36 +324,6 @@ def mask_head(lay, emb, feat, out_mask, fill):
     return segs_out
 
 
-def unpack_rows(bb, x, plan, lay):
-    """backbones.py _unpack for the buckets of `plan` = [(T_i, pair indices (int32, device), n_i, ...)] over the caller's batch
-    x (B, C_in, T) -> vis, clip, so_box, ent in the row space (vis / clip / ent stacked [subject | object])."""
-    ops = _ops()
-    R = lay.rows
-    V, Cc, S, E = bb.n_visual, bb.n_clip, bb.n_bbox_so, bb.n_bbox_entity
-    pair = ops.pair_mode()
-
-    def stacked(c0, width, as_pair):
-        h = lay.stacked().new(width, x)
-        for (off, n, T), bucket in zip(lay.segs, plan):
-            t2, idx = bucket[0], bucket[1]
-            ops.bct_to_btc(x, c0, width, _part(h, off, n, T), pair=as_pair, frames=t2, index=idx)
-            ops.bct_to_btc(x, c0 + width, width, _part(h, R + off, n, T), pair=as_pair, frames=t2, index=idx)
-        return ops.Pair(h, width) if as_pair else h
-
-    o0 = 2 * V + 2 * Cc
-    so_box = lay.new(S, x)
-    for (off, n, T), bucket in zip(lay.segs, plan):
-        ops.bct_to_btc(x, o0, S, _part(so_box, off, n, T), frames=bucket[0], index=bucket[1])
-    return stacked(0, V, pair), (stacked(2 * V, Cc, pair) if Cc else None), so_box, stacked(o0 + S, E, False)
-
-
-def backbone_rows(bb, x, plan, lay, mask):
-    """backbones.py cl for the buckets of `plan` over the caller's batch x (B, C_in, T); mask: flat (1, R) validity of the rows"""
-    vis, clip, so_box, ent = unpack_rows(bb, x, plan, lay)
-    so = bb.entity_stage(vis, clip, ent, torch.cat([mask, mask], dim=1), lay.stacked())
-    return bb.pair_stage(so, so_box, mask, lay)
-
-
 def filler_buckets(rows, t_max):
     """[(sequences, frames)] of all-padding sequences that round a row space of `rows` rows up to a multiple of 256: the
     256 x 256 GEMM kernel takes row counts that are multiples of 64 (its epilogue has no row predicates), and with 256 that
@@ -370,42 +342,4 @@ def filler_buckets(rows, t_max):
     out = [(1, first)] if first else []
     if need - first:
         out.insert(0, ((need - first) // 32, 32))
-    return out
-
-
-def with_filler(buckets, make, t_max):
-    """`buckets` [(frames, ..., sequences, flat)] plus, behind the last flat one, the filler buckets make(n, T) the row count asks
-    for -> (buckets, indices of the fillers)"""
-    fill = filler_buckets(sum(b[2] * b[0] for b in buckets), t_max)
-    at = sum(1 for b in buckets if b[-1])
-    return list(buckets[:at]) + [make(n, T) for n, T in fill] + list(buckets[at:]), set(range(at, at + len(fill)))
-
-
-def mask_vrd_rows(model, x, masks2d, plan, with_aux, out=None):
-    """MaskVRD._mask_vrd for the buckets of `plan` = [(T_i, pair indices, n_i, flat_i)] in one row space; results written into (or
-    returned as) the batch-shaped output dict: pred_logits (B, Q, K+1), pred_masks (B, Q, T) at the batch's own padded length,
-    -10 behind a bucket's."""
-    B, T = masks2d.shape
-    dev = x.device
-    # (a filler bucket recomputes the first frames of some pair under an all-false mask: finite numbers nobody reads)
-    plan, filler = with_filler(plan, lambda n, t: (t, plan[0][1][:1].repeat(n), n, True), T)
-    lay = Layout([(n, t2, flat) for t2, _, n, flat in plan])
-    idx64 = [b[1].long() for b in plan]
-    mask = torch.cat([masks2d[i64, :b[0]].reshape(-1) if j not in filler else torch.zeros(b[2] * b[0], dtype=torch.bool, device=dev)
-                      for j, (b, i64) in enumerate(zip(plan, idx64))]).view(1, lay.rows)
-    heads = model._heads(*backbone_rows(model.backbone, x, plan, lay, mask), with_aux, lay)
-    fill = -10.0                                        # the predictor's value on padded frames (predictor.py:39)
-    if out is None:
-        Q, K1 = heads[-1][0].shape[1:]
-        new = lambda: {"pred_logits": torch.empty(B, Q, K1, device=dev), "pred_masks": torch.full((B, Q, T), fill, device=dev)}  # noqa: E731
-        out = new()
-        if len(heads) > 1:
-            out["aux_outputs"] = [new() for _ in heads[:-1]]
-    for dst, (logits, segs) in zip(out.get("aux_outputs", []) + [out], heads):
-        p = 0
-        for j, (b, i64, seg) in enumerate(zip(plan, idx64, segs)):
-            if j not in filler:
-                dst["pred_logits"][i64] = logits[p:p + b[2]]
-                dst["pred_masks"][i64, :, :b[0]] = seg
-            p += b[2]
     return out
