@@ -299,8 +299,11 @@ typedef struct {
     int32_t products;       /* MFMA products per split-precision operand pair: 0 or 3 = a_hi*w_hi + a_hi*w_lo + a_lo*w_hi (every
                                mode so far); 1 = a_hi*w_hi only (f16x1; needs split_fmt == VRD_PAIR_F16 and W_split).  All three
                                split-precision kernels form the same products in the same order in either form, so the choice of
-                               kernel never changes a bit.  A call that does not qualify for a split kernel runs exact f32
-                               products, as in the three-product form.  vrd_gemm_batch needs the same value in every entry. */
+                               kernel never changes a bit of the accumulators, nor of a bias-only output.  The other epilogues give
+                               the same values on every kernel, but the sign of a zero (a masked row, GELU far below zero) may
+                               differ between the 256 x 256 kernel and the others.  A call that does not qualify for a split kernel
+                               runs exact f32 products, as in the three-product form.  vrd_gemm_batch needs the same value in
+                               every entry. */
 } vrd_gemm_args;
 int vrd_gemm(const vrd_gemm_args* a, void* stream);
 /* The kernel family (enum vrd_kernel_id) vrd_gemm would run these arguments on, without launching anything: VRD_K_GEMM (exact

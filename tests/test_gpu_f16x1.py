@@ -31,13 +31,9 @@ def no_grad():
 
 def _to_pair(t):
     """f32 (B, T, C) -> f16-format pair rows (test helper; mirrors vrd::store_pair4)"""
+    from gemm_tile_cases import encode_pair
     from vrdone_amd import _hip, ops
-    t = t * 2.0 ** _hip.F16_ACT_EXP
-    hi = t.to(torch.float16)
-    lo = (t - hi.float()).to(torch.float16)
-    C = t.shape[-1]
-    raw = torch.stack([hi.reshape(*t.shape[:-1], C // 32, 32), lo.reshape(*t.shape[:-1], C // 32, 32)], dim=-2)
-    return ops.Pair(raw.reshape(*t.shape[:-1], 2 * C).contiguous().view(torch.float32), C, _hip.PAIR_F16)
+    return ops.Pair(encode_pair(t, True), t.shape[-1], _hip.PAIR_F16)
 
 
 def _gemm(x, w, bias, mode, **kw):

@@ -598,16 +598,10 @@ def test_gemm_k3_short_sequences(precision):
 
 def _to_pair(t):
     """Encode an f32 (B, T, C) tensor as pair rows (test helper; mirrors vrd::store_pair4)."""
+    from gemm_tile_cases import encode_pair
     from vrdone_amd import _hip, ops
     f16 = ops.pair_fmt() == _hip.PAIR_F16          # the current mode's element format: f16 planes hold x * 2^F16_ACT_EXP
-    dt = torch.float16 if f16 else torch.bfloat16
-    t = t * 2.0 ** _hip.F16_ACT_EXP if f16 else t
-    hi = t.to(dt)
-    lo = (t - hi.float()).to(dt)
-    C = t.shape[-1]
-    raw = torch.stack([hi.reshape(*t.shape[:-1], C // 32, 32), lo.reshape(*t.shape[:-1], C // 32, 32)], dim=-2)
-    raw = raw.reshape(*t.shape[:-1], 2 * C).contiguous()            # blocks of [32 hi | 32 lo]: 4C bytes per row
-    return ops.Pair(raw.view(torch.float32), C)
+    return ops.Pair(encode_pair(t, f16), t.shape[-1])
 
 
 @pytest.mark.parametrize("H,hd,Tq,Tk", [(4, 128, 96, 96), (8, 64, 144, 144), (4, 128, 288, 288), (8, 64, 512, 512),

@@ -597,7 +597,10 @@ static int launch_big_one(const vrd_gemm_args& a, hipStream_t s, const BigBatch&
     // (measured, scripts/dev/stagger_sweep.sh, profiles/r04_lab_gemm_stagger.txt: 0 / 1 / 2 / 4 / 8 units -> 98.1-98.2 / 97.4 / 97.1 /
     // 97.8 / 99.4 ms of this kernel per step: about 1 %, so the epilogues were not waiting for each other's stores much)
     static const int stagger = [] { const char* e = getenv("VRD_BIG_STAGGER"); return e ? atoi(e) : 2; }();
-    const int n_cu = PERSIST ? device_cu_count() : 0;
+    // VRD_BIG_GRID=n (n > 0): the persistent form launches at most n workgroups instead of one per CU, so that a few tiles
+    // already make a workgroup walk several (the tests reach every ring phase on 14 tiles; the kernel advances by gridDim.x)
+    static const int grid_env = [] { const char* e = getenv("VRD_BIG_GRID"); return e ? atoi(e) : 0; }();
+    const int n_cu = PERSIST ? (grid_env > 0 ? grid_env : device_cu_count()) : 0;
     BigKArgs ka;
     ka.p = a, ka.tiles_m = tiles_m, ka.tiles_n = tiles_n, ka.bb = bb, ka.stagger = (PERSIST || nwg < 512) ? 0 : stagger;
     ka.rflag = a.c_pair == VRD_PAIR_F16 ? range_flag() : nullptr;
