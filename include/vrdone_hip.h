@@ -434,8 +434,8 @@ int vrd_attention(const float* q, int64_t ldq, const float* k, const float* v, i
                   float* out, int64_t ldo, int algo, int out_pair, void* stream);
 
 /* Same attention for pair-row q, k, v (split-precision modes; rows of width n_head*head_dim written by the projection
- * GEMMs with c_pair): both contractions as three 16-bit MFMA products, f32 softmax.  head_dim in {64, 128}.
- * products: 0 or 3 as described; 1 (pair_fmt VRD_PAIR_F16 only) = q_hi*k_hi for the scores and p_hi*v_hi for the output, with
+ * GEMMs with c_pair): both contractions as three 16-bit MFMA products, f32 softmax.  head_dim in {32, 64, 128}; Tk <= 4096.
+ * products: 0 or 3 as described; 1 (pair_fmt VRD_PAIR_F16 only, head_dim 64 or 128: refused at 32) = q_hi*k_hi for the scores and p_hi*v_hi for the output, with
  * p_hi = f16(P * 2^VRD_F16_ACT_EXP) of the f32 softmax probabilities P (the f16x1 mode).
  * pair_fmt: the format of q, k, v (VRD_PAIR_BF16 / VRD_PAIR_F16); out_pair: 0 or the same format.
  * q_mask (optional, B*Tq bytes): query rows the caller zeroes afterwards anyway (the output projection's row mask,

@@ -3,9 +3,18 @@
 288 rows, 256 valid): per-launch time of each, max difference between them, and against the f32 VALU kernel on a sample.
 
     python scripts/flash_bench.py [--B 2048] [--T 288] [--valid 256] [--heads 4] [--hd 128]
+
+At head_dim 32 there is one flash kernel (32 queries per wave), so --hd 32 times two ROUTES of global attention instead: pair rows
+through vrd_attention_pair (the split modes' eval route) and the same values as f32 rows through the vector-unit kernel
+(ops.attention(..., algo=1): the route of the exact-f32 mode and of training), alternating in one process, several repeats each,
+median and spread reported per shape.
+
+    python scripts/flash_bench.py --hd 32 [--cases 16:2048:96:96,16:2048:288:256,8:2048:96:96] [--repeats 5] [--json out.json]
 """
 import argparse
+import json
 import os
+import statistics
 import sys
 
 import torch
@@ -27,6 +36,57 @@ def to_pair(t):
     return ops.Pair(raw.reshape(*t.shape[:-1], 2 * C).contiguous().view(torch.float32), C)
 
 
+def time_ms(fn, iters):
+    """per-call time of `iters` back-to-back calls between two device events"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def routes_hd32(a, dev):
+    """head_dim 32: the pair-row flash route against the f32-row vector-unit route, per case heads:B:T:valid"""
+    results = []
+    for case in a.cases.split(","):
+        heads, B, T, valid = (int(x) for x in case.split(":"))
+        g = torch.Generator(device=dev).manual_seed(1)
+        C = heads * 32
+        qf, kf, vf = (torch.randn(B, T, C, device=dev, generator=g) for _ in range(3))
+        qp, kp, vp = (to_pair(t) for t in (qf, kf, vf))
+        mask = (torch.arange(T, device=dev)[None] < valid).expand(B, T).contiguous()
+        routes = {"flash_pair": lambda: ops.attention(qp, kp, vp, mask, heads, pair=a.pair, q_mask=mask),
+                  "small_f32": lambda: ops.attention(qf, kf, vf, mask, heads, algo=1)}
+        times = {name: [] for name in routes}
+        with torch.no_grad():
+            outs = {}
+            for name, fn in routes.items():
+                for _ in range(3):
+                    outs[name] = fn()
+            torch.cuda.synchronize()
+            for _ in range(a.repeats):                      # alternating: a drift of the machine hits both routes alike
+                for name, fn in routes.items():
+                    times[name].append(time_ms(fn, a.iters))
+        new = outs["flash_pair"].float() if a.pair else outs["flash_pair"]
+        diff = (new[mask] - outs["small_f32"][mask]).abs().max().item()
+        rec = {"heads": heads, "head_dim": 32, "B": B, "T": T, "valid": valid, "precision": ops.get_precision(), "iters": a.iters,
+               "max_abs_diff": diff}
+        for name, ts in times.items():
+            rec[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+        f, s = rec["flash_pair"], rec["small_f32"]
+        # the new route wins when its slowest repeat beats the other's fastest: a difference beyond the spread of both
+        rec["flash_wins_beyond_spread"] = f["max_ms"] < s["min_ms"]
+        rec["speedup_median"] = s["median_ms"] / f["median_ms"]
+        print(f"{heads:2d} x 32, B {B}, T {T} ({valid} valid), {rec['precision']}: flash on pair rows {f['median_ms']:.3f} ms "
+              f"[{f['min_ms']:.3f}, {f['max_ms']:.3f}]   vector-unit kernel on f32 rows {s['median_ms']:.3f} ms [{s['min_ms']:.3f}, "
+              f"{s['max_ms']:.3f}]   x{rec['speedup_median']:.2f}   max |diff| {diff:.2e}", flush=True)
+        results.append(rec)
+        del qf, kf, vf, qp, kp, vp, outs, new
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=2048)
@@ -36,9 +96,20 @@ def main():
     ap.add_argument("--hd", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--pair", action="store_true", help="pair-row output (what the model asks for)")
+    ap.add_argument("--cases", default="16:2048:96:96,16:2048:288:256,8:2048:96:96", help="--hd 32: heads:B:T:valid, comma separated")
+    ap.add_argument("--repeats", type=int, default=5, help="--hd 32: timed windows per route, alternating")
+    ap.add_argument("--json", help="--hd 32: append the records of this run to this JSON list")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ops.set_precision(os.environ.get("FB_PREC", "bf16x3"))          # FB_PREC=f16x3: the default mode's element format
+    if a.hd == 32:
+        recs = routes_hd32(a, dev)
+        if a.json:
+            old = json.load(open(a.json)) if os.path.exists(a.json) else []
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(old + recs, f, indent=1)
+        return
     g = torch.Generator(device=dev).manual_seed(1)
     C = a.heads * a.hd
     q, k, v = (to_pair(torch.randn(a.B, a.T, C, device=dev, generator=g)) for _ in range(3))

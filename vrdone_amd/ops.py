@@ -97,7 +97,14 @@ class Pair:
 
 def flash_pair_ok(n_head, channels, Tq):
     """True when global attention of this shape runs the split-precision flash kernel on pair-row q/k/v."""
-    return pair_mode() and channels // n_head in (64, 128) and Tq >= 32
+    hd = channels // n_head
+    # head_dim 32: the three-product modes only (vrd_attention_pair has no one-product form there: f16x1 stays on f32 rows and the
+    # vector-unit kernel).  No higher threshold than 32 query rows: measured per launch (scripts/flash_bench.py --hd 32 --pair, MI355X,
+    # 2048 sequences of T rows, f16x3), this route / attn_small on f32 rows: 16 heads T = 32: 0.17 / 3.9 ms, 64: 0.28 / 13.4,
+    # 96: 0.43 / 30.2, 288 (256 valid): 1.64 / 323; 8 heads T = 32: 0.06 / 1.56, 96: 0.21 / 14.5 (run-to-run spread below 5 %)
+    if hd == 32:
+        return pair_mode() and _precision in ("bf16x3", "f16x3") and Tq >= 32
+    return pair_mode() and hd in (64, 128) and Tq >= 32
 
 
 def pair_mode():
