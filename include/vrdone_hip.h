@@ -622,7 +622,8 @@ int vrd_attn_bwd_softmax(float* P, float* dS, const uint8_t* kv_mask, int B, int
 
 /* Global attention backward without the (B, n_head, Tq, Tk) matrices (round 4): dq, dk, dv from the forward's inputs, its output
  * `out` and dO, the scores recomputed tile by tile in the bf16 split of the other backward GEMMs (two kernels: dq -- which also
- * leaves every query's log-sum-exp and sum_d dO O in `scratch` -- then dk / dv).  head_dim 64; q / out / dO / dq rows of
+ * leaves every query's log-sum-exp and sum_d dO O in `scratch` -- then dk / dv).  head_dim 32 or 64 (any other value is refused
+ * by name); q / out / dO / dq rows of
  * leading dimension ldq / ldo / ldo / ldq, k / v / dk / dv of ldkv; scratch: 2 * B * n_head * Tq floats.  The five-product form
  * above stays for other head sizes and for the exact-f32 mode.
  * o_scale / v_scale (both or neither): vrd_absmax_scale's outputs for dO and v: the products are then formed on f16 planes (the
@@ -634,7 +635,7 @@ int vrd_attention_bwd(const float* q, int64_t ldq, const float* k, const float* 
                       const float* o_scale, const float* v_scale, void* stream);
 /* The forward of that pair for a training step: vrd_attention on f32 rows in split precision (fmt: VRD_PAIR_BF16 / VRD_PAIR_F16 --
  * the operands are split while they are staged, no pair rows), f32 rows out, plus every query's log-sum-exp of the scaled
- * scores, lse (B, n_head, Tq), which the backward then does not recompute.  head_dim 64. */
+ * scores, lse (B, n_head, Tq), which the backward then does not recompute.  head_dim 32 or 64, as vrd_attention_bwd. */
 int vrd_attention_rows(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kv_mask, int B, int Tq,
                        int Tk, int n_head, int head_dim, int fmt, float* out, int64_t ldo, float* lse, void* stream);
 

@@ -10,11 +10,19 @@ through vrd_attention_pair (the split modes' eval route) and the same values as 
 median and spread reported per shape.
 
     python scripts/flash_bench.py --hd 32 [--cases 16:2048:96:96,16:2048:288:256,8:2048:96:96] [--repeats 5] [--json out.json]
+
+--hd 32 --train times one forward + backward of autograd.Attention (ops.attention under autograd) on the flash route of training
+(vrd_attention_rows + vrd_attention_bwd) against the route it replaces (autograd.FUSED_ATTN_BWD = False: the vector-unit forward
+and the five-product backward), in f16x3 and bf16x3, at training-sized shapes; --train-step adds whole training steps of the
+16-head config (scripts/train_step.py --heads 16 in child processes, VRDONE_FUSED_ATTN_BWD=0 / 1 alternating).
+
+    python scripts/flash_bench.py --hd 32 --train [--train-step] [--json profiles/flash_hd32_train_bench.json]
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 
 import torch
@@ -50,7 +58,7 @@ def time_ms(fn, iters):
 def routes_hd32(a, dev):
     """head_dim 32: the pair-row flash route against the f32-row vector-unit route, per case heads:B:T:valid"""
     results = []
-    for case in a.cases.split(","):
+    for case in (a.cases or EVAL_CASES).split(","):
         heads, B, T, valid = (int(x) for x in case.split(":"))
         g = torch.Generator(device=dev).manual_seed(1)
         C = heads * 32
@@ -87,6 +95,80 @@ def routes_hd32(a, dev):
     return results
 
 
+EVAL_CASES = "16:2048:96:96,16:2048:288:256,8:2048:96:96"
+TRAIN_CASES = "16:256:96:96,8:256:96:96,16:48:512:512,16:256:32:32"       # heads:B:T:valid
+
+
+def train_hd32(a, dev):
+    """head_dim 32, forward + backward: the flash route of training against the route it replaces, per case and split mode"""
+    from vrdone_amd import autograd
+    results = []
+    for prec in ("f16x3", "bf16x3"):
+        ops.set_precision(prec)
+        for case in (a.cases or TRAIN_CASES).split(","):
+            heads, B, T, valid = (int(x) for x in case.split(":"))
+            g = torch.Generator(device=dev).manual_seed(1)
+            C = heads * 32
+            q, k, v = (torch.randn(B, T, C, device=dev, generator=g).requires_grad_(True) for _ in range(3))
+            dO = torch.randn(B, T, C, device=dev, generator=g)
+            mask = (torch.arange(T, device=dev)[None] < valid).expand(B, T).contiguous()
+
+            def fwd_bwd(fused):
+                autograd.FUSED_ATTN_BWD = fused
+                with torch.enable_grad():
+                    out = ops.attention(q, k, v, mask, heads)
+                    grads = torch.autograd.grad(out, (q, k, v), dO)
+                return (out.detach(), *grads)
+            routes = {"flash": lambda: fwd_bwd(True), "parent": lambda: fwd_bwd(False)}
+            times, outs = {name: [] for name in routes}, {}
+            try:
+                for name, fn in routes.items():
+                    for _ in range(3):
+                        outs[name] = fn()
+                torch.cuda.synchronize()
+                for _ in range(a.repeats):                      # alternating: a drift of the machine hits both routes alike
+                    for name, fn in routes.items():
+                        times[name].append(time_ms(fn, a.iters))
+            finally:
+                autograd.FUSED_ATTN_BWD = True
+            diff = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(outs["flash"], outs["parent"]))
+            rec = {"heads": heads, "head_dim": 32, "B": B, "T": T, "valid": valid, "precision": prec, "iters": a.iters,
+                   "what": "forward + backward of autograd.Attention", "max_rel_diff": diff}
+            for name, ts in times.items():
+                rec[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+            f, s = rec["flash"], rec["parent"]
+            # beyond the run-to-run spread of the same run: one route's slowest repeat beats the other's fastest
+            rec["flash_wins_beyond_spread"] = f["max_ms"] < s["min_ms"]
+            rec["flash_loses_beyond_spread"] = s["max_ms"] < f["min_ms"]
+            rec["speedup_median"] = s["median_ms"] / f["median_ms"]
+            print(f"{heads:2d} x 32, B {B}, T {T} ({valid} valid), {prec}: flash {f['median_ms']:.3f} ms [{f['min_ms']:.3f}, "
+                  f"{f['max_ms']:.3f}]   parent route {s['median_ms']:.3f} ms [{s['min_ms']:.3f}, {s['max_ms']:.3f}]   "
+                  f"x{rec['speedup_median']:.2f}   max rel diff {diff:.2e}", flush=True)
+            results.append(rec)
+            del q, k, v, dO, outs
+    return results
+
+
+def train_steps(a):
+    """whole training steps of the 16-head config on either route, eager and with the network replayed as HIP graphs:
+    scripts/train_step.py in child processes, the two routes alternating"""
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "train_step.py")
+    doc = {"what": f"scripts/train_step.py --heads 16 --steps {a.steps} [--graphs]: median step_ms after two warm-up steps, one figure per "
+                   "child process, VRDONE_FUSED_ATTN_BWD=0 / 1 alternating; the default precision mode"}
+    for mode, extra in (("eager", []), ("graphs", ["--graphs"])):
+        runs = {"0": [], "1": []}
+        for _ in range(2):
+            for flag in ("0", "1"):
+                env = dict(os.environ, VRDONE_FUSED_ATTN_BWD=flag)
+                out = subprocess.run([sys.executable, script, "--heads", "16", "--steps", str(a.steps), *extra], env=env, check=True,
+                                     capture_output=True, text=True, timeout=300).stdout
+                log = json.loads(out.strip().splitlines()[-1])
+                runs[flag].append(statistics.median(log["step_ms"][2:]))       # (the first steps carry warm-up and graph capture)
+                print(f"train_step --heads 16 ({mode}), VRDONE_FUSED_ATTN_BWD={flag}: median step {runs[flag][-1]:.2f} ms", flush=True)
+        doc[mode] = {"fused_attn_bwd_0_ms": runs["0"], "fused_attn_bwd_1_ms": runs["1"]}
+    return doc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=2048)
@@ -96,12 +178,24 @@ def main():
     ap.add_argument("--hd", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--pair", action="store_true", help="pair-row output (what the model asks for)")
-    ap.add_argument("--cases", default="16:2048:96:96,16:2048:288:256,8:2048:96:96", help="--hd 32: heads:B:T:valid, comma separated")
+    ap.add_argument("--cases", help="--hd 32: heads:B:T:valid, comma separated (default " + EVAL_CASES + "; --train: " + TRAIN_CASES + ")")
+    ap.add_argument("--train", action="store_true", help="--hd 32: forward + backward, the flash route of training against the route it replaces")
+    ap.add_argument("--train-step", action="store_true", help="--hd 32 --train: also whole training steps at 16 heads on either route")
+    ap.add_argument("--steps", type=int, default=12, help="--train-step: steps per child process")
     ap.add_argument("--repeats", type=int, default=5, help="--hd 32: timed windows per route, alternating")
-    ap.add_argument("--json", help="--hd 32: append the records of this run to this JSON list")
+    ap.add_argument("--json", help="--hd 32: append the records of this run to this JSON list (--train: write the run's document there)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ops.set_precision(os.environ.get("FB_PREC", "bf16x3"))          # FB_PREC=f16x3: the default mode's element format
+    if a.hd == 32 and a.train:
+        doc = {"attention": train_hd32(a, dev)}
+        if a.train_step:
+            doc["train_step"] = train_steps(a)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(doc, f, indent=1)
+        return
     if a.hd == 32:
         recs = routes_hd32(a, dev)
         if a.json:

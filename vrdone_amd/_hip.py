@@ -217,6 +217,7 @@ _SIGNATURES = {
     "vrd_attn_bwd_probs": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p]),
     "vrd_bmm": (C.c_int, [C.POINTER(BmmArgs), C.c_void_p]),
+    # the flash pair of a training step (vrd_attn_bwd.hip): head_dim 32 or 64, any other value is refused by name
     "vrd_attention_bwd": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "vrd_attention_rows": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -435,6 +435,17 @@ class LocalAttention(_Differentiable):
         return dq, dk, dv, None, None, None, d_rel
 
 
+def _flash_attention_route(split, head_dim, Tq, Tk):
+    """Whether Attention's forward and backward take the flash kernels on f32 rows (vrd_attention_rows / vrd_attention_bwd, built for
+    head_dim 32 and 64): the one condition of both sites.  FUSED_ATTN_BWD off, the exact f32 mode and f16x1 (`split` false) and
+    fewer than 32 queries or keys keep the generic forward and the five-product backward."""
+    # head_dim 32, forward + backward, flash route against the one it replaces (scripts/flash_bench.py --hd 32 --train, MI355X, median ms,
+    # profiles/flash_hd32_train_bench.json), f16x3 / bf16x3: 256 x 16 heads x 96 rows 0.26 / 0.22 against 4.40 / 4.41; 256 x 8 x 96
+    # 0.14 / 0.16 against 1.98; 48 x 16 x 512 0.63 / 0.55 against 15.1 / 15.2; at the threshold, 256 x 16 x 32, 0.17 / 0.08 against 0.54:
+    # the flash route's slowest window beats the other's fastest at every shape, so head_dim 32 takes the threshold of 64 (32 rows)
+    return bool(FUSED_ATTN_BWD and split and head_dim in (32, 64) and Tq >= 32 and Tk >= 32)
+
+
 class Attention(_Differentiable):
     """Global masked attention (f32 kernels of vrd_attention)."""
 
@@ -443,7 +454,7 @@ class Attention(_Differentiable):
         B, Tq, Cc = q.shape
         Tk = k.shape[1]
         lse = None
-        if (FUSED_ATTN_BWD and ops.split_backward() and Cc // n_head == 64 and Tq >= 32 and Tk >= 32 and
+        if (_flash_attention_route(ops.split_backward(), Cc // n_head, Tq, Tk) and
                 q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
             # the split-precision flash forward on f32 rows (operands split while they are staged), which keeps every query's
             # log-sum-exp for the backward
@@ -466,7 +477,7 @@ class Attention(_Differentiable):
         Tk, H = k.shape[1], ctx.n_head
         hd = Cc // H
         dev = q.device
-        if FUSED_ATTN_BWD and ctx.split_bwd and hd == 64 and Tq >= 32 and Tk >= 32:
+        if _flash_attention_route(ctx.split_bwd, hd, Tq, Tk):
             # flash style (vrd_attention_bwd): the scores are recomputed tile by tile in the split of the other backward GEMMs
             # (bf16 planes; f16x3 mode: f16 planes, dO and dS at power-of-two factors from the absolute maxima of dO and v);
             # no (B, H, Tq, Tk) matrix exists
