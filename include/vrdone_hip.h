@@ -493,6 +493,55 @@ typedef struct {
 } vrd_select_args;
 int vrd_select_triplets(const vrd_select_args* a, void* stream);
 
+/* ---- relation scoring, vrdone_amd/evaluate.py (the eval loop's scoring: reference utils/evaluate.py:77-126 calling
+ * VidVRD-helper's evaluation/visual_relation_detection.py `eval_detection_scores` and evaluation/common.py `viou`) --------------
+ * Added without a version change: a library built before them lacks the two symbols, which the Python binding requires.
+ *
+ * A track is `frames` consecutive rows of a flat (rows, 4) f32 box array (x0, y0, x1, y1), its first row showing frame `first
+ * frame`: duration [first frame, first frame + frames).  A relation -- predicted or ground truth -- is one row of an int64
+ * table [subject's first row, object's first row, first frame, frames]; predictions index pred_boxes, ground truths gt_boxes
+ * (both 16-byte aligned).  Candidate c = [prediction, ground truth] (int32 indices into the two tables).
+ *
+ * Replaces the two `viou` calls per visited (prediction, ground truth) of eval_detection_scores:
+ *   ov[c] = min(vIoU of the subject tracks, vIoU of the object tracks), a double;
+ *   vIoU = overlap / (vol_a + vol_b - overlap): overlap the sum over the shared frames of max(w, 0) * max(h, 0), w = min(x1) -
+ *   max(x0) + 1, h alike; vol the sum of (x1 - x0 + 1) * (y1 - y0 + 1) over the track's whole duration; 0.0 when the durations
+ *   share no frame.  All in f64, every operation rounded (no fused multiply-add); one wave per candidate, lanes striding over
+ *   frames, sums finished in a fixed order: a repeat is bit-equal, and boxes on a quarter-pixel grid below 2048 give the host's
+ *   bits.  Only rows [row, row + frames) of a track are read; a candidate whose indices or rows leave the tables reads nothing
+ *   and gives NaN.  n_cand == 0: nothing is launched. */
+typedef struct {
+    const float* pred_boxes;        /* (pred_rows, 4) */
+    int64_t pred_rows;
+    const float* gt_boxes;          /* (gt_rows, 4) */
+    int64_t gt_rows;
+    const int64_t* pred;            /* (n_pred, 4) */
+    const int64_t* gt;              /* (n_gt, 4) */
+    const int32_t* cand;            /* (n_cand, 2) */
+    int32_t n_pred, n_gt, n_cand;
+    double* ov;                     /* (n_cand) */
+} vrd_viou_args;
+int vrd_relation_viou(const vrd_viou_args* a, void* stream);
+
+/* Replaces the matching loop of eval_detection_scores for n_videos videos in one launch (one wave per video).  Video v owns
+ * predictions pred_first[v] .. pred_first[v + 1] - 1, already in scoring order (descending score, equal scores in their
+ * original order); prediction p owns candidates cand_first[p] .. cand_first[p + 1] - 1 in ascending ground-truth index.
+ * Walking a video's predictions in order, each takes the candidate with the largest ov among those whose ground truth is not
+ * yet detected and whose ov >= threshold (equal ov: the lower ground-truth index), marks that ground truth detected and stores
+ * hit[p] = its index, or -1.  detected: n_gt bytes of scratch, cleared by the kernel for the ground truths the candidates
+ * name; a ground truth must be named by the candidates of one video only.  No videos or no predictions: nothing is launched. */
+typedef struct {
+    const int32_t* pred_first;      /* (n_videos + 1) */
+    const int32_t* cand_first;      /* (n_pred + 1) */
+    const int32_t* cand;            /* (n_cand, 2) */
+    const double* ov;               /* (n_cand) */
+    int32_t n_videos, n_pred, n_cand, n_gt;
+    double threshold;
+    uint8_t* detected;              /* (n_gt) scratch */
+    int32_t* hit;                   /* (n_pred) */
+} vrd_match_args;
+int vrd_match_relations(const vrd_match_args* a, void* stream);
+
 /* ====================================================================================================================
  * Backward kernels (training step: the reference differentiates its ATen graph with autograd, train.py:186;
  * models/maskvrd.py:168-198).  All f32 rows (no pair rows).  Parameter gradients are ACCUMULATED (+=) into buffers the

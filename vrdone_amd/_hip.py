@@ -146,6 +146,18 @@ class SelectArgs(C.Structure):                        # vrd_select_args
                 ("out_count", c_i32p), ("out_index", c_i32p), ("out_score", c_f32p)]
 
 
+class ViouArgs(C.Structure):                          # vrd_viou_args
+    _fields_ = [("pred_boxes", c_f32p), ("pred_rows", C.c_int64), ("gt_boxes", c_f32p), ("gt_rows", C.c_int64),
+                ("pred", C.c_void_p), ("gt", C.c_void_p), ("cand", c_i32p),
+                ("n_pred", C.c_int32), ("n_gt", C.c_int32), ("n_cand", C.c_int32), ("ov", C.c_void_p)]
+
+
+class MatchArgs(C.Structure):                         # vrd_match_args
+    _fields_ = [("pred_first", c_i32p), ("cand_first", c_i32p), ("cand", c_i32p), ("ov", C.c_void_p),
+                ("n_videos", C.c_int32), ("n_pred", C.c_int32), ("n_cand", C.c_int32), ("n_gt", C.c_int32),
+                ("threshold", C.c_double), ("detected", c_u8p), ("hit", c_i32p)]
+
+
 class AssembleArgs(C.Structure):
     _fields_ = [("streams", c_f32p), ("snippets", c_f32p), ("stream_row", C.c_void_p), ("lens", C.c_void_p),
                 ("P", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("L", C.c_int32), ("piece", C.c_int32), ("reach", C.c_int32),
@@ -195,6 +207,9 @@ _SIGNATURES = {
     "vrd_postprocess": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_i32p,
                                   c_i32p, c_i32p, C.c_void_p]),
     "vrd_select_triplets": (C.c_int, [C.POINTER(SelectArgs), C.c_void_p]),
+    # ---- relation scoring (csrc/vrd_score.hip; vrdone_amd/evaluate.py DeviceRelationScorer)
+    "vrd_relation_viou": (C.c_int, [C.POINTER(ViouArgs), C.c_void_p]),
+    "vrd_match_relations": (C.c_int, [C.POINTER(MatchArgs), C.c_void_p]),
     # ---- backward kernels (training step)
     "vrd_gemm_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                  c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),

@@ -167,6 +167,11 @@ class MaskVRD(nn.Module):
     # 226 pairs 12.2 / 11.9, 540 pairs 18.9 / 23.1 (profiles/r06_forward_test_small.json)
     ROWS_MIN_PAIRS = int(os.environ.get("VRDONE_ROWS_MIN_PAIRS", "256"))
 
+    # forward_test / forward_test_videos build the winners' box tracks (`so_trajs`, ~100 k Python lists per video) only while
+    # this is True.  A caller that scores on the device (evaluate.DeviceRelationScorer reads the tracklet boxes where they
+    # are) sets it to False on its model: the key is then absent and every other key unchanged
+    with_so_trajs = True
+
     def _eval_rows_form(self, n_pairs):
         return self.row_space and not self.use_abs_pe and n_pairs >= self.ROWS_MIN_PAIRS
 
@@ -779,15 +784,16 @@ class MaskVRD(nn.Module):
                             so_start[pp] + st, so_start[pp] + en,
                             so_start[pp] - durs[sel_s, 0] + st, so_start[pp] - durs[sel_o, 0] + st, en - st],
                            dim=1).cpu().tolist()
-        so_trajs = self._so_trajs(input_data['bboxes_list'], host)
-        return {
+        out = {
             "triplets": [r[2:5] for r in host],
             "triple_scores": tri[order].cpu().tolist(),
             "triple_scores_avg": avg[order].cpu().tolist(),
-            "so_trajs": so_trajs,
-            "pred_durations": [r[5:7] for r in host],
-            "so_tids": [r[0:2] for r in host],
         }
+        if self.with_so_trajs:
+            out["so_trajs"] = self._so_trajs(input_data['bboxes_list'], host)
+        out["pred_durations"] = [r[5:7] for r in host]
+        out["so_tids"] = [r[0:2] for r in host]
+        return out
 
     @staticmethod
     def _so_trajs(boxes, host):
@@ -939,12 +945,14 @@ class MaskVRD(nn.Module):
                              so_start[pp] + st, so_start[pp] + en,
                              so_start[pp] - durs[sel_s, 0] + st, so_start[pp] - durs[sel_o, 0] + st, en - st], axis=1).tolist()
             tri = np.stack([cat_scores[sel_s], p_score[j, :n], cat_scores[sel_o]], axis=1)
-            results[i] = {
+            out = {
                 "triplets": [r[2:5] for r in rows],
                 "triple_scores": tri.tolist(),
                 "triple_scores_avg": avg[j, :n].tolist(),
-                "so_trajs": self._so_trajs(videos[i]['bboxes_list'], rows),
-                "pred_durations": [r[5:7] for r in rows],
-                "so_tids": [r[0:2] for r in rows],
             }
+            if self.with_so_trajs:
+                out["so_trajs"] = self._so_trajs(videos[i]['bboxes_list'], rows)
+            out["pred_durations"] = [r[5:7] for r in rows]
+            out["so_tids"] = [r[0:2] for r in rows]
+            results[i] = out
         return results

@@ -1209,3 +1209,46 @@ def select_triplets(cand, s_score, o_score, so_offset, so_start, so_end, video_p
     a.out_count, a.out_index, a.out_score = count.data_ptr(), index.data_ptr(), score.data_ptr()
     _hip.check(lib.vrd_select_triplets(C.byref(a), _stream()), "vrd_select_triplets")
     return count, index, score
+
+
+def relation_viou(pred_boxes, pred, gt_boxes, gt, cand):
+    """ov (n_cand,) float64 = min(subject vIoU, object vIoU) of every (prediction, ground truth) candidate (vrd_relation_viou):
+    evaluate.viou's formula in f64, one wave per candidate.  pred_boxes / gt_boxes: (rows, 4) f32 flat box arrays; pred / gt:
+    (n, 4) int64 relation tables [subject's first row, object's first row, first frame, frames]; cand: (n_cand, 2) int32
+    [prediction, ground truth] -- all contiguous, on the device."""
+    for t in (pred_boxes, gt_boxes):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 4 and t.is_contiguous()
+    for t in (pred, gt):
+        assert t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 4 and t.is_contiguous()
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[1] == 2 and cand.is_contiguous()
+    # (the kernel reads a box as one 16-byte load; a view that starts off that alignment is copied)
+    pred_boxes, gt_boxes = (t.clone() if t.data_ptr() % 16 else t for t in (pred_boxes, gt_boxes))
+    ov = torch.empty(cand.shape[0], device=cand.device, dtype=torch.float64)
+    a = _hip.ViouArgs()
+    a.pred_boxes, a.pred_rows, a.gt_boxes, a.gt_rows = pred_boxes.data_ptr(), pred_boxes.shape[0], gt_boxes.data_ptr(), gt_boxes.shape[0]
+    a.pred, a.gt, a.cand = pred.data_ptr(), gt.data_ptr(), cand.data_ptr()
+    a.n_pred, a.n_gt, a.n_cand, a.ov = pred.shape[0], gt.shape[0], cand.shape[0], ov.data_ptr()
+    _hip.check(lib.vrd_relation_viou(C.byref(a), _stream()), "vrd_relation_viou")
+    return ov
+
+
+def match_relations(pred_first, cand_first, cand, ov, n_gt, threshold):
+    """hit (n_pred,) int32: eval_detection_scores' greedy matching for every video of the call in one launch
+    (vrd_match_relations).  pred_first (n_videos + 1,) int32: video v owns predictions pred_first[v] .. pred_first[v + 1] - 1,
+    in scoring order; cand_first (n_pred + 1,) int32: prediction p owns candidates cand_first[p] .. cand_first[p + 1] - 1, in
+    ascending ground-truth index; cand (n_cand, 2) int32; ov (n_cand,) float64; n_gt: rows of the ground-truth table.
+    hit[p] = the matched ground truth, -1 for a miss."""
+    for t in (pred_first, cand_first):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.shape[0] >= 1 and t.is_contiguous()
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[1] == 2 and cand.is_contiguous()
+    assert ov.dtype == torch.float64 and ov.shape == (cand.shape[0],) and ov.is_contiguous()
+    dev = pred_first.device
+    n_pred = cand_first.shape[0] - 1
+    hit = torch.full((n_pred,), -1, device=dev, dtype=torch.int32)
+    detected = torch.empty(n_gt, device=dev, dtype=torch.uint8)
+    a = _hip.MatchArgs()
+    a.pred_first, a.cand_first, a.cand, a.ov = pred_first.data_ptr(), cand_first.data_ptr(), cand.data_ptr(), ov.data_ptr()
+    a.n_videos, a.n_pred, a.n_cand, a.n_gt = pred_first.shape[0] - 1, n_pred, cand.shape[0], n_gt
+    a.threshold, a.detected, a.hit = float(threshold), detected.data_ptr(), hit.data_ptr()
+    _hip.check(lib.vrd_match_relations(C.byref(a), _stream()), "vrd_match_relations")
+    return hit

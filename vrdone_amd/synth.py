@@ -105,3 +105,47 @@ def synth_raw_video(n_tracklets, n_visual, min_len, max_len, seed=7, n_clip=0, w
     if n_clip:
         out["clip_features_list"] = clip
     return out
+
+
+def synth_relation_ground_truth(video_names, videos, results, entity_id_to_name, pred_id_to_name, per_video=20, seed=0,
+                                absent_predicate=0):
+    """A ground-truth relation file ({video: [{triplet, duration, sub_traj, obj_traj}]}, what evaluate.eval_relation loads) made
+    from a model's own predictions, so that scoring them finds hits and misses: per video `per_video` relations in five kinds,
+    taken from predictions spread over the ranks --
+      0  the prediction's own tracks (vIoU 1);  1  both tracks moved by ~1/8 of the box width (vIoU ~0.78);
+      2  both tracks moved by ~2/3 of the box width (vIoU ~0.2);  3  kind 1 again for the same prediction, shorter by its last
+      quarter (a second ground truth of one triplet);  4  a triplet with the predicate `absent_predicate`, which no prediction has.
+    videos: the proposals (`bboxes_list`, `traj_durations`); results: forward_test's (`so_tids`, `pred_durations`, `triplets`);
+    a None result gives an empty list.  Shifts are whole quarter pixels, so boxes on a quarter-pixel grid stay on it."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for name, video, res in zip(video_names, videos, results):
+        rels = out[name] = []
+        if res is None:
+            continue
+        n = len(res["triplets"])
+        spans = torch.as_tensor(video["traj_durations"]).cpu().tolist()
+        picks = torch.randperm(n, generator=g)[:per_video].sort().values.tolist()
+        for j, i in enumerate(picks):
+            kind = j % 5
+            (s, o), (start, end) = res["so_tids"][i], res["pred_durations"][i]
+            tracks = [video["bboxes_list"][t].cpu()[start - spans[t][0]:end - spans[t][0]].clone() for t in (s, o)]
+            triplet = list(res["triplets"][i])
+            if kind == 4:
+                triplet[1] = absent_predicate
+            if kind in (1, 2, 3):
+                for t in tracks:
+                    width = float((t[:, 2] - t[:, 0] + 1).mean())
+                    dx = round(width * (2 / 3 if kind == 2 else 1 / 8) * 4) / 4
+                    t[:, 0] += dx
+                    t[:, 2] += dx
+            if kind == 3:
+                end = max(start + 1, end - (end - start) // 4)
+                tracks = [t[:end - start] for t in tracks]
+            rels.append({"triplet": [entity_id_to_name[triplet[0]], pred_id_to_name[triplet[1]], entity_id_to_name[triplet[2]]],
+                         "duration": [start, end], "sub_traj": tracks[0].tolist(), "obj_traj": tracks[1].tolist()})
+            if kind == 3:                  # ... and the same prediction's kind-1 relation over the whole duration next to it
+                rels.append(dict(rels[-1], duration=list(res["pred_durations"][i]),
+                                 sub_traj=tracks[0].tolist() + [tracks[0][-1].tolist()] * (res["pred_durations"][i][1] - end),
+                                 obj_traj=tracks[1].tolist() + [tracks[1][-1].tolist()] * (res["pred_durations"][i][1] - end)))
+    return out
