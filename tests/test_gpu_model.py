@@ -968,11 +968,13 @@ def test_full_size_properties():
     assert torch.equal(rev["pred_masks"].flip(0), out["pred_masks"])
 
 
-@pytest.mark.parametrize("B,T", [(384, 512), (4096, 512)])
+@pytest.mark.parametrize("B,T", [(384, 512), (4096, 512), (2560, 512)])
 def test_full_size_properties_vidor_x(B, T):
     """BASELINE config 5 (vidor_x.yaml: C_in 3093 with the CLIP slabs, 8 heads, window 9), at its full 4096 pairs x 512
-    frames (26 GB of input, two 2048-pair chunks) and at 384 pairs: finite outputs, -10 on masked frames, and rows equal to a
-    3-pair run of the small-shape kernels."""
+    frames (26 GB of input, two 2048-pair chunks), at 384 pairs, and at 2560 pairs -- the largest single wave (MaskVRD._chunk_size),
+    the only shape whose 512-wide buffers cross 2^32 bytes: finite outputs, -10 on masked frames, and rows equal to a
+    3-pair run of the small-shape kernels -- the first pairs, the pairs on both sides of the wave boundary and the last pairs, which
+    lie at the far end of every buffer.  The single wave also gives, for the reversed batch, the reversed outputs bit for bit."""
     model, mc, _, _ = get_model("vidor_x")
     gen = torch.Generator(device=DEV).manual_seed(15)
     lens = torch.randint(2, T + 1, (B,), generator=torch.Generator().manual_seed(16))
@@ -987,6 +989,18 @@ def test_full_size_properties_vidor_x(B, T):
     small = model._mask_vrd(x[:3].contiguous(), m[:3].contiguous(), with_aux=False)
     close(small["pred_logits"], out["pred_logits"][:3], 1e-5)
     close(small["pred_masks"], out["pred_masks"][:3], 1e-4)
+    if B >= 2560:
+        groups = [slice(B - 3, B)] + ([slice(2046, 2050)] if B == 4096 else [])
+        for sl in groups:
+            small = model._mask_vrd(x[sl].contiguous(), m[sl].contiguous(), with_aux=False)
+            close(small["pred_logits"], out["pred_logits"][sl], 1e-5)
+            close(small["pred_masks"], out["pred_masks"][sl], 1e-4)
+    if B == 2560:
+        assert model._chunk_size(B) == B
+        rev = model._mask_vrd(x.flip(0), m.flip(0), with_aux=False)
+        assert torch.equal(rev["pred_logits"].flip(0), out["pred_logits"])
+        assert torch.equal(rev["pred_masks"].flip(0), out["pred_masks"])
+        del rev
     del x, out
     torch.cuda.empty_cache()
 
