@@ -444,6 +444,18 @@ int vrd_attention_pair(const float* q, int64_t ldq, const float* k, const float*
                        const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, int head_dim,
                        float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream, int products);
 
+/* The same over two ragged row spaces in one call: q / out are rows laid out by qsegs, k / v rows laid out by ksegs (host memory,
+ * as for vrd_local_attn_segs; equal count and equal n[i]).  Group i is vrd_attention_pair with B = n[i], Tq = qsegs->T[i],
+ * Tk = ksegs->T[i] on the operands from row qsegs->row[i] / ksegs->row[i] on, bit for bit; rows no group names are neither read nor
+ * written.  kv_mask / q_mask: one byte per row of the key / query row space, or NULL.  Every group runs the kernel its own call
+ * would run, so the call is one launch, or two where the groups fall on both sides of that choice.  The checks are those of
+ * vrd_attention_pair per group (Tk <= 4096), and: count in 1 .. VRD_MAX_SEGS, tables that agree, every n and T > 0. */
+int vrd_attention_pair_segs(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
+                            const uint8_t* kv_mask, const uint8_t* q_mask,
+                            const vrd_row_segs* qsegs, const vrd_row_segs* ksegs,
+                            int n_head, int head_dim, float* out, int64_t ldo,
+                            int out_pair, int pair_fmt, void* stream, int products);
+
 /* ---- MaxPool1d(3,2,1) skip * mask (models/blocks.py:1040-1046,1074) and mask[::2] ------- */
 int vrd_maxpool_mask(const float* x, int64_t ldx, int B, int Tin, int C, const uint8_t* mask_in,
                      float* y, int64_t ldy, uint8_t* mask_out, void* stream);

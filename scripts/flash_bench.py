@@ -17,6 +17,14 @@ and the five-product backward), in f16x3 and bf16x3, at training-sized shapes; -
 16-head config (scripts/train_step.py --heads 16 in child processes, VRDONE_FUSED_ATTN_BWD=0 / 1 alternating).
 
     python scripts/flash_bench.py --hd 32 --train [--train-step] [--json profiles/flash_hd32_train_bench.json]
+
+--segs times global attention over the bucket table of the benchmark's ragged variant (2048 pairs, lengths U[2, 256] at T_pad 288,
+the vidvrd model's tight-padding buckets) as ragged.attention issues it: the per-bucket loop over its side streams against the
+buckets as the row groups of ONE call (vrd_attention_pair_segs), the latter with either item order of the persistent kernel
+(VRD_FLASH_WALK=0: strided over the groups sorted by cost; 1: contiguous runs cut by cumulative cost).  vidvrd's 4 heads x 128
+and vidor_x's 8 heads x 64, alternating in one process, medians and spread over --repeats windows.
+
+    python scripts/flash_bench.py --segs [--repeats 7] [--json profiles/attn_segs_bench.json]
 """
 import argparse
 import json
@@ -169,6 +177,69 @@ def train_steps(a):
     return doc
 
 
+def segs_bench(a, dev):
+    """the per-bucket loop of ragged.attention against the one call over the buckets as row groups, on the ragged benchmark's table"""
+    from vrdone_amd import configs
+    from vrdone_amd.models import ragged
+    from vrdone_amd.models.maskvrd import MaskVRD
+    pairs, frames, t_pad = 2048, 256, 288
+    lens = torch.randint(2, frames + 1, (pairs,), generator=torch.Generator().manual_seed(1235))          # bench.py's ragged leg
+    lens[0] = frames
+    lens = lens.tolist()
+    model = MaskVRD(configs.model_config("vidvrd"), device="cpu")
+    want = {}
+    for i, t2 in enumerate(model.tight_buckets(lens, [t_pad] * pairs, model.ROWS_MIN_ROWS)):          # MaskVRD._tight_plan's buckets
+        want.setdefault((lens[i] <= t2 - 2, t2), []).append(i)
+    order = sorted(want, key=lambda k: (not k[0], k[1]))
+    lay = ragged.Layout([(len(want[key]), key[1], key[0]) for key in order])
+    valid = torch.cat([(torch.arange(key[1])[None] < torch.tensor([lens[i] for i in want[key]])[:, None]).reshape(-1) for key in order])[None]
+    mask = valid.to(dev).contiguous()
+    results = []
+    for heads, hd, what in ((4, 128, "vidvrd"), (8, 64, "vidor_x")):
+        C = heads * hd
+        g = torch.Generator(device=dev).manual_seed(1)
+        q, k, v = (to_pair(torch.randn(1, lay.rows, C, device=dev, generator=g)) for _ in range(3))
+
+        def route(on, walk):
+            def fn():
+                ragged.ATTN_SEGS = on
+                if walk is None:
+                    os.environ.pop("VRD_FLASH_WALK", None)
+                else:
+                    os.environ["VRD_FLASH_WALK"] = walk
+                return ragged.attention(q, k, v, mask, mask, heads, lay, lay, pair=True)
+            return fn
+        routes = {"bucket_loop": route(False, None), "segs_strided_sorted": route(True, "0"), "segs_contiguous_by_cost": route(True, "1")}
+        times, outs = {name: [] for name in routes}, {}
+        try:
+            with torch.no_grad():
+                for name, fn in routes.items():
+                    for _ in range(3):
+                        outs[name] = fn()
+                torch.cuda.synchronize()
+                for _ in range(a.repeats):                      # alternating: a drift of the machine hits every route alike
+                    for name, fn in routes.items():
+                        times[name].append(time_ms(fn, a.iters))
+        finally:
+            ragged.ATTN_SEGS = False
+            os.environ.pop("VRD_FLASH_WALK", None)
+        same = all(torch.equal(outs["bucket_loop"].t.view(torch.int32), o.t.view(torch.int32)) for o in outs.values())
+        rec = {"what": f"global attention over the ragged benchmark's bucket table, {what} shape", "heads": heads, "head_dim": hd,
+               "pairs": pairs, "lengths": f"U[2, {frames}] (seed 1235)", "T_pad": t_pad, "rows": lay.rows,
+               "groups": [[n, T] for _, n, T in lay.segs], "precision": ops.get_precision(), "iters": a.iters, "repeats": a.repeats,
+               "side_streams": ragged.ATTN_LANES, "bit_equal": same}
+        for name, ts in times.items():
+            rec[name] = {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+        b = rec["bucket_loop"]
+        print(f"{what}: {heads} x {hd}, {len(lay.segs)} groups, {lay.rows} rows, {rec['precision']}, outputs bit-equal: {same}", flush=True)
+        for name in routes:
+            r = rec[name]
+            print(f"  {name:24s} {r['median_ms']:7.3f} ms [{r['min_ms']:.3f}, {r['max_ms']:.3f}]   x{b['median_ms'] / r['median_ms']:.2f}", flush=True)
+        results.append(rec)
+        del q, k, v, outs
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=2048)
@@ -184,9 +255,19 @@ def main():
     ap.add_argument("--steps", type=int, default=12, help="--train-step: steps per child process")
     ap.add_argument("--repeats", type=int, default=5, help="--hd 32: timed windows per route, alternating")
     ap.add_argument("--json", help="--hd 32: append the records of this run to this JSON list (--train: write the run's document there)")
+    ap.add_argument("--segs", action="store_true", help="the ragged benchmark's bucket table: per-bucket loop against one row-group call")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ops.set_precision(os.environ.get("FB_PREC", "bf16x3"))          # FB_PREC=f16x3: the default mode's element format
+    if a.segs:
+        recs = segs_bench(a, dev)
+        if a.json:
+            doc = json.load(open(a.json)) if os.path.exists(a.json) else {}
+            doc.setdefault("kernel_level", []).extend(recs)
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump(doc, f, indent=1)
+        return
     if a.hd == 32 and a.train:
         doc = {"attention": train_hd32(a, dev)}
         if a.train_step:

@@ -200,6 +200,9 @@ _SIGNATURES = {
                                 C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vrd_attention_pair": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, c_u8p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "vrd_attention_pair_segs": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, c_u8p, C.POINTER(RowSegs),
+                                          C.POINTER(RowSegs), C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_int]),
     "vrd_maxpool_mask": (C.c_int, [c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, c_u8p, c_f32p, C.c_int64, c_u8p,
                                    C.c_void_p]),
     "vrd_mask_head": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -35,6 +35,7 @@
 // subnormals kept; P <= 1 -- <= 2^8 with the second kernel's deferred rescaling -- so P * 2^4 is far inside the f16 range);
 // the softmax, its running sums and maxima stay f32.  The lo planes still arrive in LDS but are not read.
 #include "vrd_common.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -67,13 +68,35 @@ struct AG {
     }
 };
 
-template <int HD, int NW, bool F16, int NPROD = 3>
+// The row groups of one launch of vrd_attention_pair_segs, in the kernel arguments (SEGS instantiations; the (B, T) form gets an
+// empty struct): group g holds sequences of Tq[g] query and Tk[g] key rows from row qrow[g] / krow[g] of their row spaces on, and
+// owns the work units [end[g-1], end[g]) of the launch -- (b, h) items of the second kernel; for the first kernel the slots of ONE
+// XCD's share of the workgroups (see there), units[g] workgroups in all.  A workgroup finds its unit's group by a scalar walk over
+// `end`; everything it reads here is wave-uniform.
+struct AttnSegs {
+    int count, nkt_max, nqg_max;                  // groups; the largest group's key tiles / 32-query groups (LDS layout)
+    int cost[VRD_MAX_SEGS];                       // of one item of the group (key tiles x query groups): the contiguous walk's cuts
+    int units[VRD_MAX_SEGS];                      // first kernel: workgroups of the group (q-blocks x heads x sequences)
+    int end[VRD_MAX_SEGS], Tq[VRD_MAX_SEGS], Tk[VRD_MAX_SEGS];
+    int64_t qrow[VRD_MAX_SEGS], krow[VRD_MAX_SEGS];
+};
+struct NoSegs {};
+template <bool SEGS>
+using SegArg = std::conditional_t<SEGS, AttnSegs, NoSegs>;
+__device__ __forceinline__ int seg_of(const AttnSegs& sg, int unit) {
+    int g = 0;
+    while (g + 1 < sg.count && unit >= sg.end[g]) ++g;
+    return g;
+}
+
+template <int HD, int NW, bool F16, int NPROD = 3, bool SEGS = false>
 __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* __restrict__ q, int64_t ldq,
                                                                 const float* __restrict__ k, const float* __restrict__ v,
                                                                 int64_t ldkv, const uint8_t* __restrict__ kv_mask,
                                                                 const uint8_t* __restrict__ q_mask, int Tq,
                                                                 int Tk, int width, float scale, float* __restrict__ out,
-                                                                int64_t ldo, int pair_out, int q_blocks, int n_head_) {
+                                                                int64_t ldo, int pair_out, int q_blocks, int n_head_,
+                                                                const SegArg<SEGS> sg) {
     using G = AG<HD>;
     typedef typename vrd::SplitFmt<F16>::x8 bf16x8;      // eight 16-bit elements of this instantiation's format (bf16 or f16)
     static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
@@ -91,7 +114,29 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_flash_x3_kernel(const float* 
     // (4.2 GB fetched per launch against 1.8 GB of q, k, v).
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, qq = nwg >> 3, rem = nwg & 7;
-    const int lid = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + (bid >> 3);
+    int lid = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + (bid >> 3);
+    if constexpr (SEGS) {
+        // Groups differ in cost, so the renumbering above -- an eighth of the GRID per XCD -- would hand one XCD the long groups and
+        // another the short ones (measured on the ragged benchmark's table: 0.80 ms against 0.70 for the per-group launches).  Here
+        // every XCD takes an eighth of EVERY group: group g has end[g] - end[g-1] slots per XCD (its workgroups / 8, rounded up),
+        // slot j of XCD x is the group's workgroup x * slots + j -- consecutive ones still share an XCD -- and the few slots past the
+        // group's last workgroup leave at once (the whole workgroup, before any barrier).
+        const int j = bid >> 3;
+        const int g = seg_of(sg, j);
+        const int j0 = g ? sg.end[g - 1] : 0;
+        lid = xcd * (sg.end[g] - j0) + (j - j0);
+        if (lid >= sg.units[g]) return;
+        // the workgroup's group: its lengths and its rows take the place of the call's (the sequence index b counts inside the group)
+        Tq = sg.Tq[g];
+        Tk = sg.Tk[g];
+        q_blocks = ((Tq + 31) / 32 + NW - 1) / NW;
+        q += sg.qrow[g] * ldq;
+        out += sg.qrow[g] * ldo;
+        k += sg.krow[g] * ldkv;
+        v += sg.krow[g] * ldkv;
+        if (kv_mask) kv_mask += sg.krow[g];
+        if (q_mask) q_mask += sg.qrow[g];
+    }
     const int qblk = lid % q_blocks, h = (lid / q_blocks) % n_head_, b = lid / (q_blocks * n_head_);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -443,13 +488,14 @@ __device__ unsigned long long g_attn_stamp[65];
 #define VRD_STAMP(i) do { } while (0)
 #endif
 
-template <int HD, bool F16, int NPROD = 3>
+template <int HD, bool F16, int NPROD = 3, bool SEGS = false>
 __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* __restrict__ q, int64_t ldq,
                                                                   const float* __restrict__ k, const float* __restrict__ v,
                                                                   int64_t ldkv, const uint8_t* __restrict__ kv_mask,
                                                                   const uint8_t* __restrict__ q_mask, int Tq, int Tk, int width,
                                                                   float scale_log2e, float* __restrict__ out, int64_t ldo,
-                                                                  int pair_out, int q_blocks, int n_head_, int n_batch, int prefetch, int item_step) {
+                                                                  int pair_out, int q_blocks, int n_head_, int n_batch, int prefetch, int item_step,
+                                                                  const SegArg<SEGS> sg) {
     using G = AG<HD>;
     static_assert(NPROD == 3 || (NPROD == 1 && F16), "the one-product form exists for the f16 format only");
     // NPROD = 1: of the six MFMAs of a gap group only the two hi x hi ones (j = 4, 5) are issued; the softmax pieces keep their
@@ -473,12 +519,20 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
     char* const lds = reinterpret_cast<char*>(smem);
     // behind the ring: key bias of the item's row of tiles, per tile whether none / some / all of its keys are valid, per group
     // of 32 queries whether any is live; then (prefetch mode) the NEXT item's mask bytes as LDS-DMA leaves them, a dword each
-    const int nkt = (Tk + 31) / 32, nqg = (Tq + 31) / 32;
+    // (SEGS: Tq, Tk, nkt, nqg, q_blocks and the operand pointers are those of the item's group, set at the top of the item loop;
+    // the tables keep ONE layout, that of the launch's largest group -- the next item's mask bytes land while this item's tables
+    // are in use, so neither may move with the item)
+    int nkt = (Tk + 31) / 32, nqg = (Tq + 31) / 32;
+    int lay_k = nkt, lay_q = nqg;
+    if constexpr (SEGS) {
+        lay_k = sg.nkt_max;
+        lay_q = sg.nqg_max;
+    }
     float* const kbias = reinterpret_cast<float*>(lds + NS * G::STAGE);      // [32 * nkt]: 0 or -inf per key
-    int* const tile_on = reinterpret_cast<int*>(kbias + nkt * 32);           // [nkt]
-    int* const qgrp = tile_on + nkt;                                         // [nqg]
-    const int nk64 = (nkt * 32 + 63) & ~63, nq64 = (nqg * 32 + 63) & ~63;
-    int* const raw_k = qgrp + nqg;                                           // [nk64]  (prefetch mode only)
+    int* const tile_on = reinterpret_cast<int*>(kbias + lay_k * 32);         // [nkt]
+    int* const qgrp = tile_on + lay_k;                                       // [nqg]
+    const int nk64 = (lay_k * 32 + 63) & ~63;
+    int* const raw_k = qgrp + lay_q;                                         // [nk64]  (prefetch mode only)
     int* const raw_q = raw_k + nk64;                                         // [nq64]
 #ifdef VRD_ATTN_STAMP
     unsigned long long* const stamp_lds = reinterpret_cast<unsigned long long*>(lds + 163840 - 64 * 8);
@@ -498,7 +552,15 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
     // bytes are requested by LDS-DMA (global_load_lds_ubyte: a dword per byte, no registers held) before the item's first
     // tile, land under its tile loop -- the vector-memory counter is in order: every counted wait for a tile covers them --
     // and are turned into the three tables between two barriers at the start of their item.
-    const int n_items = n_head_ * n_batch;
+    int n_items = n_head_ * n_batch;
+    if constexpr (SEGS) n_items = sg.end[sg.count - 1];
+    // (SEGS) the operands of the call; q, k, v, out and the masks themselves point at the item's group
+    const float* const q_all = q;
+    const float* const k_all = k;
+    const float* const v_all = v;
+    float* const out_all = out;
+    const uint8_t* const kvm_all = kv_mask;
+    const uint8_t* const qm_all = q_mask;
     bool masks_pending = true;                    // mask bytes requested that no wait of this wave has covered yet
     // (per-lane values of the mask staging are formed from a lane id read afresh: as loop invariants the compiler computed
     // them once, spilled them -- every register is spoken for in the tile loop -- and reloaded them at the start of each
@@ -509,33 +571,84 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
         return ln;
     };
     auto dma_masks = [&](int it2) {
-        const int b2 = it2 / n_head_;
+        int b2 = it2 / n_head_, Tk2 = Tk, Tq2 = Tq;      // the item's sequence and lengths
+        const uint8_t *kvm2 = kv_mask, *qm2 = q_mask;
+        if constexpr (SEGS) {                            // ... looked up in ITS group, which need not be the current item's
+            const int g2 = seg_of(sg, it2);
+            b2 = (it2 - (g2 ? sg.end[g2 - 1] : 0)) / n_head_;
+            Tk2 = sg.Tk[g2];
+            Tq2 = sg.Tq[g2];
+            kvm2 = kvm_all ? kvm_all + sg.krow[g2] : nullptr;
+            qm2 = qm_all ? qm_all + sg.qrow[g2] : nullptr;
+        }
+        const int nk64_2 = (((Tk2 + 31) / 32) * 32 + 63) & ~63, nq64_2 = (((Tq2 + 31) / 32) * 32 + 63) & ~63;
         const int ln = fresh_lane();
-        if (kv_mask) {
-            const uint8_t* base = kv_mask + (int64_t)b2 * Tk;
-            for (int j = wave; j < nk64 / 64; j += 4) {
+        if (kvm2) {
+            const uint8_t* base = kvm2 + (int64_t)b2 * Tk2;
+            for (int j = wave; j < nk64_2 / 64; j += 4) {
                 const int key = j * 64 + ln;
-                const unsigned voff = (unsigned)(key < Tk ? key : Tk - 1);
+                const unsigned voff = (unsigned)(key < Tk2 ? key : Tk2 - 1);
                 const unsigned dst = lds_base + (unsigned)(reinterpret_cast<char*>(raw_k) - lds) + j * 256;
                 asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_ubyte %1, %2" ::"s"(dst), "v"(voff), "s"(base) : "memory");
             }
         }
-        if (q_mask) {
-            const uint8_t* base = q_mask + (int64_t)b2 * Tq;
-            for (int j = wave; j < nq64 / 64; j += 4) {
+        if (qm2) {
+            const uint8_t* base = qm2 + (int64_t)b2 * Tq2;
+            for (int j = wave; j < nq64_2 / 64; j += 4) {
                 const int r = j * 64 + ln;
-                const unsigned voff = (unsigned)(r < Tq ? r : Tq - 1);
+                const unsigned voff = (unsigned)(r < Tq2 ? r : Tq2 - 1);
                 const unsigned dst = lds_base + (unsigned)(reinterpret_cast<char*>(raw_q) - lds) + j * 256;
                 asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_ubyte %1, %2" ::"s"(dst), "v"(voff), "s"(base) : "memory");
             }
         }
     };
     // item walk: strided (item_step = grid) or, item_step = 1, a contiguous run of items per workgroup
-    const int item_first = item_step == 1 ? (int)(((long long)n_items * blockIdx.x) / gridDim.x) : (int)blockIdx.x;
-    const int item_end = item_step == 1 ? (int)(((long long)n_items * (blockIdx.x + 1)) / gridDim.x) : n_items;
+    int item_first = item_step == 1 ? (int)(((long long)n_items * blockIdx.x) / gridDim.x) : (int)blockIdx.x;
+    int item_end = item_step == 1 ? (int)(((long long)n_items * (blockIdx.x + 1)) / gridDim.x) : n_items;
+    if constexpr (SEGS) {
+        // Groups differ in length, so equal item counts are not equal work.  The host sorts the groups by cost, dearest first:
+        // the strided walk then starts the longest sequences first; the contiguous walk cuts the item row where the
+        // cumulative cost (items x key tiles x query groups) passes w / grid of the total -- a cut falls on an item
+        // boundary, cut(0) = 0, cut(grid) = n_items, and the cuts rise with w, so every item runs exactly once.
+        if (item_step == 1) {
+            long long total = 0;
+            for (int g = 0; g < sg.count; ++g) total += (long long)(sg.end[g] - (g ? sg.end[g - 1] : 0)) * sg.cost[g];
+            auto cut = [&](unsigned w) {
+                if (w >= gridDim.x) return n_items;
+                const long long t = total * w / gridDim.x;
+                long long cum = 0;
+                for (int g = 0; g < sg.count; ++g) {
+                    const int i0 = g ? sg.end[g - 1] : 0;
+                    const long long c = (long long)(sg.end[g] - i0) * sg.cost[g];
+                    if (t < cum + c) return i0 + (int)((t - cum + sg.cost[g] - 1) / sg.cost[g]);
+                    cum += c;
+                }
+                return n_items;
+            };
+            item_first = __builtin_amdgcn_readfirstlane(cut(blockIdx.x));
+            item_end = __builtin_amdgcn_readfirstlane(cut(blockIdx.x + 1));
+        }
+    }
     for (int item = item_first; item < item_end; item += item_step) {
     VRD_STAMP(0);
-    const int h = item % n_head_, b = item / n_head_;
+    int h = item % n_head_, b = item / n_head_;
+    if constexpr (SEGS) {
+        const int g = seg_of(sg, item);
+        const int l = item - (g ? sg.end[g - 1] : 0);
+        h = l % n_head_;
+        b = l / n_head_;
+        Tq = __builtin_amdgcn_readfirstlane(sg.Tq[g]);
+        Tk = __builtin_amdgcn_readfirstlane(sg.Tk[g]);
+        nkt = (Tk + 31) / 32;
+        nqg = (Tq + 31) / 32;
+        q_blocks = (Tq + 255) / 256;
+        q = q_all + sg.qrow[g] * ldq;
+        out = out_all + sg.qrow[g] * ldo;
+        k = k_all + sg.krow[g] * ldkv;
+        v = v_all + sg.krow[g] * ldkv;
+        kv_mask = kvm_all ? kvm_all + sg.krow[g] : nullptr;
+        q_mask = qm_all ? qm_all + sg.qrow[g] : nullptr;
+    }
     if (prefetch && item == item_first) dma_masks(item);
     // The ring, the tables and the output slabs of the previous item are free; (prefetch) this item's mask bytes have landed:
     // they are older than the rows of Q every live block waits for, so only an item without one has to wait here.  The
@@ -1209,10 +1322,17 @@ __global__ __launch_bounds__(256, 1) void attn_flash_x3_w64_kernel(const float* 
 #undef VRD_MFMA
 }
 
-template <int HD, bool F16, int NPROD = 3>
+template <bool SEGS>
+SegArg<SEGS> seg_arg(const AttnSegs* sg) {
+    if constexpr (SEGS) return *sg;
+    else return {};
+}
+
+// (SEGS: Tq and Tk are the largest of the launch's groups -- they size the LDS request and decide `prefetch` -- and B is unused)
+template <int HD, bool F16, int NPROD = 3, bool SEGS = false>
 int launch_w64(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kv_mask, const uint8_t* q_mask, int B,
-               int Tq, int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s) {
-    auto kern = attn_flash_x3_w64_kernel<HD, F16, NPROD>;
+               int Tq, int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s, const AttnSegs* sg = nullptr) {
+    auto kern = attn_flash_x3_w64_kernel<HD, F16, NPROD, SEGS>;
     // behind the ring: key bias + tile flags for Tk <= 4096, a flag per 32 queries (Tq <= 65536: the dispatch keeps longer ones
     // away), and -- if it fits in what is left of the 160 KiB -- the staging area of the next item's mask bytes, a dword each
     constexpr size_t lds_all = 160 * 1024;
@@ -1238,7 +1358,7 @@ int launch_w64(const float* q, int64_t ldq, const float* k, const float* v, int6
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         return n > 0 ? n : 256;
     }();
-    const int n_items = n_head * B;
+    const int n_items = SEGS ? sg->end[sg->count - 1] : n_head * B;
     // VRD_FLASH_GRID caps the number of workgroups (read per call: the tests walk several items per workgroup on small inputs)
     const char* const grid_e = getenv("VRD_FLASH_GRID");
     const int grid_cap = grid_e && atoi(grid_e) > 0 ? atoi(grid_e) : n_cu;
@@ -1246,16 +1366,21 @@ int launch_w64(const float* q, int64_t ldq, const float* k, const float* v, int6
     // a workgroup walks a contiguous run of items (the heads of a sequence, then the next sequence: measured 2 % faster than
     // items blockIdx.x, + grid, ... -- 37 MB apart in each tensor at the benchmark shape); VRD_FLASH_WALK=0: the strided walk
     const char* const walk_e = getenv("VRD_FLASH_WALK");
-    const int item_step = walk_e && atoi(walk_e) == 0 ? grid : 1;
+    // (SEGS: the strided walk unless VRD_FLASH_WALK=1 -- over the groups sorted by cost it starts the longest sequences first and
+    // deals every workgroup the same mix; measured 0.72 ms against 0.88 for contiguous runs cut by cost on the ragged benchmark's
+    // table, profiles/attn_segs_bench.json)
+    const int item_step = SEGS ? (walk_e && atoi(walk_e) != 0 ? 1 : grid) : (walk_e && atoi(walk_e) == 0 ? grid : 1);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_launch, s, q, ldq, k, v, ldkv, kv_mask, q_mask,
-                       Tq, Tk, n_head * HD, scale * 1.44269504088896340736f, out, ldo, pair_out, q_blocks, n_head, B, prefetch, item_step);      // (scale: see vrd_attention_pair)
+                       Tq, Tk, n_head * HD, scale * 1.44269504088896340736f, out, ldo, pair_out, q_blocks, n_head, B, prefetch, item_step,
+                       seg_arg<SEGS>(sg));      // (scale: see vrd_attention_pair)
     return 0;
 }
 
-template <int HD, int NW, bool F16, int NPROD = 3>
+// (SEGS: Tk is the largest of the launch's groups -- it sizes the LDS request -- and the grid is 8 XCDs x the table's slots per XCD)
+template <int HD, int NW, bool F16, int NPROD = 3, bool SEGS = false>
 int launch(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq,
-           int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s) {
-    auto kern = attn_flash_x3_kernel<HD, NW, F16, NPROD>;
+           int Tk, int n_head, float scale, float* out, int64_t ldo, int pair_out, hipStream_t s, const AttnSegs* sg = nullptr) {
+    auto kern = attn_flash_x3_kernel<HD, NW, F16, NPROD, SEGS>;
     constexpr size_t lds_max = 2 * AG<HD>::STAGE + (4096 + 128) * sizeof(float);       // key bias + tile flags for Tk <= 4096
     const size_t lds = 2 * AG<HD>::STAGE + (size_t)((Tk + 31) / 32) * 33 * sizeof(float);
     if (lds > lds_max) {
@@ -1265,8 +1390,9 @@ int launch(const float* q, int64_t ldq, const float* k, const float* v, int64_t 
     if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(kern), lds_max, "vrd_attention_pair")) return rc;
     const int tiles = (Tq + 31) / 32;
     const int q_blocks = (tiles + NW - 1) / NW;
-    hipLaunchKernelGGL(kern, dim3((unsigned)q_blocks * n_head * B), dim3(NW * 64), lds, s, q, ldq, k, v, ldkv, kv_mask, q_mask, Tq, Tk,
-                       n_head * HD, scale, out, ldo, pair_out, q_blocks, n_head);
+    const unsigned grid = SEGS ? 8u * (unsigned)sg->end[sg->count - 1] : (unsigned)q_blocks * n_head * B;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, q, ldq, k, v, ldkv, kv_mask, q_mask, Tq, Tk,
+                       n_head * HD, scale, out, ldo, pair_out, q_blocks, n_head, seg_arg<SEGS>(sg));
     return 0;
 }
 
@@ -1284,6 +1410,63 @@ extern "C" int vrd_lab_attn_stamps(unsigned long long* dst65, int reset) {
     return 0;
 }
 #endif
+
+namespace {
+
+// Which kernel a (Tq, Tk) problem runs on: vrd_attention_pair for its call, vrd_attention_pair_segs for every group.
+struct FlashChoice {
+    bool w64;                 // attn_flash_x3_w64_kernel (else attn_flash_x3_kernel with nw waves)
+    int nw;
+};
+FlashChoice choose_flash(int head_dim, int Tq, int Tk, int64_t ldq, int64_t ldkv) {
+    // waves (32-query tiles) per workgroup: every workgroup streams the whole K / V row of its (b, h), and the kernel is
+    // bound by that stream (LDS-DMA issue), so fewer, fuller workgroups win even when the last one is mostly empty:
+    // 288 queries = 9 tiles run as 4 + 4 + 1 (the lone tile is the padded tail at the benchmark shape and exits at
+    // once) 17 % faster than as 3 + 3 + 3.  Two workgroups of 4 waves fill a CU's registers (247 VGPRs per wave); ONE
+    // workgroup of 8 waves (a single stream per (b, h)) was measured 70 % slower: nothing runs while it waits at its
+    // barrier for a tile.
+    // (VRD_FLASH_NW and VRD_FLASH_W64 are ignored at head_dim 32: one instantiation there, 4 waves of 32 queries)
+    static const int nw_env = [] { const char* e = getenv("VRD_FLASH_NW"); return e ? atoi(e) : 0; }();
+    const int nw = nw_env == 3 || nw_env == 4 ? nw_env : 4;
+    // 64 queries per wave, one wave per SIMD (attn_flash_x3_w64_kernel): head_dim 128 from 160 query rows.  Measured per launch
+    // (scripts/flash_bench.py --pair, MI355X, round 6: its item loop rebuilt), 4 heads x 128, 2048 sequences of T rows, this kernel
+    // against the two-waves-per-SIMD one: T = 96: 0.51 / 0.36 ms, 128: 0.60 / 0.48, 160: 0.68 / 0.78, 192: 0.78 / 0.91, 224: 0.95 / 1.08,
+    // 288 (256 valid): 1.07 / 1.25-1.33.  At head_dim 64 it has half the MFMAs per softmax instruction and no more than ties (8 heads x
+    // 64, 1024 sequences: T = 128: 0.37 / 0.25, 256: 0.63 / 0.63, 288: 1.13 / 0.88 -- a second block of 32 rows --, 512: 2.00 / 2.01).
+    // VRD_FLASH_W64=0 / 1 forces the choice (read per call: tests compare the two kernels in one process).
+    const char* const w64_e = getenv("VRD_FLASH_W64");
+    const int w64_env = w64_e ? atoi(w64_e) : -1;
+    // (its LDS-DMA offsets are 32-bit: a batch element's Q and K / V slabs have to stay below 2 GiB)
+    const bool w64 = head_dim != 32 && (w64_env >= 0 ? w64_env != 0 : (head_dim == 128 && Tq >= 160)) && (int64_t)Tk * ldkv * 4 < (int64_t(1) << 31) &&
+                     (int64_t)Tq * ldq * 4 < (int64_t(1) << 31) && Tq <= 65536;
+    return {w64, nw};
+}
+
+// one launch of the chosen instantiation; SEGS: over the row groups of *sg (B is unused; Tq, Tk: the largest group's)
+template <bool SEGS>
+int launch_flash(FlashChoice c, int head_dim, bool f16, int products, const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
+                 const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, float scale, float* out, int64_t ldo,
+                 int out_pair, hipStream_t s, const AttnSegs* sg) {
+    const bool w64 = c.w64;
+    const int nw = c.nw;
+    int rc;
+#define VRD_ATTN_ARGS q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s, sg
+    if (head_dim == 32) rc = f16 ? launch<32, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<32, 4, false, 3, SEGS>(VRD_ATTN_ARGS);
+    else if (products == 1) {
+        if (w64) rc = head_dim == 128 ? launch_w64<128, true, 1, SEGS>(VRD_ATTN_ARGS) : launch_w64<64, true, 1, SEGS>(VRD_ATTN_ARGS);
+        else if (head_dim == 128) rc = nw == 3 ? launch<128, 3, true, 1, SEGS>(VRD_ATTN_ARGS) : launch<128, 4, true, 1, SEGS>(VRD_ATTN_ARGS);
+        else rc = nw == 3 ? launch<64, 3, true, 1, SEGS>(VRD_ATTN_ARGS) : launch<64, 4, true, 1, SEGS>(VRD_ATTN_ARGS);
+    } else if (w64) rc = head_dim == 128 ? (f16 ? launch_w64<128, true, 3, SEGS>(VRD_ATTN_ARGS) : launch_w64<128, false, 3, SEGS>(VRD_ATTN_ARGS))
+                                  : (f16 ? launch_w64<64, true, 3, SEGS>(VRD_ATTN_ARGS) : launch_w64<64, false, 3, SEGS>(VRD_ATTN_ARGS));
+    else if (head_dim == 128) rc = nw == 3 ? (f16 ? launch<128, 3, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<128, 3, false, 3, SEGS>(VRD_ATTN_ARGS))
+                                           : (f16 ? launch<128, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<128, 4, false, 3, SEGS>(VRD_ATTN_ARGS));
+    else rc = nw == 3 ? (f16 ? launch<64, 3, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<64, 3, false, 3, SEGS>(VRD_ATTN_ARGS))
+                      : (f16 ? launch<64, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<64, 4, false, 3, SEGS>(VRD_ATTN_ARGS));
+#undef VRD_ATTN_ARGS
+    return rc;
+}
+
+}  // namespace
 
 extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                                   const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, int head_dim,
@@ -1306,41 +1489,93 @@ extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, c
     const float scale = (f16 ? vrd::F16_ACT_INV * vrd::F16_ACT_INV : 1.0f) / sqrtf((float)head_dim);
     vrd::ProfScope prof(VRD_K_ATTN_FLASH, s, 4.0 * B * (double)n_head * Tq * Tk * head_dim,
                         4.0 * B * (double)width * (2.0 * Tq + 2.0 * Tk));
-    // waves (32-query tiles) per workgroup: every workgroup streams the whole K / V row of its (b, h), and the kernel is
-    // bound by that stream (LDS-DMA issue), so fewer, fuller workgroups win even when the last one is mostly empty:
-    // 288 queries = 9 tiles run as 4 + 4 + 1 (the lone tile is the padded tail at the benchmark shape and exits at
-    // once) 17 % faster than as 3 + 3 + 3.  Two workgroups of 4 waves fill a CU's registers (247 VGPRs per wave); ONE
-    // workgroup of 8 waves (a single stream per (b, h)) was measured 70 % slower: nothing runs while it waits at its
-    // barrier for a tile.
-    // (VRD_FLASH_NW and VRD_FLASH_W64 are ignored at head_dim 32: one instantiation there, 4 waves of 32 queries)
-    static const int nw_env = [] { const char* e = getenv("VRD_FLASH_NW"); return e ? atoi(e) : 0; }();
-    const int nw = nw_env == 3 || nw_env == 4 ? nw_env : 4;
-    // 64 queries per wave, one wave per SIMD (attn_flash_x3_w64_kernel): head_dim 128 from 160 query rows.  Measured per launch
-    // (scripts/flash_bench.py --pair, MI355X, round 6: its item loop rebuilt), 4 heads x 128, 2048 sequences of T rows, this kernel
-    // against the two-waves-per-SIMD one: T = 96: 0.51 / 0.36 ms, 128: 0.60 / 0.48, 160: 0.68 / 0.78, 192: 0.78 / 0.91, 224: 0.95 / 1.08,
-    // 288 (256 valid): 1.07 / 1.25-1.33.  At head_dim 64 it has half the MFMAs per softmax instruction and no more than ties (8 heads x
-    // 64, 1024 sequences: T = 128: 0.37 / 0.25, 256: 0.63 / 0.63, 288: 1.13 / 0.88 -- a second block of 32 rows --, 512: 2.00 / 2.01).
-    // VRD_FLASH_W64=0 / 1 forces the choice (read per call: tests compare the two kernels in one process).
-    const char* const w64_e = getenv("VRD_FLASH_W64");
-    const int w64_env = w64_e ? atoi(w64_e) : -1;
-    // (its LDS-DMA offsets are 32-bit: a batch element's Q and K / V slabs have to stay below 2 GiB)
-    const bool w64 = head_dim != 32 && (w64_env >= 0 ? w64_env != 0 : (head_dim == 128 && Tq >= 160)) && (int64_t)Tk * ldkv * 4 < (int64_t(1) << 31) &&
-                     (int64_t)Tq * ldq * 4 < (int64_t(1) << 31) && Tq <= 65536;
-    int rc;
-#define VRD_ATTN_ARGS q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s
-    if (head_dim == 32) rc = f16 ? launch<32, 4, true>(VRD_ATTN_ARGS) : launch<32, 4, false>(VRD_ATTN_ARGS);
-    else if (products == 1) {
-        if (w64) rc = head_dim == 128 ? launch_w64<128, true, 1>(VRD_ATTN_ARGS) : launch_w64<64, true, 1>(VRD_ATTN_ARGS);
-        else if (head_dim == 128) rc = nw == 3 ? launch<128, 3, true, 1>(VRD_ATTN_ARGS) : launch<128, 4, true, 1>(VRD_ATTN_ARGS);
-        else rc = nw == 3 ? launch<64, 3, true, 1>(VRD_ATTN_ARGS) : launch<64, 4, true, 1>(VRD_ATTN_ARGS);
-    } else if (w64) rc = head_dim == 128 ? (f16 ? launch_w64<128, true>(VRD_ATTN_ARGS) : launch_w64<128, false>(VRD_ATTN_ARGS))
-                                  : (f16 ? launch_w64<64, true>(VRD_ATTN_ARGS) : launch_w64<64, false>(VRD_ATTN_ARGS));
-    else if (head_dim == 128) rc = nw == 3 ? (f16 ? launch<128, 3, true>(VRD_ATTN_ARGS) : launch<128, 3, false>(VRD_ATTN_ARGS))
-                                           : (f16 ? launch<128, 4, true>(VRD_ATTN_ARGS) : launch<128, 4, false>(VRD_ATTN_ARGS));
-    else rc = nw == 3 ? (f16 ? launch<64, 3, true>(VRD_ATTN_ARGS) : launch<64, 3, false>(VRD_ATTN_ARGS))
-                      : (f16 ? launch<64, 4, true>(VRD_ATTN_ARGS) : launch<64, 4, false>(VRD_ATTN_ARGS));
-#undef VRD_ATTN_ARGS
-    if (rc) return rc;
+    const FlashChoice c = choose_flash(head_dim, Tq, Tk, ldq, ldkv);
+    if (int rc = launch_flash<false>(c, head_dim, f16, products, q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s,
+                                     nullptr))
+        return rc;
     VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same over the row groups of a ragged row space: every group runs the instantiation its own vrd_attention_pair call would
+// run (choose_flash per group), so a call is at most two launches -- the groups of the one-wave-per-SIMD kernel and those of the
+// other -- each with its sub-table in the kernel arguments.  Items are independent: the result is that of the per-group calls
+// bit for bit, whatever the order.
+extern "C" int vrd_attention_pair_segs(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
+                                       const uint8_t* kv_mask, const uint8_t* q_mask, const vrd_row_segs* qsegs,
+                                       const vrd_row_segs* ksegs, int n_head, int head_dim, float* out, int64_t ldo, int out_pair,
+                                       int pair_fmt, void* stream, int products) {
+    VRD_CHECK_ARG(q && k && v && out && qsegs && ksegs, "vrd_attention_pair_segs: null pointer");
+    VRD_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128, "vrd_attention_pair_segs: head_dim must be 32, 64 or 128 (got %d)", head_dim);
+    VRD_CHECK_ARG(n_head > 0 && n_head <= 65535, "vrd_attention_pair_segs: bad sizes");
+    VRD_CHECK_ARG(qsegs->count >= 1 && qsegs->count <= VRD_MAX_SEGS, "vrd_attention_pair_segs: bad row groups (%d groups, 1..%d)", qsegs->count,
+                  VRD_MAX_SEGS);
+    VRD_CHECK_ARG(ksegs->count == qsegs->count, "vrd_attention_pair_segs: the query and key tables disagree (%d and %d groups)", qsegs->count,
+                  ksegs->count);
+    const int width = n_head * head_dim;
+    VRD_CHECK_ARG(ldq >= width && ldkv >= width && ldo >= width && ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 &&
+                      aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out),
+                  "vrd_attention_pair_segs: rows must be 16-byte aligned pair rows of width n_head*head_dim");
+    VRD_CHECK_ARG(pair_fmt == VRD_PAIR_BF16 || pair_fmt == VRD_PAIR_F16, "vrd_attention_pair_segs: pair_fmt must be VRD_PAIR_BF16 or VRD_PAIR_F16");
+    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == pair_fmt, "vrd_attention_pair_segs: pair output comes in the operands' format");
+    VRD_CHECK_ARG(products == 0 || products == 3 || (products == 1 && pair_fmt == VRD_PAIR_F16),
+                  "vrd_attention_pair_segs: products must be 0 or 3, or 1 with VRD_PAIR_F16 operands (got %d, pair_fmt %d)", products, pair_fmt);
+    VRD_CHECK_ARG(products != 1 || head_dim != 32,
+                  "vrd_attention_pair_segs: head_dim 32 has no one-product form (products = 1 needs head_dim 64 or 128)");
+    const int count = qsegs->count;
+    int64_t units_w64 = 0, units_x3 = 0;
+    FlashChoice choice[VRD_MAX_SEGS];
+    for (int g = 0; g < count; ++g) {
+        const int n = qsegs->n[g], Tq = qsegs->T[g], Tk = ksegs->T[g];
+        VRD_CHECK_ARG(ksegs->n[g] == n, "vrd_attention_pair_segs: the query and key tables disagree (group %d: %d and %d sequences)", g, n,
+                      ksegs->n[g]);
+        VRD_CHECK_ARG(n > 0 && n <= 65535 && Tq > 0 && Tk > 0 && qsegs->row[g] >= 0 && ksegs->row[g] >= 0,
+                      "vrd_attention_pair_segs: bad sizes (group %d: n = %d, Tq = %d, Tk = %d)", g, n, Tq, Tk);
+        VRD_CHECK_ARG(Tk <= 4096, "vrd_attention_pair_segs: Tk = %d (group %d) exceeds the 4096 keys the key-bias row is sized for", Tk, g);
+        choice[g] = choose_flash(head_dim, Tq, Tk, ldq, ldkv);
+        if (choice[g].w64) units_w64 += (int64_t)n * n_head;
+        else units_x3 += (int64_t)(((Tq + 31) / 32 + choice[g].nw - 1) / choice[g].nw) * n_head * n + 7;      // (+ 7: slots, rounded up per XCD)
+    }
+    VRD_CHECK_ARG(units_w64 < (int64_t(1) << 31) && units_x3 < (int64_t(1) << 31), "vrd_attention_pair_segs: bad sizes (too many workgroups)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool f16 = pair_fmt == VRD_PAIR_F16;
+    const float scale = (f16 ? vrd::F16_ACT_INV * vrd::F16_ACT_INV : 1.0f) / sqrtf((float)head_dim);      // (see vrd_attention_pair)
+    for (int pass = 0; pass < 2; ++pass) {
+        const bool w64 = pass == 0;
+        // the launch's groups by cost, dearest first: the longest sequences start first and the short ones fill the launch's tail
+        // (the item walks of the one-wave-per-SIMD kernel: see there; the other kernel's workgroups are dispatched in this order)
+        int order[VRD_MAX_SEGS], m = 0;
+        for (int g = 0; g < count; ++g)
+            if (choice[g].w64 == w64) order[m++] = g;
+        if (!m) continue;
+        auto cost = [&](int g) { return ((ksegs->T[g] + 31) / 32) * ((qsegs->T[g] + 31) / 32); };
+        std::stable_sort(order, order + m, [&](int a, int b) { return cost(a) > cost(b); });
+        AttnSegs sg = {};
+        sg.count = m;
+        int Tq_max = 0, Tk_max = 0, end = 0;
+        double flops = 0.0, bytes = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const int g = order[i], n = qsegs->n[g], Tq = qsegs->T[g], Tk = ksegs->T[g];
+            sg.units[i] = w64 ? n * n_head : (((Tq + 31) / 32 + choice[g].nw - 1) / choice[g].nw) * n_head * n;
+            end += w64 ? sg.units[i] : (sg.units[i] + 7) / 8;          // (first kernel: slots per XCD, see there)
+            sg.end[i] = end;
+            sg.cost[i] = cost(g);
+            sg.Tq[i] = Tq;
+            sg.Tk[i] = Tk;
+            sg.qrow[i] = qsegs->row[g];
+            sg.krow[i] = ksegs->row[g];
+            Tq_max = Tq > Tq_max ? Tq : Tq_max;
+            Tk_max = Tk > Tk_max ? Tk : Tk_max;
+            flops += 4.0 * n * (double)n_head * Tq * Tk * head_dim;
+            bytes += 4.0 * n * (double)width * (2.0 * Tq + 2.0 * Tk);
+        }
+        sg.nkt_max = (Tk_max + 31) / 32;
+        sg.nqg_max = (Tq_max + 31) / 32;
+        vrd::ProfScope prof(VRD_K_ATTN_FLASH, s, flops, bytes);
+        if (int rc = launch_flash<true>(choice[order[0]], head_dim, f16, products, q, ldq, k, v, ldkv, kv_mask, q_mask, 0, Tq_max, Tk_max, n_head,
+                                        scale, out, ldo, out_pair, s, &sg))
+            return rc;
+        VRD_LAUNCH_CHECK();
+    }
     return 0;
 }

@@ -203,7 +203,8 @@ def dwconv_ln(lay, x, sets, mask_out, *, stride=1, x_up=None, pre_ln=None):
 
 
 def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False):
-    """Global (half_win None) or banded attention of the queries in `qlay` over the keys in `klay`, bucket by bucket.
+    """Global (half_win None) or banded attention of the queries in `qlay` over the keys in `klay`: bucket by bucket, or the
+    buckets as the row groups of one kernel call (banded attention; global attention on pair rows with ATTN_SEGS).
     q_mask: rows the caller masks afterwards (global attention only)."""
     ops = _ops()
     qsegs, ksegs = qlay.segs, klay.segs
@@ -228,6 +229,13 @@ def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, re
         assert list(qsegs) == list(ksegs)
         r = ops.local_attention(q, k, v, kv_mask, n_head, half_win, pair=pair, rel_pe=rel_pe, out=out, segs=list(qsegs))
         return ops.Pair(out, Cc, r.fmt) if isinstance(r, ops.Pair) else out
+    if half_win is None and ATTN_SEGS and all(isinstance(x, ops.Pair) for x in (q, k, v)):
+        # global attention on pair rows, opted in: the buckets as the row groups of one call (two launches at the most), in
+        # runs of _MAX_SEGS buckets; f32 rows (the exact mode, the generic kernel, training) keep the bucket walk below
+        for g0 in range(0, len(qsegs), _MAX_SEGS):
+            r = ops.attention(q, k, v, kv_mask, n_head, pair=pair, q_mask=q_mask, out=out,
+                              segs=(list(qsegs[g0:g0 + _MAX_SEGS]), list(ksegs[g0:g0 + _MAX_SEGS])))
+        return ops.Pair(out, Cc, r.fmt) if isinstance(r, ops.Pair) else out
     # global attention walks the buckets; a bucket's launch is n x heads x query blocks workgroups of one per CU -- 4.02 rounds
     # of the chip for 257 pairs x 4 heads take five --, so the buckets' launches alternate between ATTN_LANES streams and fill
     # each other's last rounds
@@ -249,6 +257,9 @@ def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, re
 
 
 ATTN_LANES = int(__import__("os").environ.get("VRDONE_ROWS_ATTN_STREAMS", "2"))      # streams the buckets' global attention alternates between
+# opt-in (VRDONE_ROWS_ATTN_SEGS=1): global attention on pair rows takes the buckets as the row groups of one call instead of
+# walking them over the side streams (a module value, like ATTN_LANES: tests and A/B runs flip it in one process)
+ATTN_SEGS = __import__("os").environ.get("VRDONE_ROWS_ATTN_SEGS", "0") == "1"
 _side_streams = {}
 
 

@@ -1061,12 +1061,17 @@ def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, ou
     return Pair(out, Cc) if _fmt(pair) else out
 
 
-def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=None):
+def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=None, segs=None):
     """Global masked attention; q: (B, Tq, C), k/v: (B, Tk, C); kv_mask (B, Tk) or None.
     out: (B, Tq, C) contiguous rows to write instead of a fresh tensor (inference path).
     pair: pair-row output when the flash kernel runs (otherwise a plain tensor is returned).
     q_mask (B, Tq): rows the caller masks afterwards; the split-precision kernel leaves out query tiles without a valid
-    row (they read 0)."""
+    row (they read 0).
+    segs (inference path, pair-row operands only): (qsegs, ksegs) -- q / q_mask / out are a ragged row space (1, Rq, ...) of the
+    groups qsegs = [(first row, sequences, frames)], k / v / kv_mask one of ksegs (vrd_row_segs; the same sequences per group on
+    both sides): every group's attention in one call (vrd_attention_pair_segs), bit for bit the group-by-group calls."""
+    if segs is not None:
+        return _attention_segs(q, k, v, kv_mask, n_head, pair, q_mask, out, *segs)
     if not isinstance(q, Pair) and recording(q, k, v):
         from . import autograd
         return autograd.Attention.apply(q, k, v, kv_mask, n_head)
@@ -1104,6 +1109,34 @@ def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=Non
     _hip.check(lib.vrd_attention(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), B, Tq, Tk, n_head, hd,
                                  out.data_ptr(), Cc, algo, _fmt(pair), _stream()), "vrd_attention")
     return Pair(out, Cc) if pair else out
+
+
+def _attention_segs(q, k, v, kv_mask, n_head, pair, q_mask, out, qsegs, ksegs):
+    if not (isinstance(q, Pair) and isinstance(k, Pair) and isinstance(v, Pair)):
+        raise TypeError("attention(segs=...): the row groups of one call exist for pair-row operands only (the split-precision "
+                        "flash kernel); f32 rows go group by group")
+    assert q.width == k.width == v.width == q.shape[-1] and q.fmt == k.fmt == v.fmt
+    fmt = q.fmt
+    q, k, v = q.t, k.t, v.t
+    qsegs, ksegs = list(qsegs), list(ksegs)
+    assert len(qsegs) == len(ksegs) >= 1 and all(a[1] == b[1] for a, b in zip(qsegs, ksegs))
+    (B, Rq, Cc), Rk = q.shape, k.shape[1]
+    assert B == 1 and k.shape[0] == 1 and v.shape == k.shape
+    assert all(0 <= off and off + n * T <= Rq for off, n, T in qsegs) and all(0 <= off and off + n * T <= Rk for off, n, T in ksegs)
+    pq, _, _, ldq = _rows(q)
+    pk, rows_k, _, ldk = _rows(k)
+    pv, _, _, ldv = _rows(v)
+    assert ldk == ldv
+    if out is None:
+        out = torch.empty(1, Rq, Cc, device=q.device, dtype=torch.float32)
+    assert out.shape == (1, Rq, Cc) and out.is_contiguous()
+    for g0 in range(0, len(qsegs), _hip.MAX_SEGS):              # a call takes MAX_SEGS groups: consecutive runs of them
+        tq, tk = _hip.RowSegs.of(qsegs[g0:g0 + _hip.MAX_SEGS]), _hip.RowSegs.of(ksegs[g0:g0 + _hip.MAX_SEGS])
+        _hip.check(lib.vrd_attention_pair_segs(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), _mask_ptr(q_mask, Rq), C.byref(tq),
+                                               C.byref(tk), n_head, Cc // n_head, out.data_ptr(), Cc, fmt if pair else 0, fmt,
+                                               _stream(), products() if fmt == _hip.PAIR_F16 else 0),
+                   "vrd_attention_pair_segs")
+    return Pair(out, Cc, fmt) if pair else out
 
 
 def maxpool_mask(x, mask_in, out=None):
