@@ -472,6 +472,9 @@ int vrd_mask_head(const float* emb, int64_t ld_emb, const float* feat, int64_t l
  * frame with sigmoid(mask) > 0.5 inside the valid length.  Outputs, per (p, q):
  *   top_score[p,q,k], top_cat[p,q,k] (class id, already +1), seg_first[p,q], seg_last[p,q]
  *   (-1 when the query's mask is empty).
+ * top_cat[p,q,:] are topk distinct classes in 1 .. K1-1, scores in descending order, equal probabilities to the lower class.
+ * A row of logits that has no softmax (a NaN or +inf entry, or every entry -inf) keeps that: its scores are NaN, its classes
+ * the finite candidates in order and then the lowest classes not yet returned; its segment and all other rows are unaffected.
  * logits: (P, Q, K1); masks: (P, Q, T); valid_len: (P) int32. */
 int vrd_postprocess(const float* logits, const float* masks, const int32_t* valid_len,
                     int P, int Q, int K1, int T, int topk,

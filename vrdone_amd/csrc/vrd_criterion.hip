@@ -9,7 +9,7 @@
 //                           (relation, query, layer).  Entry [g, q] is entry [b*Q + q, g] of the reference's matrices.
 //   (vrd_assign, vrd_train_tail.hip, turns the costs into query_of[l][g].)
 //   vrd_criterion_losses    per layer: class-weighted cross-entropy over all (pair, query) rows, masked focal loss and dice
-//                           loss of the matched rows; one workgroup per layer, sums in a fixed order (no atomics).
+//                           loss of the matched rows; one workgroup per layer, compensated sums in a fixed order (no atomics).
 //   vrd_criterion_backward  d(sum_l sum_i gout[l][i] * loss[l][i]) / d logits_l, d masks_l: one wave per (pair, query, layer) row.
 //
 // All arithmetic is f32 like the reference's; softplus follows torch's (linear above 20).  gamma = 2 is evaluated as a square.
@@ -47,8 +47,13 @@ __device__ __forceinline__ float target_at(const vrd_criterion_args& a, int g, i
     return (ramp ? w : 0.0f) + (core ? hard : 0.0f);
 }
 
-// log-sum-exp of a row of K values, by one wave
-__device__ __forceinline__ float wave_lse(const float* __restrict__ row, int K, int lane) {
+// log-sum-exp of a row of K values, by one wave, as its two parts: lse = mx + ls.  They stay apart because -log softmax(x)[k] =
+// ls - (x[k] - mx) keeps the precision of x[k] - mx, where (mx + ls) - x[k] rounds at the size of the logits (1.5e-5 at 150).
+struct Lse {
+    float mx, ls;
+    __device__ __forceinline__ float nll(float x) const { return ls - (x - mx); }       // -log softmax at a logit x of the row
+};
+__device__ __forceinline__ Lse wave_lse(const float* __restrict__ row, int K, int lane) {
     float mx = -INFINITY;
     for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[k]);
 #pragma unroll
@@ -56,7 +61,7 @@ __device__ __forceinline__ float wave_lse(const float* __restrict__ row, int K, 
     float s = 0.f;
     for (int k = lane; k < K; k += 64) s += expf(row[k] - mx);
     s = vrd::wave_sum(s);
-    return mx + logf(s);
+    return {mx, logf(s)};
 }
 
 __global__ void criterion_costs_kernel(vrd_criterion_args a, float* __restrict__ cost) {
@@ -86,10 +91,10 @@ __global__ void criterion_costs_kernel(vrd_criterion_args a, float* __restrict__
     s_t = vrd::wave_sum(s_t);
     n_valid = vrd::wave_sum(n_valid);
     const float* lr = a.logits[l] + ((int64_t)b * a.Q + q) * a.K1;
-    const float lse = wave_lse(lr, a.K1, lane);
+    const Lse lse = wave_lse(lr, a.K1, lane);
     if (lane == 0) {
         // a class id outside [0, K1) (F.cross_entropy raises on one): NaN cost -> the pair comes back unassigned -> poisoned losses
-        const float c_class = class_ok(a, g) ? lse - lr[a.tgt_ids[g]] : __builtin_nanf("");
+        const float c_class = class_ok(a, g) ? lse.nll(lr[a.tgt_ids[g]]) : __builtin_nanf("");
         const float c_mask = (s_pos + s_neg) / n_valid;
         const float c_dice = 1.0f - (2.0f * s_st + 1.0f) / (s_sig + s_t + 1.0f);
         cost[((int64_t)l * a.G + g) * a.Q + q] = a.w_class * c_class + a.w_mask * c_mask + a.w_dice * c_dice;
@@ -111,6 +116,17 @@ __device__ __forceinline__ FocalAt focal_at(const vrd_criterion_args& a, int g, 
     return f;
 }
 
+// Compensated (Kahan) running sum.  A wave of the loss kernel adds up to B * Q / 16 terms one after another: at the 12,000 rows
+// the kernel's table admits, a plain f32 sum is 5e-6 off the class loss, twenty times the tensor form's error.
+struct KahanSum {
+    float s = 0.f, c = 0.f;
+    __device__ __forceinline__ void add(float v) {
+        const float y = v - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
 constexpr int LOSS_WAVES = 16;
 __global__ __launch_bounds__(LOSS_WAVES * 64) void criterion_losses_kernel(vrd_criterion_args a, const int32_t* __restrict__ query_of,
                                                                          const float* __restrict__ class_weight, float num_masks,
@@ -129,17 +145,17 @@ __global__ __launch_bounds__(LOSS_WAVES * 64) void criterion_losses_kernel(vrd_c
     }
     __syncthreads();
     // ---- class term: sum_r w[t_r] * (lse_r - x_r[t_r]) / sum_r w[t_r]
-    float num = 0.f, den = 0.f;
+    KahanSum num, den;
     for (int r = wave; r < rows; r += LOSS_WAVES) {
         const float* lr = a.logits[l] + (int64_t)r * a.K1;
-        const float lse = wave_lse(lr, a.K1, lane);
+        const Lse lse = wave_lse(lr, a.K1, lane);
         const int t = tgt_cls[r];
         const float w = class_weight[t];
-        num += w * (lse - lr[t]);
-        den += w;
+        num.add(w * lse.nll(lr[t]));
+        den.add(w);
     }
     // ---- matched rows: focal (mean over ALL T frames of the masked term) and dice
-    float focal = 0.f, dice = 0.f;
+    KahanSum focal, dice;
     for (int g = wave; g < a.G; g += LOSS_WAVES) {
         const int b = a.owner[g], q = qo[g] < 0 ? 0 : qo[g];
         const float* x = a.masks[l] + ((int64_t)b * a.Q + q) * a.T;
@@ -157,14 +173,14 @@ __global__ __launch_bounds__(LOSS_WAVES * 64) void criterion_losses_kernel(vrd_c
         s_pt = vrd::wave_sum(s_pt);
         s_p = vrd::wave_sum(s_p);
         s_t = vrd::wave_sum(s_t);
-        focal += s_f / (float)a.T;
-        dice += 1.0f - (2.0f * s_pt + 1.0f) / (s_p + s_t + 1.0f);
+        focal.add(s_f / (float)a.T);
+        dice.add(1.0f - (2.0f * s_pt + 1.0f) / (s_p + s_t + 1.0f));
     }
     if (lane == 0) {
-        part[wave * 4 + 0] = num;
-        part[wave * 4 + 1] = den;
-        part[wave * 4 + 2] = focal;
-        part[wave * 4 + 3] = dice;
+        part[wave * 4 + 0] = num.s;
+        part[wave * 4 + 1] = den.s;
+        part[wave * 4 + 2] = focal.s;
+        part[wave * 4 + 3] = dice.s;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -199,9 +215,9 @@ __global__ __launch_bounds__(64) void criterion_backward_kernel(vrd_criterion_ar
         const float* lr = a.logits[l] + (int64_t)r * a.K1;
         float* go = gr.logits[l] + (int64_t)r * a.K1;
         const int t = (g_match >= 0 && class_ok(a, g_match)) ? (int)a.tgt_ids[g_match] : 0;
-        const float lse = wave_lse(lr, a.K1, lane);
+        const Lse lse = wave_lse(lr, a.K1, lane);
         const float coef = g_class * class_weight[t] / fwd_out[l * 4 + 3];
-        for (int k = lane; k < a.K1; k += 64) go[k] = coef * (expf(lr[k] - lse) - (k == t ? 1.0f : 0.0f));
+        for (int k = lane; k < a.K1; k += 64) go[k] = coef * (expf(-lse.nll(lr[k])) - (k == t ? 1.0f : 0.0f));
     }
     // ---- mask terms: only matched rows carry a gradient
     float* gm = gr.masks[l] + (int64_t)r * a.T;

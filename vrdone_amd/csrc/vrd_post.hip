@@ -1,8 +1,9 @@
 // Eval post-processing on the device: what MaskVRD.forward_test does per candidate in a
 // Python loop with one device sync each (reference models/maskvrd.py:247-309), done here
 // once per (pair, query) by one wavefront:
-//   softmax over the K1 class logits, top-k over classes 1..K1-1 (class 0 = background),
-//   and the first / last frame whose sigmoid(mask logit) > 0.5 inside the valid length.
+//   softmax over the K1 class logits, top-k over classes 1..K1-1 (class 0 = background; equal probabilities go to the lower
+//   class; a row without a softmax -- a NaN or +inf logit, or only -inf -- returns topk distinct foreground classes with NaN
+//   scores), and the first / last frame whose sigmoid(mask logit) > 0.5 inside the valid length.
 // Every (query, class) candidate of a query shares that query's segment (maskvrd.py:252).
 #include "vrd_common.h"
 #include <cmath>
@@ -55,6 +56,16 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
             const float ob = __shfl_xor(best, off, 64);
             const int oi = __shfl_xor(bi, off, 64);
             if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        if (bi == 0x7fffffff) {
+            // Nothing compares above -1: the classes still to return all have a NaN probability (a NaN or +inf logit in the
+            // row, or only -inf ones; den is NaN then too).  The slot takes the lowest of them, with a NaN score.
+#pragma unroll
+            for (int i = PP_MAX_K1 / 64 - 1; i >= 0; --i)
+                if (val[i] != val[i]) bi = lane + 64 * i;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) bi = min(bi, __shfl_xor(bi, off, 64));
+            best = __builtin_nanf("");
         }
         if (lane == 0) {
             top_score[(int64_t)pq * topk + r] = best / den;
