@@ -583,7 +583,7 @@ def test_gemm_staged_rows_a_scale():
         dy = torch.zeros(M, Nw, device=DEV)
         dy[M - 1, Nw - 1] = value
         zero()
-        ops.conv_gemm(dy, w, None, _dgrad=True, _a_scale=scale, _bfmt=_hip.PAIR_F16)
+        ops.conv_dgrad(dy, w, a_scale=scale, fmt=_hip.PAIR_F16)
         assert bits() == want, (factor, value)
 
 

@@ -624,6 +624,15 @@ def _family_of(case):
     return getattr(_hip, case.body)
 
 
+def _gemm(family, *args, **kwargs):
+    """ops.conv_gemm(*args, **kwargs) on plain tensors; `family` receives the kernel family the library runs the call on"""
+    from vrdone_amd import ops
+    a, result = ops.gemm_args(*args, **kwargs)
+    family.append(ops.gemm_family(a))
+    ops.launch_gemm(a)
+    return result
+
+
 @pytest.mark.parametrize("case,m", cases_for(*[n for n in named("gemm_") if "mlp" not in n]))
 def test_gemm_far(case, m, arena):
     """512 -> 512, k = 1 / 3, mask * scale + two residuals; x, res, res2 and out each at their own pitch"""
@@ -650,8 +659,8 @@ def test_gemm_far(case, m, arena):
         out = arena.output("out", B * Ts, N, pitches["out"])
         xv = rows3(x, Ts)
         family = []
-        ops.conv_gemm(ops.Pair(xv, Cin, fmt) if pair_in else xv, w.to(DEV), bias.to(DEV), row_mask=tiled(m_p, B), scale=scale.to(DEV),
-                      res=rows3(res, Ts), res_masked=True, res2=rows3(res2, Ts), out=rows3(out, Ts), _family=family)
+        _gemm(family, ops.Pair(xv, Cin, fmt) if pair_in else xv, w.to(DEV), bias.to(DEV), row_mask=tiled(m_p, B), scale=scale.to(DEV),
+              res=rows3(res, Ts), res_masked=True, res2=rows3(res2, Ts), out=rows3(out, Ts))
         assert family[0] == _family_of(case), f"the call ran kernel family {family[0]}, the case is built for {case.body}"
         arena.check({"out": P})
         scale_tol = 5.0 if m == "bf16x3" else 1.0                              # tests/test_gpu_ops.py GEMM_TOL_SCALE
@@ -681,9 +690,9 @@ def test_gemm_mlp_far(case, m, arena):
         res = arena.input("res", res_p.to(DEV), B * T)
         md = tiled(m_p, B)
         xv, fam = rows3(x, T), []
-        h = ops.conv_gemm(ops.Pair(xv, Cw, fmt) if pair else xv, w1.to(DEV), b1.to(DEV), act=ops.ACT_GELU, out=rows3(hid, T), out_pair=pair,
-                          skip_rows=md, _family=fam)
-        ops.conv_gemm(h, w2.to(DEV), b2.to(DEV), row_mask=md, scale=scale.to(DEV), res=rows3(res, T), out=rows3(out, T), _family=fam)
+        h = _gemm(fam, ops.Pair(xv, Cw, fmt) if pair else xv, w1.to(DEV), b1.to(DEV), act=ops.ACT_GELU, out=rows3(hid, T), out_pair=pair,
+                  skip_rows=md)
+        _gemm(fam, h, w2.to(DEV), b2.to(DEV), row_mask=md, scale=scale.to(DEV), res=rows3(res, T), out=rows3(out, T))
         assert fam == [_family_of(case)] * 2, f"the calls ran kernel families {fam}, the case is built for {case.body}"
         arena.check({"hidden": P, "out": P})
         scale_tol = 5.0 if m == "bf16x3" else 1.0                              # tests/test_gpu_ops.py GEMM_TOL_SCALE

@@ -60,11 +60,12 @@ def _run_case(case, mode, group, ops, _hip):
     ops._skip_padding, ops.SKIP_MIN_ROWS = maps, 0 if maps else old_min
     try:
         def calls(m, pair):
-            fam, out = [], []
+            out = []
             with ops.use_precision(m):
                 for p in inp.problems:
                     a = (ops.Pair(p.hA.view, case.Cin, fmt), p.w.to(DEV), p.bias.to(DEV) if p.bias is not None else None)
-                    out.append((a, dict(kw, out=(p.hP if pair else p.hC).view, out_pair=pair, _family=fam)))
+                    out.append((a, dict(kw, out=(p.hP if pair else p.hC).view, out_pair=pair)))
+                fam = [ops.gemm_family(ops.gemm_args(*a, **k)[0]) for a, k in out]
                 if case.layout == "batch3":
                     ops.conv_gemm_batch(out)
                 else:

@@ -848,3 +848,65 @@ def test_few_channel_conv_layernorm_row_kernel(Cin, N, ln, pair, precision):
         h = ops.conv_gemm(xd, wd, bd, row_mask=md, out_pair=True)
     hf = (h.float() if isinstance(h, ops.Pair) else h).cpu().double()
     assert float((gotf - hf).abs().max()) <= tol * max(1.0, float(want.abs().max()))
+
+
+@pytest.mark.parametrize("precision", ["f16x3"], indirect=True)
+def test_derived_operand_cache_rule(precision):
+    """ops._derived at all its users -- the depthwise parameter image, the packed weight, both split operands, the padding map:
+    (a) eager, an operand is built once per version of what it was derived from; (b) a graph capture rebuilds every operand
+    inside the recording, so a replay computes with the weights as they are then; (c) and it stores nothing; (d) except what
+    presplit_weights published inside the same presplit_scope, which the captures of that scope (only) take from the cache.
+    Two sequences of 32 frames at 256 channels, the narrowest rows vrd_dwconv_ln takes; the dense conv is 256 -> 64, k = 3."""
+    from vrdone_amd import _hip, ops
+    gen = torch.Generator().manual_seed(9)
+    rn = lambda *s: torch.randn(*s, generator=gen).to(DEV)      # noqa: E731
+    x, mask = rn(2, 32, 256), (torch.arange(32)[None, :] < torch.tensor([32, 20])[:, None]).to(DEV)
+    dw, db, gamma, beta = rn(256, 1, 3), rn(256), rn(256), rn(256)
+    w, bias = rn(64, 256, 3) / 768 ** 0.5, rn(64)
+    fwd = "_vrd_split_f16"
+    bwd = "_vrd_split_t_f16" if ops.backward_fmt() == _hip.PAIR_F16 else "_vrd_split_t"
+    users = [lambda: ops._dwconv_block(dw, db, gamma, beta), lambda: ops.packed_conv_weight(w), lambda: ops.split_conv_weight(w),
+             lambda: ops.split_conv_weight_dgrad(w), lambda: ops.row_blocks(mask)]
+    slots = [(dw, "_vrd_dw_block"), (w, "_vrd_packed"), (w, fwd), (w, bwd), (mask, "_vrd_row_blocks")]
+
+    def run():
+        h = ops.dwconv_ln(x, [dict(weight=dw, bias=db, gamma=gamma, beta=beta)], mask_out=mask)[0]
+        return ops.conv_gemm(h, w, bias, row_mask=mask)
+
+    # (a)
+    first = [use() for use in users]
+    assert all(use() is val for use, val in zip(users, first))
+    assert all(getattr(owner, slot)[1] is val for (owner, slot), val in zip(slots, first))
+    dw.mul_(1.5), w.mul_(0.5), mask.logical_and_(mask)
+    assert all(use() is not val for use, val in zip(users, first))
+    run()
+    # (b)
+    before = [getattr(owner, slot) for owner, slot in slots]
+    mask2 = mask.clone()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        y = run()
+        assert ops.row_blocks(mask2) is not None
+    dw.mul_(1.5), w.mul_(0.5)
+    graph.replay()
+    # (c) (first: _capture_keep is emptied by the first cached op after the capture, the eager run below)
+    assert all(getattr(owner, slot) is entry for (owner, slot), entry in zip(slots, before))
+    assert not hasattr(mask2, "_vrd_row_blocks") and len(ops._capture_keep) > 0
+    assert torch.equal(y, run())
+    assert ops._capture_keep == []
+    # (d)
+    plans = {}
+    ops.presplit_weights([w], plans)          # (a plan's job table is built outside any capture)
+    (plan,) = plans.values()
+    bufs = {slot: out for _, slot, out in plan.outs}
+    assert set(bufs) == {fwd, bwd}
+    in_scope, out_of_scope = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with ops.presplit_scope() as scope:
+        with torch.cuda.graph(in_scope):
+            ops.presplit_weights([w], plans)
+            got = ops.split_conv_weight(w), ops.split_conv_weight_dgrad(w)
+    assert got[0] is bufs[fwd] and got[1] is bufs[bwd]
+    assert len(scope.plans) == 1 and scope.plans[0] is plan
+    with torch.cuda.graph(out_of_scope):
+        fresh = ops.split_conv_weight(w), ops.split_conv_weight_dgrad(w)
+    assert fresh[0] is not bufs[fwd] and fresh[1] is not bufs[bwd]

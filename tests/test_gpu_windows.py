@@ -432,8 +432,9 @@ def _gemm_case(B, T, Cin, N, k, pair_in, sample, expect_family):
             kw = dict(row_mask=mask, scale=scale, res=hr.view, res_masked=True, res2=hr2.view)
             kw_plain = dict(kw, res=res, res2=res2)
             want = y * mk * scale.double().cpu() + res[sample].double().cpu() * mk + res2[sample].double().cpu()
-        family = []
-        ops.conv_gemm(wrap(hx.view), w, bias, out=ho.view, _family=family, **kw)
+        a, _ = ops.gemm_args(wrap(hx.view), w, bias, out=ho.view, **kw)
+        family = [ops.gemm_family(a)]
+        ops.launch_gemm(a)
         assert family[0] == expect_family, f"the call ran kernel family {family[0]}, the case is built for {expect_family}"
         plain = ops.conv_gemm(wrap(xin), w, bias, **kw_plain)
         W.check([ho], ins)

@@ -358,3 +358,26 @@ def test_every_host_side_switch_is_documented():
     assert len(seen) >= 12
     missing = sorted(s for s in seen if s not in text)
     assert not missing, f"switches read by the host code but not in INTEGRATION.md: {missing}"
+
+
+def test_split_operand_forms_and_public_gemm_signature():
+    """ops._split_forms: the one table split_conv_weight, split_conv_weight_dgrad and presplit_weights take a weight's operand
+    forms from -- (cache attribute, format, offset, R, Q, taps, strides along r / tap / q), written out by hand: the forward
+    operand is the tap-major packed weight (Cin*k % 32 == 0), the input-gradient operand the transposed, tap-flipped matrix
+    (N*k % 32 == 0), each cached per element format.  And ops.conv_gemm takes no private keyword."""
+    import inspect
+    from vrdone_amd import _hip, ops
+    BF, F16 = _hip.PAIR_BF16, _hip.PAIR_F16
+    forms = lambda shape, fwd, bwd: [tuple(f) for f in ops._split_forms(shape, fwd, bwd)]        # noqa: E731
+    # (N, Cin, k) = (64, 32, 3): both forms
+    assert forms((64, 32, 3), BF, F16) == [("_vrd_split", BF, 0, 64, 32, 3, 96, 1, 3),
+                                           ("_vrd_split_t_f16", F16, 2, 32, 64, 3, 3, -1, 96)]
+    assert forms((64, 32, 3), F16, BF) == [("_vrd_split_f16", F16, 0, 64, 32, 3, 96, 1, 3),
+                                           ("_vrd_split_t", BF, 2, 32, 64, 3, 3, -1, 96)]
+    # (48, 32, 1): N*k = 48, forward only
+    assert forms((48, 32, 1), F16, F16) == [("_vrd_split_f16", F16, 0, 48, 32, 1, 32, 1, 1)]
+    assert forms((48, 32, 1), BF, BF) == [("_vrd_split", BF, 0, 48, 32, 1, 32, 1, 1)]
+    # (64, 5, 3): Cin*k = 15, input gradient only
+    assert forms((64, 5, 3), BF, BF) == [("_vrd_split_t", BF, 2, 5, 64, 3, 3, -1, 15)]
+    assert forms((64, 5, 3), BF, F16) == [("_vrd_split_t_f16", F16, 2, 5, 64, 3, 3, -1, 15)]
+    assert not [p for p in inspect.signature(ops.conv_gemm).parameters if p.startswith("_")]

@@ -191,8 +191,8 @@ class Linear(_Differentiable):
 
     @staticmethod
     def forward(ctx, x, weight, bias, row_mask):
-        family = []
-        y = ops.conv_gemm(x, weight, bias, row_mask=row_mask, _family=family)
+        a, y = ops.gemm_args(x, weight, bias, row_mask=row_mask)
+        ops.launch_gemm(a)
         ctx.save_for_backward(x, weight)
         ctx.row_mask, ctx.has_bias = row_mask, bias is not None
         # the backward runs in the arithmetic of ITS forward, whatever the mode is by then (MaskVRD.forward_training repeats a
@@ -202,7 +202,7 @@ class Linear(_Differentiable):
         # taken only where the forward GEMM above split the same rows (and reported on them, tag 16 of ops.f16_range_flag); a
         # forward on the exact-f32 kernel (Cin * k % 32 != 0, unaligned rows: the library says which, vrd_gemm_family) is
         # followed by the exact-f32 weight gradient
-        ctx.f16_wgrad = ctx.bfmt != PAIR_F16 or family[0] != _hip.K_GEMM
+        ctx.f16_wgrad = ctx.bfmt != PAIR_F16 or ops.gemm_family(a) != _hip.K_GEMM
         ctx.det = ops.get_deterministic()             # (so is the deterministic mode)
         return y
 
@@ -225,7 +225,7 @@ class Linear(_Differentiable):
             fused = (ctx.split_bwd and (N * k) % 32 == 0 and N % 4 == 0 and dy.stride(-2) % 4 == 0 and
                      dy.data_ptr() % 16 == 0 and weight.is_contiguous())
             # the unfused fallback: bf16 planes in either split mode (gradients have no fixed scale), and EXACT f32 products
-            # (_split_fmt 0, not None = "the mode at hand") behind an f32 forward -- the backward of a step that was repeated in
+            # (split_fmt 0, not None = "the mode at hand") behind an f32 forward -- the backward of a step that was repeated in
             # f32 runs after that block has been left, in whatever mode is current by then
             gfmt = PAIR_BF16 if ctx.split_bwd else 0
             # f16x3 mode: the gradient's power-of-two factor for its f16 planes (one absmax launch, shared with the weight gradient)
@@ -234,15 +234,15 @@ class Linear(_Differentiable):
                 fused = False
             if k == 1:       # masking the rows of dy = masking the rows of dx
                 if fused:
-                    dx = ops.conv_gemm(dy, wd, None, row_mask=mask, _dgrad=True, _a_scale=gs, _bfmt=ctx.bfmt)
+                    dx = ops.conv_dgrad(dy, wd, row_mask=mask, a_scale=gs, fmt=ctx.bfmt)
                 else:
-                    dx = ops.conv_gemm(dy, weight.detach().permute(1, 0, 2).contiguous(), None, row_mask=mask, _split_fmt=gfmt)
+                    dx = ops.conv_gemm(dy, weight.detach().permute(1, 0, 2).contiguous(), None, row_mask=mask, split_fmt=gfmt)
             else:            # dx[r] = sum_tap (dy * mask)[r - (tap - 1)] W[:, :, tap]: a k=3 conv with flipped, transposed taps
                 g = rowcol_scale(dy, row_mask=mask) if mask is not None else dy
                 if fused:
-                    dx = ops.conv_gemm(g, wd, None, _dgrad=True, _a_scale=gs, _bfmt=ctx.bfmt)
+                    dx = ops.conv_dgrad(g, wd, a_scale=gs, fmt=ctx.bfmt)
                 else:
-                    dx = ops.conv_gemm(g, weight.detach().flip(2).permute(1, 0, 2).contiguous(), None, _split_fmt=gfmt)
+                    dx = ops.conv_gemm(g, weight.detach().flip(2).permute(1, 0, 2).contiguous(), None, split_fmt=gfmt)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             packed = _zeros(N, k * Cin, device=dy.device)

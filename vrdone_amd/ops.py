@@ -8,6 +8,7 @@ without copies.  Masks are ``torch.bool``/``uint8`` tensors of shape ``(B, T)``.
 PyTorch is used for device memory and the current stream only; every op below runs one
 hand-written HIP kernel.  Nothing here works on CPU tensors.
 """
+import collections
 import ctypes as C
 import os
 
@@ -202,6 +203,11 @@ def _unwrap(x):
     return (x.t, x.width) if isinstance(x, Pair) else (x, 0)
 
 
+def _as_pair(t, width, fmt):
+    """what an op returns for the buffer `t` it wrote with out_pair = fmt: the Pair, or t itself for f32 rows (fmt 0)"""
+    return Pair(t, width, fmt) if fmt else t
+
+
 def _mask_ptr(m, rows):
     if m is None:
         return None
@@ -233,27 +239,38 @@ def _keep_for_capture(val):
     return val
 
 
-def _cached(w, slot, build):
-    key = (w.data_ptr(), w._version)
-    hit = getattr(w, slot, None)
+def _version_key(t):
+    return (t.data_ptr(), t._version)
+
+
+def _entry(owner, slot, key):
+    """The (key, value, scope) entry of `slot` on `owner` when it was made for `key`, else None.  scope: the presplit_scope
+    whose capture presplit_weights published the entry in, None for an entry made outside any capture."""
+    hit = getattr(owner, slot, None)
+    return hit if hit is not None and hit[0] == key else None
+
+
+def _derived(owner, slot, key, build):
+    """The operand `build()` derives from `owner` (a weight, a mask), cached in its attribute `slot` for as long as `key`
+    -- (address, version) of everything it was derived from -- holds."""
+    hit = _entry(owner, slot, key)
     if _capturing():
         # inside a recording only what presplit_weights built inside the SAME recording scope counts (its launch is part of
-        # the graph; train_graph opens one scope around a recording's forward and backward graphs)
-        if hit is not None and hit[0] == key and len(hit) > 2 and hit[2] is not None and hit[2] is _presplit_scope:
+        # the graph; train_graph opens one scope around a recording's forward and backward graphs); nothing is stored
+        if hit is not None and hit[2] is not None and hit[2] is _presplit_scope:
             return hit[1]
         return _keep_for_capture(build())
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    val = build()
-    setattr(w, slot, (key, val))
-    return val
+    if hit is None:
+        hit = (key, build(), None)
+        setattr(owner, slot, hit)
+    return hit[1]
 
 
 def packed_conv_weight(w):
     """Conv1d weight (N, Cin, k) -> (N, k*Cin) tap-major for k = 3; k = 1 weights are used in place."""
     if w.shape[-1] == 1:
         return w
-    return _cached(w, "_vrd_packed", lambda: w.detach().permute(0, 2, 1).contiguous())
+    return _derived(w, "_vrd_packed", _version_key(w), lambda: w.detach().permute(0, 2, 1).contiguous())
 
 
 # GEMM precision mode.
@@ -378,7 +395,6 @@ def f16_range_flag(device=None):
         dev = torch.device("cuda", torch.cuda.current_device())
     flag = _range_flags.get(dev.index)
     if flag is None:
-        import ctypes as C
         with torch.cuda.device(dev):
             ptr = C.c_void_p()
             _hip.check(lib.vrd_f16_range_flag(C.byref(ptr)), "vrd_f16_range_flag")
@@ -417,37 +433,53 @@ class SplitWeight:
         a.w_scale = self.scale.data_ptr() if self.scale is not None else None
 
 
-def _split_weight(w, offset, R, Q, taps, sr, st, sq, fmt=None):
-    assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and (taps * Q) % 32 == 0
-    fmt = pair_fmt() if fmt is None else fmt
+def _split_forms(shape, fwd_fmt, bwd_fmt):
+    """The split operands a Conv1d weight of `shape` (N, Cin, k) has, as vrd_split_weight / a vrd_split_job reads them from the
+    parameter: (cache attribute -- one per element format --, fmt, offset of the first element, R rows, Q, taps, and the
+    parameter's strides along r, tap and q).  The forward operand (fwd_fmt; Cin*k % 32 == 0) is the tap-major packed weight,
+    the input-gradient operand (bwd_fmt; N*k % 32 == 0) the (Cin, k*N) matrix [c][tap*N + n] = w[n][c][k-1-tap]: transposed,
+    taps flipped.  A format of None leaves that operand out."""
+    N, Cin, k = shape
+    f16 = lambda fmt: "_f16" if fmt == _hip.PAIR_F16 else ""      # noqa: E731
+    if fwd_fmt is not None and (Cin * k) % 32 == 0:
+        yield ("_vrd_split" + f16(fwd_fmt), fwd_fmt, 0, N, Cin, k, Cin * k, 1, k)
+    if bwd_fmt is not None and (N * k) % 32 == 0:
+        yield ("_vrd_split_t" + f16(bwd_fmt), bwd_fmt, k - 1, Cin, N, k, k, -1, Cin * k)
+
+
+def _alloc_split(R, K, fmt, device):
+    """the empty SplitWeight of an (R, K) operand: planes, and in the f16 format the 4 floats of its scale"""
     f16 = fmt == _hip.PAIR_F16
-    out = torch.empty(R, taps * Q // 32, 2, 32, device=w.device, dtype=torch.float16 if f16 else torch.bfloat16)
-    scale = torch.empty(4, device=w.device, dtype=torch.float32) if f16 else None
-    _hip.check(lib.vrd_split_weight(w.data_ptr() + 4 * offset, R, Q, taps, sr, st, sq, out.data_ptr(), fmt, _ptr(scale), _stream()),
-               "vrd_split_weight")
-    return SplitWeight(out, fmt, scale)
+    return SplitWeight(torch.empty(R, K // 32, 2, 32, device=device, dtype=torch.float16 if f16 else torch.bfloat16), fmt,
+                       torch.empty(4, device=device, dtype=torch.float32) if f16 else None)
 
 
-def _split_slot(base, fmt=None):
-    """the cache attribute of a weight's split operand: one per element format"""
-    return base + ("_f16" if (pair_fmt() if fmt is None else fmt) == _hip.PAIR_F16 else "")
+def _split_operand(w, forms):
+    """the one operand of `forms` (_split_forms), from w's cache or built by a launch of its own"""
+    form = next(forms, None)
+    assert form is not None, "the K of a split operand (Cin*k forward, N*k input gradient) must be a multiple of 32"
+    slot, fmt, offset, R, Q, taps, sr, st, sq = form
+
+    def build():
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+        out = _alloc_split(R, taps * Q, fmt, w.device)
+        _hip.check(lib.vrd_split_weight(w.data_ptr() + 4 * offset, R, Q, taps, sr, st, sq, out.data_ptr(), fmt, _ptr(out.scale), _stream()),
+                   "vrd_split_weight")
+        return out
+    return _derived(w, slot, _version_key(w), build)
 
 
 def split_conv_weight(w, fmt=None):
     """SplitWeight of the tap-major packed weight (K = Cin*k, K % 32 == 0): (N, K/32, 2, 32) 16-bit, per block of 32 K
     positions [32 x hi | 32 x lo] -- the pair-row block format of vrd_common.h, so one 128-byte line holds what a K step
     needs from a weight row -- in the current mode's element format.  Built once per weight, weight version and format."""
-    N, Cin, k = w.shape
-    return _cached(w, _split_slot("_vrd_split", fmt), lambda: _split_weight(w.detach(), 0, N, Cin, k, Cin * k, 1, k, fmt))
+    return _split_operand(w, _split_forms(w.shape, pair_fmt() if fmt is None else fmt, None))
 
 
 def split_conv_weight_dgrad(w, fmt=None):
-    """The same operand for the input-gradient GEMM of the conv: the (Cin, k*N) matrix [c][tap*N + n] = w[n][c][k-1-tap]
-    (transposed, taps flipped), straight from the parameter, in the backward GEMMs' element format (backward_fmt; `fmt`: the
-    format the op's forward ran under, autograd.Linear)."""
-    N, Cin, k = w.shape
-    fmt = backward_fmt() if fmt is None else fmt
-    return _cached(w, _split_slot("_vrd_split_t", fmt), lambda: _split_weight(w.detach(), k - 1, Cin, N, k, k, -1, Cin * k, fmt))
+    """The same operand for the input-gradient GEMM of the conv (K = N*k), straight from the parameter, in the backward
+    GEMMs' element format (backward_fmt; `fmt`: the format the op's forward ran under, autograd.Linear)."""
+    return _split_operand(w, _split_forms(w.shape, None, backward_fmt() if fmt is None else fmt))
 
 
 # ---- all split operands of a training step in one launch
@@ -474,73 +506,71 @@ class presplit_scope:
         return False
 
 
+# what one vrd_split_weights launch needs: the job table on the device, every 32 x 32 tile's job and index within it, the jobs'
+# (weight address, cache attribute, persistent SplitWeight) and their number
+_SplitPlan = collections.namedtuple("_SplitPlan", "table chunk_job chunk_index outs n_jobs")
+
+
+def _split_plan(weights, plans):
+    """presplit_weights' plan for `weights` in the current mode, found in `plans` or built into it; None when there is nothing
+    to split or when it would have to be built (and uploaded) during a graph capture."""
+    fmt, bfmt = pair_fmt(), backward_fmt()
+    # (the plan is keyed on the weights' addresses, shapes and the element format: another model whose parameters land on
+    # the same addresses with other shapes, or a change of mode, builds its own)
+    key = (fmt, bfmt) + tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
+    for old in [k for k in plans if k != key]:        # operands of another mode / of parameters that were replaced
+        del plans[old]
+    plan = plans.get(key)
+    if plan is not None or _capturing():
+        return plan
+    jobs, outs, chunk_job, chunk_index = [], [], [], []
+    for w in weights:
+        assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 3
+        for slot, jf, offset, R, Q, taps, sr, st, sq in _split_forms(w.shape, fmt, bfmt):
+            out = _alloc_split(R, taps * Q, jf, w.device)
+            jobs.append(_hip.SplitJob(src=w.data_ptr() + 4 * offset, out=out.data_ptr(), R=R, Q=Q, taps=taps, fmt=jf, sr=sr, st=st,
+                                      sq=sq, scale=_ptr(out.scale)))
+            n_tiles = -(-R // 32) * (taps * Q // 32)          # 32 x 32 tiles: row block x K block
+            chunk_job.extend([len(jobs) - 1] * n_tiles)
+            chunk_index.extend(range(n_tiles))
+            outs.append((w.data_ptr(), slot, out))
+    if not jobs:
+        return None
+    dev = weights[0].device
+    table = torch.frombuffer(bytearray(bytes((_hip.SplitJob * len(jobs))(*jobs))), dtype=torch.uint8).to(dev)
+    plan = plans[key] = _SplitPlan(table, torch.tensor(chunk_job, dtype=torch.int32, device=dev),
+                                   torch.tensor(chunk_index, dtype=torch.int32, device=dev), outs, len(jobs))
+    return plan
+
+
 def presplit_weights(weights, plans):
     """The split-precision operands of `weights` (Conv1d parameters (N, Cin, k)) -- the forward operand where Cin*k % 32 == 0
     and the input-gradient operand where N*k % 32 == 0 -- built by ONE vrd_split_weights launch into persistent buffers and
     left in the weights' operand caches (the attributes split_conv_weight / split_conv_weight_dgrad look at) for the current
     version of each weight.  A training step otherwise
     re-splits every weight with a launch of its own, twice (after every optimiser update): 242 launches on the 24-pair batch.
-    plans: a dict the caller owns (the model's): tuple of weight addresses -> (job table on the device, chunk tables, the
-    persistent operand buffers).  Plans of another mode or of replaced parameters are dropped from it here; a graph
+    plans: a dict the caller owns (the model's): tuple of weight addresses -> _SplitPlan (job table on the device, chunk
+    tables, the persistent operand buffers).  Plans of another mode or of replaced parameters are dropped from it here; a graph
     recording that captured a plan's launch keeps its own reference (presplit_scope.plans), so the buffers its replays
     read and write outlive the dict entry.
     The job table is built (and uploaded) on the first call for a set of weights -- outside any graph capture: inside one,
     without a table, nothing is done and the per-weight launches run as before."""
     if _precision not in ("bf16x3", "f16x3", "f16x1") or not weights or not _presplit_on:
         return
-    fmt = pair_fmt()
-    # (the plan is keyed on the weights' addresses, shapes and the element format: another model whose parameters land on
-    # the same addresses with other shapes, or a change of mode, builds its own)
-    key = (fmt, backward_fmt()) + tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
-    for old in [k for k in plans if k != key]:        # operands of another mode / of parameters that were replaced
-        del plans[old]
-    plan = plans.get(key)
+    plan = _split_plan(weights, plans)
     if plan is None:
-        if _capturing():
-            return
-        import ctypes as C
-        jobs, outs, chunk_job, chunk_index = [], [], [], []
-        for w in weights:
-            assert w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 3
-            N, Cin, k = w.shape
-            forms = []
-            if (Cin * k) % 32 == 0:
-                forms.append((_split_slot("_vrd_split"), 0, N, Cin, k, Cin * k, 1, k))           # = split_conv_weight
-            if (N * k) % 32 == 0:       # = split_conv_weight_dgrad: the backward GEMMs' format
-                forms.append((_split_slot("_vrd_split_t", backward_fmt()), k - 1, Cin, N, k, k, -1, Cin * k))
-            for slot, offset, R, Q, taps, sr, st, sq in forms:
-                jf = backward_fmt() if slot.startswith("_vrd_split_t") else fmt
-                jf16 = jf == _hip.PAIR_F16
-                out = torch.empty(R, taps * Q // 32, 2, 32, device=w.device, dtype=torch.float16 if jf16 else torch.bfloat16)
-                scale = torch.empty(4, device=w.device, dtype=torch.float32) if jf16 else None
-                jobs.append(_hip.SplitJob(src=w.data_ptr() + 4 * offset, out=out.data_ptr(), R=R, Q=Q, taps=taps, fmt=jf, sr=sr, st=st,
-                                          sq=sq, scale=_ptr(scale)))
-                n_tiles = -(-R // 32) * (taps * Q // 32)          # 32 x 32 tiles: row block x K block
-                chunk_job.extend([len(jobs) - 1] * n_tiles)
-                chunk_index.extend(range(n_tiles))
-                outs.append((w.data_ptr(), slot, SplitWeight(out, jf, scale)))
-        if not jobs:
-            return
-        raw = bytes((_hip.SplitJob * len(jobs))(*jobs))
-        dev = weights[0].device
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-        plan = (table, torch.tensor(chunk_job, dtype=torch.int32, device=dev), torch.tensor(chunk_index, dtype=torch.int32, device=dev), outs,
-                len(jobs))
-        plans[key] = plan
-    table, cj, ci, outs, n_jobs = plan
-    if _capturing() and _presplit_scope is not None and not any(q is plan for q in _presplit_scope.plans):
-        _presplit_scope.plans.append(plan)
+        return
+    scope = _presplit_scope if _capturing() else None
+    if scope is not None and not any(q is plan for q in scope.plans):
+        scope.plans.append(plan)
     by_ptr = {w.data_ptr(): w for w in weights}
-    if not _capturing():        # nothing moved since the last call (an evaluation of the same weights, a second forward): keep the operands
-        def current(ptr, slot):
-            hit = getattr(by_ptr[ptr], slot, None)
-            return hit is not None and hit[0] == (ptr, by_ptr[ptr]._version) and hit[1] is not None
-        if all(current(ptr, slot) for ptr, slot, _ in outs):
-            return
-    _hip.check(lib.vrd_split_weights(table.data_ptr(), n_jobs, cj.data_ptr(), ci.data_ptr(), cj.numel(), _stream()), "vrd_split_weights")
-    for ptr, slot, out in outs:
-        w = by_ptr[ptr]
-        setattr(w, slot, ((ptr, w._version), out, _presplit_scope if _capturing() else None))
+    # nothing moved since the last call (an evaluation of the same weights, a second forward): keep the operands
+    if not _capturing() and all(_entry(by_ptr[ptr], slot, _version_key(by_ptr[ptr])) is not None for ptr, slot, _ in plan.outs):
+        return
+    _hip.check(lib.vrd_split_weights(plan.table.data_ptr(), plan.n_jobs, plan.chunk_job.data_ptr(), plan.chunk_index.data_ptr(),
+                                     plan.chunk_job.numel(), _stream()), "vrd_split_weights")
+    for ptr, slot, out in plan.outs:
+        setattr(by_ptr[ptr], slot, (_version_key(by_ptr[ptr]), out, scope))
 
 
 def bct_to_btc(x, c0, count, out, pair=False, frames=None, index=None):
@@ -555,7 +585,7 @@ def bct_to_btc(x, c0, count, out, pair=False, frames=None, index=None):
     assert rows == B * T and cols == count and T <= Tx
     fmt = _fmt(pair)
     _hip.check(lib.vrd_bct_to_btc(x.data_ptr(), B, Ct, T, c0, count, p, ld, fmt, Tx, _ptr(index), _stream()), "vrd_bct_to_btc")
-    return Pair(out, count, fmt) if fmt else out
+    return _as_pair(out, count, fmt)
 
 
 def pair_table(feats):
@@ -572,6 +602,22 @@ def pair_table(feats):
             torch.tensor([f.shape[1] for f in feats], dtype=torch.int32, device=dev))
 
 
+def _new_f32(device):
+    """shape -> an uninitialised float32 buffer on `device`"""
+    return lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)
+
+
+def _len_mask(lens, T, device):
+    """(B, T) bool validity mask of sequences of lens[b] frames"""
+    return torch.arange(T, device=device)[None, :] < lens[:, None]
+
+
+def _wide_pairs(vis, clip, V, Cc, fmt):
+    """the wide visual / clip buffers a batch builder filled with pair_wide = fmt, as its callers get them: Pairs when fmt;
+    a buffer that was not built stays None"""
+    return tuple(t if t is None else _as_pair(t, width, fmt) for t, width in ((vis, V), (clip, Cc)))
+
+
 def pack_pairs(table, lens, T, V, Cc, S, E, pair_wide):
     """Batch the pairs described by `table` (B device pointers) / `lens` (B) straight into the backbone's
     channels-last operand buffers (see vrd_pack_pairs).
@@ -579,7 +625,7 @@ def pack_pairs(table, lens, T, V, Cc, S, E, pair_wide):
     B = table.shape[0]
     dev = table.device
     assert table.dtype == torch.int64 and lens.dtype == torch.int32 and table.is_contiguous() and lens.is_contiguous()
-    new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+    new = _new_f32(dev)
     vis, so_box, ent = new(2 * B, T, V), new(B, T, S), new(2 * B, T, E)
     clip = new(2 * B, T, Cc) if Cc else None
     a = _hip.PackArgs()
@@ -588,11 +634,7 @@ def pack_pairs(table, lens, T, V, Cc, S, E, pair_wide):
     a.vis, a.clip, a.so_box, a.ent = vis.data_ptr(), _ptr(clip), so_box.data_ptr(), ent.data_ptr()
     a.pair_wide = _fmt(pair_wide)
     _hip.check(lib.vrd_pack_pairs(C.byref(a), _stream()), "vrd_pack_pairs")
-    mask = torch.arange(T, device=dev)[None, :] < lens[:, None]
-    if a.pair_wide:
-        vis = Pair(vis, V, a.pair_wide)
-        clip = Pair(clip, Cc, a.pair_wide) if Cc else None
-    return vis, clip, so_box, ent, mask
+    return (*_wide_pairs(vis, clip, V, Cc, a.pair_wide), so_box, ent, _len_mask(lens, T, dev))
 
 
 def gather_pairs(source, sel, T, S, E, pair_wide):
@@ -614,7 +656,7 @@ def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False
     dev = source.vis.device
     V, Cc = source.n_visual, source.n_clip
     assert s_row.dtype == o_row.dtype == torch.int64 and lens.dtype == torch.int32 and s_row.shape == o_row.shape == (B,)
-    new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+    new = _new_f32(dev)
     so_box, ent = new(B, T, S), new(2 * B, T, E)
     vis = None if boxes_only else new(2 * B, T, V)
     clip = new(2 * B, T, Cc) if Cc and not boxes_only else None
@@ -629,18 +671,14 @@ def gather_rows(source, s_row, o_row, lens, T, S, E, pair_wide, boxes_only=False
         assert seq_wh.dtype == torch.float32 and seq_wh.shape == (B, 2) and seq_wh.is_contiguous() and seq_wh.device == dev
         a.seq_wh = seq_wh.data_ptr()
     _hip.check(lib.vrd_gather_pairs(C.byref(a), _stream()), "vrd_gather_pairs")
-    mask = torch.arange(T, device=dev)[None, :] < lens[:, None]
-    if a.pair_wide and not boxes_only:
-        vis = Pair(vis, V, a.pair_wide)
-        clip = Pair(clip, Cc, a.pair_wide) if Cc else None
-    return vis, clip, so_box, ent, mask
+    return (*_wide_pairs(vis, clip, V, Cc, a.pair_wide), so_box, ent, _len_mask(lens, T, dev))
 
 
 def train_buffers(B, T, V, Cc, S, E, device):
     """Fresh operand buffers of a B-sequence training batch, in gather_train's `out=` order: [vis (2B, T, V), so_box
     (B, T, S), ent (2B, T, E), mask (B, T) bool] + [clip (2B, T, Cc)] when Cc."""
-    new = lambda *shape: torch.empty(*shape, device=device, dtype=torch.float32)      # noqa: E731
-    bufs = [new(2 * B, T, V), new(B, T, S), new(2 * B, T, E), torch.empty(B, T, device=device, dtype=torch.bool)]
+    new = _new_f32(device)
+    bufs =[new(2 * B, T, V), new(B, T, S), new(2 * B, T, E), torch.empty(B, T, device=device, dtype=torch.bool)]
     return bufs + ([new(2 * B, T, Cc)] if Cc else [])
 
 
@@ -676,10 +714,7 @@ def gather_train(source, tables, T, S, E, pair_wide, out=None):
     a.out_mask, a.out_targets = mask.data_ptr(), targets.data_ptr()
     a.pair_wide = _fmt(pair_wide)
     _hip.check(lib.vrd_gather_train(C.byref(a), _stream()), "vrd_gather_train")
-    if a.pair_wide:
-        vis = Pair(vis, V, a.pair_wide)
-        clip = Pair(clip, Cc, a.pair_wide) if Cc else None
-    return vis, clip, so_box, ent, mask, targets
+    return (*_wide_pairs(vis, clip, V, Cc, a.pair_wide), so_box, ent, mask, targets)
 
 
 def assemble_pairs(streams, snippets, stream_row, lens, T, piece, reach):
@@ -730,14 +765,10 @@ def row_blocks(mask):
     """Padding map of a (B, T) validity mask for vrd_gemm: (order, n_active per segment, segment length) -- two device
     int32 tensors made by vrd_row_blocks -- or None when the rows do not split into aligned 32-row blocks.  Cached on
     the mask tensor object (keyed on its address and version counter), so it dies with it."""
-    hit = getattr(mask, "_vrd_row_blocks", None)
-    key = (mask.data_ptr(), mask._version)
-    capturing = _capturing()
-    if hit is not None and hit[0] == key and not capturing:
-        return hit[1]
-    rows = mask.numel()
-    val = None
-    if rows % 32 == 0 and mask.is_contiguous() and mask.data_ptr() % 16 == 0 and mask.dtype in (torch.bool, torch.uint8):
+    def build():
+        rows = mask.numel()
+        if not (rows % 32 == 0 and mask.is_contiguous() and mask.data_ptr() % 16 == 0 and mask.dtype in (torch.bool, torch.uint8)):
+            return None
         # about eight segments (one per XCD of the GEMM's tile order), each a whole number of 256-row tiles
         nblk = rows // 32
         seg_len = 8 * (((nblk + 7) // 8 + 7) // 8)
@@ -745,42 +776,15 @@ def row_blocks(mask):
         count = torch.empty((nblk + seg_len - 1) // seg_len, device=mask.device, dtype=torch.int32)
         _hip.check(lib.vrd_row_blocks(mask.data_ptr(), rows, seg_len, order.data_ptr(), count.data_ptr(), _stream()),
                    "vrd_row_blocks")
-        val = (order, count, seg_len)
-    if capturing:
-        return _keep_for_capture(val)
-    mask._vrd_row_blocks = (key, val)
-    return val
+        return order, count, seg_len
+    return _derived(mask, "_vrd_row_blocks", _version_key(mask), build)
 
 
-def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False,
-              res2=None, out=None, out_pair=False, skip_rows=None, row_scale=None, _launch=None, _dgrad=False, _split_fmt=None,
-              _a_scale=None, _bfmt=None, _family=None):
-    """Dense Conv1d (k = 1 or 3, stride 1, zero padding k//2) with the fused epilogue of
-    vrd_gemm.  x: (B, T, Cin) tensor or Pair; weight: the Conv1d parameter (N, Cin, k).
-    out_pair: write the result as pair rows of width N (returns a Pair).
-    skip_rows: validity mask of the rows; aligned 32-row blocks without a valid row skip the contraction (exact with
-    row_mask, which is then the default; without row_mask those rows hold bias-only filler, so pass it only where
-    no valid row ever reads a padded one: projections feeding masked attention, an MLP's hidden layer).
-    row_scale (rows,): per-row factor on the branch term (stochastic depth, blocks.py:1107-1120); autograd path only.
-    _split_fmt: element format of the split products instead of the mode's (the unfused backward GEMMs pass PAIR_BF16; 0 = exact
-    f32 products whatever the mode, None = the mode's format).
-    _family: a list that receives the kernel family (_hip.K_GEMM* = enum vrd_kernel_id) the library runs this call on.
-    _dgrad / _a_scale: the conv's input-gradient GEMM on the parameter's transposed operand; x is then a gradient, and in the
-    f16 format its rows are split at the power-of-two factor of grad_scale(x) (vrd_gemm_args.a_scale).
-    Under autograd (`recording`) the op runs as autograd.conv_gemm and returns a fresh tensor (`out` is ignored)."""
-    # row_scale (stochastic depth, sampled whenever the model trains) lives in the autograd form's epilogue: it goes there even
-    # when nothing of this call needs a gradient (a frozen sub-module under requires_grad_(False), reference blocks.py:1107-1120
-    # drops paths regardless)
-    if _launch is None and not isinstance(x, Pair) and (recording(x, weight, bias, scale, res, res2) or row_scale is not None):
-        from . import autograd
-        assert not out_pair
-        return autograd.conv_gemm(x, weight, bias, act=act, row_mask=row_mask, scale=scale, row_scale=row_scale, res=res,
-                                  res_masked=res_masked, res2=res2)
-    assert row_scale is None, "row_scale (drop-path sampling) exists for plain f32 rows only"
-    N, Cin, k = weight.shape
-    if _dgrad:          # the conv's input gradient: weight (Cin_of_x... = N_w, Cin_w, k) acts as the (Cin_w, N_w, k) flipped conv
-        N, Cin = Cin, N
-    x_fmt = x.fmt if isinstance(x, Pair) else 0
+def _gemm_struct(x, N, Cin, k, W, split, bias=None, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False, res2=None,
+                 out=None, out_pair=False, skip_rows=None):
+    """(vrd_gemm_args, result) of one GEMM problem: the rows of x (tensor or Pair, Cin channels) against an (N, k*Cin) tap-major
+    operand -- `W` its f32 form (None: there is none), `split` its SplitWeight (None: exact f32 products) -- with conv_gemm's
+    epilogue.  Nothing is launched."""
     x, a_width = _unwrap(x)
     pa, rows, cols, lda = _rows(x)
     assert cols == Cin, f"input has {cols} channels, weight expects {Cin}"
@@ -790,40 +794,22 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
     pc, rows_c, cols_c, ldc = _rows(out)
     assert rows_c == rows and cols_c == N
     a = _hip.GemmArgs()
-    if _dgrad:
-        # split-precision only (autograd.Linear checks): the operand is built from the parameter in one launch; the f32
-        # weight pointer is not read by the split-precision kernels and points at the same buffer
-        assert (Cin * k) % 32 == 0 and not a_width
-        wt = split_conv_weight_dgrad(weight, _bfmt)
-        a.W = wt.data_ptr()
-        wt.set_args(a)
-        if wt.fmt == _hip.PAIR_F16:      # x is a gradient: its f16 planes need its own power-of-two factor
-            assert _a_scale is not None
-            a.a_scale = _a_scale.data_ptr()
-    else:
-        a.W = _param_ptr(packed_conv_weight(weight), x, "conv weight")
+    # (the split-precision kernels do not read the f32 weight pointer: without an f32 form it points at the split operand)
+    a.W = split.data_ptr() if W is None else _param_ptr(W, x, "conv weight")
+    if split is not None:
+        split.set_args(a)
     a.A, a.lda, a.bias = pa, lda, _param_ptr(bias, x, "conv bias")
     a.C, a.ldc = pc, ldc
     a.M, a.N, a.Cin, a.taps, a.T = rows, N, Cin, k, T
     a.act = act
     a.row_mask = _mask_ptr(row_mask, rows)
     a.scale = _param_ptr(scale, x, "drop-path scale")
-    if a_width:
-        assert pair_fmt() and x_fmt == pair_fmt() and Cin % 32 == 0, "pair input needs the split-precision mode it was made in and Cin % 32 == 0"
-    w_fmt = pair_fmt() if _split_fmt is None else _split_fmt
-    if _dgrad:
-        w_fmt = a.split_fmt
-    assert not (a_width and w_fmt != x_fmt) and not (out_pair and w_fmt != pair_fmt())
-    if not _dgrad and w_fmt and (Cin * k) % 32 == 0:
-        split_conv_weight(weight, w_fmt).set_args(a)
-        if w_fmt == _hip.PAIR_F16 and _split_fmt is None:
-            a.products = products()
     a.a_pair_width = a_width
     a.c_pair = _fmt(out_pair)
     if skip_rows is None:
         skip_rows = row_mask
     # (the kernels that take the block list: the 256 x 256 split kernel -- pair-row input -- and the exact-f32 kernel)
-    f32_kernel = not a_width and not _dgrad and not (w_fmt and (Cin * k) % 32 == 0)
+    f32_kernel = not a_width and split is None
     if _skip_padding and skip_rows is not None and (a_width or f32_kernel) and rows >= SKIP_MIN_ROWS and skip_rows.numel() == rows:
         blocks = row_blocks(skip_rows)
         if blocks is not None:
@@ -837,25 +823,87 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
         pr, rr, rc, ldr = _rows(res2)
         assert rr == rows and rc == N
         a.res2, a.ldres2 = pr, ldr
-    if _family is not None:
-        fam = lib.vrd_gemm_family(C.byref(a))
-        if fam < 0:
-            _hip.check(fam, "vrd_gemm_family")
-        _family.append(fam)
-    if _launch is not None:            # conv_gemm_batch collects the argument structs instead of launching
-        _launch.append(a)
-    else:
-        _hip.check(lib.vrd_gemm(C.byref(a), _stream()), "vrd_gemm")
-    return Pair(out, N, a.c_pair) if a.c_pair else out
+    return a, _as_pair(out, N, a.c_pair)
+
+
+def gemm_args(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False, res2=None, out=None,
+              out_pair=False, skip_rows=None, split_fmt=None):
+    """(a, result): the vrd_gemm_args of conv_gemm(x, weight, bias, ...) without autograd and the tensor or Pair its launch will
+    have written.  Nothing is launched: launch_gemm(a) does that, gemm_family(a) names the kernel family it runs on."""
+    N, Cin, k = weight.shape
+    x_fmt, a_width = (x.fmt, x.width) if isinstance(x, Pair) else (0, 0)
+    if a_width:
+        assert pair_fmt() and x_fmt == pair_fmt() and Cin % 32 == 0, "pair input needs the split-precision mode it was made in and Cin % 32 == 0"
+    w_fmt = pair_fmt() if split_fmt is None else split_fmt
+    assert not (a_width and w_fmt != x_fmt) and not (out_pair and w_fmt != pair_fmt())
+    split = split_conv_weight(weight, w_fmt) if w_fmt and (Cin * k) % 32 == 0 else None
+    a, result = _gemm_struct(x, N, Cin, k, packed_conv_weight(weight), split, bias, act, row_mask, scale, res, res_masked, res2, out,
+                             out_pair, skip_rows)
+    if split is not None and w_fmt == _hip.PAIR_F16 and split_fmt is None:
+        a.products = products()
+    return a, result
+
+
+def gemm_family(a):
+    """The kernel family (_hip.K_GEMM* = enum vrd_kernel_id) the library runs the vrd_gemm_args `a` on (vrd_gemm_family)."""
+    fam = lib.vrd_gemm_family(C.byref(a))
+    if fam < 0:
+        _hip.check(fam, "vrd_gemm_family")
+    return fam
+
+
+def launch_gemm(a):
+    _hip.check(lib.vrd_gemm(C.byref(a), _stream()), "vrd_gemm")
+
+
+def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False,
+              res2=None, out=None, out_pair=False, skip_rows=None, row_scale=None, split_fmt=None):
+    """Dense Conv1d (k = 1 or 3, stride 1, zero padding k//2) with the fused epilogue of
+    vrd_gemm.  x: (B, T, Cin) tensor or Pair; weight: the Conv1d parameter (N, Cin, k).
+    out_pair: write the result as pair rows of width N (returns a Pair).
+    skip_rows: validity mask of the rows; aligned 32-row blocks without a valid row skip the contraction (exact with
+    row_mask, which is then the default; without row_mask those rows hold bias-only filler, so pass it only where
+    no valid row ever reads a padded one: projections feeding masked attention, an MLP's hidden layer).
+    row_scale (rows,): per-row factor on the branch term (stochastic depth, blocks.py:1107-1120); autograd path only.
+    split_fmt: element format of the split products instead of the mode's (the unfused backward GEMMs pass PAIR_BF16; 0 = exact
+    f32 products whatever the mode, None = the mode's format).
+    Under autograd (`recording`) the op runs as autograd.conv_gemm and returns a fresh tensor (`out` is ignored)."""
+    # row_scale (stochastic depth, sampled whenever the model trains) lives in the autograd form's epilogue: it goes there even
+    # when nothing of this call needs a gradient (a frozen sub-module under requires_grad_(False), reference blocks.py:1107-1120
+    # drops paths regardless)
+    if not isinstance(x, Pair) and (recording(x, weight, bias, scale, res, res2) or row_scale is not None):
+        from . import autograd
+        assert not out_pair
+        return autograd.conv_gemm(x, weight, bias, act=act, row_mask=row_mask, scale=scale, row_scale=row_scale, res=res,
+                                  res_masked=res_masked, res2=res2)
+    assert row_scale is None, "row_scale (drop-path sampling) exists for plain f32 rows only"
+    a, result = gemm_args(x, weight, bias, act=act, row_mask=row_mask, scale=scale, res=res, res_masked=res_masked, res2=res2, out=out,
+                          out_pair=out_pair, skip_rows=skip_rows, split_fmt=split_fmt)
+    launch_gemm(a)
+    return result
+
+
+def conv_dgrad(dy, weight, *, row_mask=None, a_scale=None, fmt=None):
+    """The conv's input gradient as a GEMM on the parameter's transposed operand (split_conv_weight_dgrad, format `fmt`): the
+    weight (N, Cin, k) acts as the (Cin, N, k) tap-flipped conv on the f32 rows of the gradient dy (N channels).  Split-precision
+    only (autograd.Linear checks).  a_scale: in the f16 format the rows of dy are split at the power-of-two factor of
+    grad_scale(dy) (vrd_gemm_args.a_scale)."""
+    N, Cin, k = weight.shape
+    assert (N * k) % 32 == 0 and not isinstance(dy, Pair)
+    wt = split_conv_weight_dgrad(weight, fmt)
+    a, dx = _gemm_struct(dy, Cin, N, k, None, wt, row_mask=row_mask)
+    if wt.fmt == _hip.PAIR_F16:      # dy is a gradient: its f16 planes need its own power-of-two factor
+        assert a_scale is not None
+        a.a_scale = a_scale.data_ptr()
+    launch_gemm(a)
+    return dx
 
 
 def split_forward(x, weight, bias=None, **kwargs):
     """True when conv_gemm(x, weight, ...) runs a split-precision GEMM kernel in the current mode, False when it lands on the
     exact-f32 kernel: the library's own answer for the arguments conv_gemm builds (vrd_gemm_family), nothing is launched.  In the
     f16 modes only the split kernels check f32 rows against the operand range (tag 16 of f16_range_flag)."""
-    family = []
-    conv_gemm(x, weight, bias, _launch=[], _family=family, **kwargs)
-    return family[0] != _hip.K_GEMM
+    return gemm_family(gemm_args(x, weight, bias, **kwargs)[0]) != _hip.K_GEMM
 
 
 def conv_gemm_batch(calls):
@@ -865,12 +913,9 @@ def conv_gemm_batch(calls):
     assert 1 <= len(calls) <= 4
     if torch.is_grad_enabled():         # differentiable path: one op per projection
         return [conv_gemm(*args, **kwargs) for args, kwargs in calls]
-    collected, results = [], []
-    for args, kwargs in calls:
-        results.append(conv_gemm(*args, _launch=collected, **kwargs))
-    arr = (_hip.GemmArgs * len(collected))(*collected)
-    _hip.check(lib.vrd_gemm_batch(arr, len(collected), _stream()), "vrd_gemm_batch")
-    return results
+    collected, results = zip(*(gemm_args(*args, **kwargs) for args, kwargs in calls))
+    _hip.check(lib.vrd_gemm_batch((_hip.GemmArgs * len(collected))(*collected), len(collected), _stream()), "vrd_gemm_batch")
+    return list(results)
 
 
 def layernorm(x, gamma, beta, *, relu=False, post_add=None, out=None, pair=False):
@@ -893,7 +938,7 @@ def layernorm(x, gamma, beta, *, relu=False, post_add=None, out=None, pair=False
     _hip.check(lib.vrd_layernorm(px, ldx, py, ldy, rows, cols, _param_ptr(gamma, x, "LayerNorm weight"),
                                  _param_ptr(beta, x, "LayerNorm bias"), 1 if relu else 0,
                                  pa, lda, period, _fmt(pair), _stream()), "vrd_layernorm")
-    return Pair(out, cols) if _fmt(pair) else out
+    return _as_pair(out, cols, _fmt(pair))
 
 
 CONV_LN_MAXK = 32
@@ -927,7 +972,7 @@ def conv_ln(x, weight, bias, *, row_mask=None, gamma=None, beta=None, relu=False
     a.relu = 1 if relu else 0
     a.y, a.ldy, a.out_pair = py, ldy, _fmt(pair)
     _hip.check(lib.vrd_conv_ln(C.byref(a), _stream()), "vrd_conv_ln")
-    return Pair(out, N) if a.out_pair else out
+    return _as_pair(out, N, a.out_pair)
 
 
 _CONST_ROWS = {}
@@ -947,18 +992,11 @@ def _dwconv_block(w, bias, gamma, beta):
     """The on-chip parameter image of one dwconv_ln set (vrd_dwconv_ln_args.packed): taps tap-major | bias | gamma |
     beta.  Cached on the weight, keyed on the (address, version) of all four tensors."""
     parts = (w, bias, gamma, beta)
-    key = tuple((t.data_ptr(), t._version) if t is not None else None for t in parts)
-    hit = getattr(w, "_vrd_dw_block", None)
-    capturing = _capturing()
-    if hit is not None and hit[0] == key and not capturing:
-        return hit[1]
+    key = tuple(_version_key(t) if t is not None else None for t in parts)
     Cout, g, k = w.shape
     one = lambda t, fill: _const_row(Cout, fill, w.device) if t is None else t.detach().float().reshape(-1)  # noqa: E731
-    val = torch.cat([w.detach().float().permute(1, 2, 0).reshape(-1), one(bias, 0.0), one(gamma, 1.0), one(beta, 0.0)]).contiguous()
-    if capturing:
-        return _keep_for_capture(val)
-    w._vrd_dw_block = (key, val)
-    return val
+    return _derived(w, "_vrd_dw_block", key, lambda: torch.cat(
+        [w.detach().float().permute(1, 2, 0).reshape(-1), one(bias, 0.0), one(gamma, 1.0), one(beta, 0.0)]).contiguous())
 
 
 def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=None):
@@ -1013,7 +1051,7 @@ def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=
         a.relu[i] = 1 if s.get("relu") else 0
         a.y[i], a.ldy[i] = po, ldo
         a.out_pair[i] = _fmt(s.get("pair"))
-        outs.append(Pair(o, Cout) if _fmt(s.get("pair")) else o)
+        outs.append(_as_pair(o, Cout, a.out_pair[i]))
     _hip.check(lib.vrd_dwconv_ln(C.byref(a), _stream()), "vrd_dwconv_ln")
     return outs
 
@@ -1055,10 +1093,10 @@ def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, ou
         table = _hip.RowSegs.of(segs)
         _hip.check(lib.vrd_local_attn_segs(pq, pk, pv, ld, _mask_ptr(mask, rows), rel, C.byref(table), Cc, n_head, half_win,
                                            out.data_ptr(), Cc, _fmt(pair), _stream()), "vrd_local_attn_segs")
-        return Pair(out, Cc) if _fmt(pair) else out
+        return _as_pair(out, Cc, _fmt(pair))
     _hip.check(lib.vrd_local_attn(pq, pk, pv, ld, _mask_ptr(mask, rows), rel, B, T, Cc, n_head, half_win,
                                   out.data_ptr(), Cc, _fmt(pair), _stream()), "vrd_local_attn")
-    return Pair(out, Cc) if _fmt(pair) else out
+    return _as_pair(out, Cc, _fmt(pair))
 
 
 def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=None, segs=None):
@@ -1075,68 +1113,60 @@ def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=Non
     if not isinstance(q, Pair) and recording(q, k, v):
         from . import autograd
         return autograd.Attention.apply(q, k, v, kv_mask, n_head)
+    fmt, (B, Tq, Cc), (_, Tk, _), pq, ldq, pk, pv, ldk, rows_k, out = _qkv_rows(q, k, v, out)
+    if fmt:
+        out_fmt = fmt if pair else 0
+        _hip.check(lib.vrd_attention_pair(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), _mask_ptr(q_mask, B * Tq), B, Tq, Tk, n_head,
+                                          Cc // n_head, out.data_ptr(), Cc, out_fmt, fmt, _stream(),
+                                          products() if fmt == _hip.PAIR_F16 else 0),
+                   "vrd_attention_pair")
+        return _as_pair(out, Cc, out_fmt)
+    hd = Cc // n_head
+    flash = algo == 2 or (algo == 0 and hd in (64, 128))      # mirrors vrd_attention's auto choice
+    out_fmt = _fmt(pair and flash)
+    _hip.check(lib.vrd_attention(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), B, Tq, Tk, n_head, hd,
+                                 out.data_ptr(), Cc, algo, out_fmt, _stream()), "vrd_attention")
+    return _as_pair(out, Cc, out_fmt)
+
+
+def _qkv_rows(q, k, v, out):
+    """The operands of a global attention call, all three Pairs of one format and full width or all three f32 rows:
+    (fmt -- 0 for f32 rows --, q's shape, k's shape, q's address and leading dimension, k's and v's addresses and their common
+    leading dimension, k's row count, out: the contiguous rows of q's shape to write, fresh unless given)."""
+    fmt = 0
     if isinstance(q, Pair):
         assert isinstance(k, Pair) and isinstance(v, Pair) and q.width == k.width == v.width == q.shape[-1]
         assert q.fmt == k.fmt == v.fmt
         fmt = q.fmt
         q, k, v = q.t, k.t, v.t
-        B, Tq, Cc = q.shape
-        Tk = k.shape[1]
-        pq, _, _, ldq = _rows(q)
-        pk, rows_k, _, ldk = _rows(k)
-        pv, _, _, ldv = _rows(v)
-        assert ldk == ldv
-        if out is None:
-            out = torch.empty(B, Tq, Cc, device=q.device, dtype=torch.float32)
-        assert out.shape == (B, Tq, Cc) and out.is_contiguous()
-        _hip.check(lib.vrd_attention_pair(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), _mask_ptr(q_mask, B * Tq), B, Tq, Tk, n_head,
-                                          Cc // n_head, out.data_ptr(), Cc, fmt if pair else 0, fmt, _stream(),
-                                          products() if fmt == _hip.PAIR_F16 else 0),
-                   "vrd_attention_pair")
-        return Pair(out, Cc, fmt) if pair else out
-    B, Tq, Cc = q.shape
-    Tk = k.shape[1]
     pq, _, _, ldq = _rows(q)
     pk, rows_k, _, ldk = _rows(k)
     pv, _, _, ldv = _rows(v)
     assert ldk == ldv
     if out is None:
-        out = torch.empty(B, Tq, Cc, device=q.device, dtype=torch.float32)
-    assert out.shape == (B, Tq, Cc) and out.is_contiguous()
-    hd = Cc // n_head
-    flash = algo == 2 or (algo == 0 and hd in (64, 128))      # mirrors vrd_attention's auto choice
-    pair = bool(pair and flash and pair_fmt())
-    _hip.check(lib.vrd_attention(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), B, Tq, Tk, n_head, hd,
-                                 out.data_ptr(), Cc, algo, _fmt(pair), _stream()), "vrd_attention")
-    return Pair(out, Cc) if pair else out
+        out = torch.empty(q.shape, device=q.device, dtype=torch.float32)
+    assert out.shape == q.shape and out.is_contiguous()
+    return fmt, q.shape, k.shape, pq, ldq, pk, pv, ldk, rows_k, out
 
 
 def _attention_segs(q, k, v, kv_mask, n_head, pair, q_mask, out, qsegs, ksegs):
     if not (isinstance(q, Pair) and isinstance(k, Pair) and isinstance(v, Pair)):
         raise TypeError("attention(segs=...): the row groups of one call exist for pair-row operands only (the split-precision "
                         "flash kernel); f32 rows go group by group")
-    assert q.width == k.width == v.width == q.shape[-1] and q.fmt == k.fmt == v.fmt
-    fmt = q.fmt
-    q, k, v = q.t, k.t, v.t
+    fmt, (B, Rq, Cc), k_shape, pq, ldq, pk, pv, ldk, rows_k, out = _qkv_rows(q, k, v, out)
     qsegs, ksegs = list(qsegs), list(ksegs)
     assert len(qsegs) == len(ksegs) >= 1 and all(a[1] == b[1] for a, b in zip(qsegs, ksegs))
-    (B, Rq, Cc), Rk = q.shape, k.shape[1]
-    assert B == 1 and k.shape[0] == 1 and v.shape == k.shape
+    Rk = k_shape[1]
+    assert B == 1 and k_shape[0] == 1 and v.shape == k_shape
     assert all(0 <= off and off + n * T <= Rq for off, n, T in qsegs) and all(0 <= off and off + n * T <= Rk for off, n, T in ksegs)
-    pq, _, _, ldq = _rows(q)
-    pk, rows_k, _, ldk = _rows(k)
-    pv, _, _, ldv = _rows(v)
-    assert ldk == ldv
-    if out is None:
-        out = torch.empty(1, Rq, Cc, device=q.device, dtype=torch.float32)
-    assert out.shape == (1, Rq, Cc) and out.is_contiguous()
+    out_fmt = fmt if pair else 0
     for g0 in range(0, len(qsegs), _hip.MAX_SEGS):              # a call takes MAX_SEGS groups: consecutive runs of them
         tq, tk = _hip.RowSegs.of(qsegs[g0:g0 + _hip.MAX_SEGS]), _hip.RowSegs.of(ksegs[g0:g0 + _hip.MAX_SEGS])
         _hip.check(lib.vrd_attention_pair_segs(pq, ldq, pk, pv, ldk, _mask_ptr(kv_mask, rows_k), _mask_ptr(q_mask, Rq), C.byref(tq),
-                                               C.byref(tk), n_head, Cc // n_head, out.data_ptr(), Cc, fmt if pair else 0, fmt,
+                                               C.byref(tk), n_head, Cc // n_head, out.data_ptr(), Cc, out_fmt, fmt,
                                                _stream(), products() if fmt == _hip.PAIR_F16 else 0),
                    "vrd_attention_pair_segs")
-    return Pair(out, Cc, fmt) if pair else out
+    return _as_pair(out, Cc, out_fmt)
 
 
 def maxpool_mask(x, mask_in, out=None):
