@@ -88,7 +88,7 @@ const char* vrd_last_error(void);
  * documented safe bound (4094 decodes exactly).  Every kernel that WRITES pair rows in this format, or splits f32 rows into
  * such planes while staging, therefore reports: it ORs a tag naming its family into one 32-bit flag word per device --
  *    1  boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs, vrd_gather_train
- *    2  vrd_layernorm, vrd_conv_ln
+ *    2  vrd_layernorm, vrd_conv_ln, vrd_dwconv_ln_multi (its pair-row output sets only)
  *    4  vrd_dwconv_ln (its pair-row output sets only; f32 output sets of the same call do not count)
  *    8  pair-row outputs of vrd_gemm / vrd_gemm_batch (every kernel and epilogue of the family)
  *   16  f32 rows split while staged: A of vrd_gemm / vrd_gemm_batch (the value times a_scale[0] where a_scale is given),
@@ -407,6 +407,34 @@ typedef struct {
                                    row[i] / stride, its x_up rows at row[i] / 2 */
 } vrd_dwconv_ln_args;
 int vrd_dwconv_ln(const vrd_dwconv_ln_args* a, void* stream);
+
+/* ---- the same for up to five weight sets over ONE stream of rows, read once -------------
+ * C = 512, ksize = 3, stride 1, group_in = 1, no x_up.  Set o reads the rows as they are (pre_ln[o] == 0) or behind the input
+ * LayerNorm (pre_ln[o] != 0; pre_gamma / pre_beta are then required): the subject / object layers of the backbone feed a
+ * stream to its own self-attention (q, k from LN1(x), v from x) and to the other layer's cross-attention (k, v from x), five
+ * depthwise-conv + LayerNorm branches that a vrd_dwconv_ln call per group of branches reads three times.  Every output row has
+ * the bits the vrd_dwconv_ln call with that set's parameters and input form gives.  A set's parameters come as the on-chip image
+ * only (vrd_dwconv_ln_args.packed: taps [3][C] | bias [C] | gamma [C] | beta [C], 6 * C floats); has_ln[o] says whether the set
+ * ends in its LayerNorm.  Pair-row sets in the f16 format report tag 2 of the range word (above).  Profiled with the
+ * VRD_K_DWCONV_LN family. */
+#define VRD_DWCONV_MULTI_SETS 5
+typedef struct {
+    const float* x;  int64_t ldx;
+    int32_t B, Tin, C;
+    const uint8_t* mask_out;
+    int32_t n_out;                                   /* 1 .. VRD_DWCONV_MULTI_SETS */
+    const float* packed[VRD_DWCONV_MULTI_SETS];
+    int32_t has_ln[VRD_DWCONV_MULTI_SETS];
+    int32_t relu[VRD_DWCONV_MULTI_SETS];
+    int32_t pre_ln[VRD_DWCONV_MULTI_SETS];
+    float* y[VRD_DWCONV_MULTI_SETS];
+    int64_t ldy[VRD_DWCONV_MULTI_SETS];
+    int32_t out_pair[VRD_DWCONV_MULTI_SETS];       /* enum vrd_pair_format per set */
+    const float* pre_gamma;                          /* the input LayerNorm (nullable when no set has pre_ln) */
+    const float* pre_beta;
+    const vrd_row_segs* segs;                        /* nullable (host memory): the rows as groups of sequences; B and Tin are then ignored */
+} vrd_dwconv_ln_multi_args;
+int vrd_dwconv_ln_multi(const vrd_dwconv_ln_multi_args* a, void* stream);
 
 /* ---- banded (local-window) attention, models/blocks.py:950-986 ---------------------------
  * query t attends keys j in [t-half_win, t+half_win] within [0,T); masked keys get -1e4,

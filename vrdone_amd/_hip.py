@@ -88,6 +88,19 @@ class DwconvLnArgs(C.Structure):
                 ("pre_gamma", c_f32p), ("pre_beta", c_f32p), ("packed", c_f32p * 3), ("segs", C.POINTER(RowSegs))]
 
 
+DWCONV_MULTI_SETS = 5                             # VRD_DWCONV_MULTI_SETS
+
+
+class DwconvLnMultiArgs(C.Structure):                 # vrd_dwconv_ln_multi_args
+    _fields_ = [("x", c_f32p), ("ldx", C.c_int64), ("B", C.c_int32), ("Tin", C.c_int32), ("C", C.c_int32),
+                ("mask_out", c_u8p), ("n_out", C.c_int32),
+                ("packed", c_f32p * DWCONV_MULTI_SETS), ("has_ln", C.c_int32 * DWCONV_MULTI_SETS),
+                ("relu", C.c_int32 * DWCONV_MULTI_SETS), ("pre_ln", C.c_int32 * DWCONV_MULTI_SETS),
+                ("y", c_f32p * DWCONV_MULTI_SETS), ("ldy", C.c_int64 * DWCONV_MULTI_SETS),
+                ("out_pair", C.c_int32 * DWCONV_MULTI_SETS),
+                ("pre_gamma", c_f32p), ("pre_beta", c_f32p), ("segs", C.POINTER(RowSegs))]
+
+
 class ConvLnArgs(C.Structure):
     _fields_ = [("x", c_f32p), ("ldx", C.c_int64), ("rows", C.c_int64),
                 ("Cin", C.c_int32), ("taps", C.c_int32), ("T", C.c_int32), ("N", C.c_int32),
@@ -192,6 +205,7 @@ _SIGNATURES = {
     "vrd_layernorm": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int,
                                 c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vrd_dwconv_ln": (C.c_int, [C.POINTER(DwconvLnArgs), C.c_void_p]),
+    "vrd_dwconv_ln_multi": (C.c_int, [C.POINTER(DwconvLnMultiArgs), C.c_void_p]),
     "vrd_local_attn": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_u8p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, c_f32p, C.c_int64, C.c_int, C.c_void_p]),
     "vrd_local_attn_segs": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_u8p, c_f32p, C.POINTER(RowSegs), C.c_int, C.c_int,
@@ -314,7 +328,7 @@ def check(rc, what):
 # tags of the f16 operand-range flag word (vrd_f16_range_flag; enum RangeTag of csrc/vrd_common.h): the entry points that OR each
 # bit.  A value x reports from |x| >= 4095 on (|x * 2^4| >= 65520 rounds to hi = inf); |x| < 4094 is the documented safe bound.
 RANGE_TAGS = {1: "boundary tensors (vrd_bct_to_btc / vrd_pack_pairs / vrd_gather_pairs / vrd_gather_train)",
-              2: "vrd_layernorm / vrd_conv_ln outputs",
+              2: "vrd_layernorm / vrd_conv_ln / vrd_dwconv_ln_multi outputs",
               4: "vrd_dwconv_ln outputs",
               8: "pair-row outputs of vrd_gemm / vrd_gemm_batch",
               16: "f32 rows split while staged (vrd_gemm / vrd_gemm_batch, vrd_attention_rows, vrd_attention_bwd)",

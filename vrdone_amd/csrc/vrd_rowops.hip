@@ -614,6 +614,166 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(vrd_dwconv_ln_args p, in
 }
 
 // ------------------------------------------------------------------------------------------
+// the same for up to five weight sets that read ONE stream, each set the raw rows or the rows behind the input LayerNorm
+// (vrd_dwconv_ln_multi: the subject / object layers' attention inputs -- a stream's own q / k (normalised) and v (raw) and
+// the other layer's cross-attention k / v (raw) -- from one pass over the stream).  512 channels, k = 3, stride 1.
+// ------------------------------------------------------------------------------------------
+// dwconv_ln_kernel<2, 3, 1> with a second window: a row is kept raw and, when a set asks for it, normalised (ln_rows, once, as
+// the row enters the window); a set's arithmetic on its window is that kernel's, expression for expression, so a row's bits do
+// not depend on the launch that wrote it.  Five parameter blocks and the input LayerNorm are 64 KiB of LDS: the workgroup is
+// EIGHT waves that share one image, two workgroups per CU -- the sixteen waves per CU the three-set kernel runs at with its four
+// 40-KiB workgroups of four waves (amdgpu_waves_per_eu keeps the registers within that: 128 per wave).
+constexpr int DWM_SETS = VRD_DWCONV_MULTI_SETS, DWM_WAVES = 8;
+
+struct DwmRow {
+    float4 v[2];
+};
+
+// output row `row` of set o from the window win[k] = input row to + k - 1
+__device__ __forceinline__ void dwm_set_row(const vrd_dwconv_ln_multi_args& p, int o, const float* ls, const DwmRow (&win)[3], float mk,
+                                            int64_t row, int lane, vrd::RangeTrack* rt) {
+    constexpr int NV = 2, KS = 3, C = 512, NT = 3;
+    float4 acc[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane_chan<NV, true>(i, lane);
+        float4 r = *reinterpret_cast<const float4*>(ls + NT * C + c);          // bias
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+            const float4 w = *reinterpret_cast<const float4*>(ls + k * C + c);
+            const float4 v = win[k].v[i];
+            r.x += w.x * v.x; r.y += w.y * v.y; r.z += w.z * v.z; r.w += w.w * v.w;
+        }
+        acc[i] = make_float4(r.x * mk, r.y * mk, r.z * mk, r.w * mk);
+    }
+    if (p.has_ln[o]) {
+        ln_rows<NV, true>(acc, ls + (NT + 1) * C, ls + (NT + 2) * C, lane, p.relu[o] != 0);
+    } else if (p.relu[o]) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            acc[i].x = fmaxf(acc[i].x, 0.f); acc[i].y = fmaxf(acc[i].y, 0.f);
+            acc[i].z = fmaxf(acc[i].z, 0.f); acc[i].w = fmaxf(acc[i].w, 0.f);
+        }
+    }
+    if (p.out_pair[o]) {
+        vrd::store_pair8(p.y[o] + row * p.ldy[o], lane * 8, acc[0], acc[NV - 1], p.out_pair[o], rt);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) st4(p.y[o] + row * p.ldy[o] + lane_chan<NV, true>(i, lane), acc[i]);
+    }
+}
+
+__global__ __launch_bounds__(64 * DWM_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void dwconv_ln_multi_kernel(vrd_dwconv_ln_multi_args p, int strips_per_seq, int rw, unsigned* rflag, vrd::SegTable sg) {
+    vrd::RangeTrack rt;
+    constexpr int NV = 2, C = 512, NT = 3, SETF = (NT + 3) * C;
+    extern __shared__ __attribute__((aligned(16))) float dw_lds[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // ---- parameters -> LDS: the callers' images of the blocks (taps tap-major | bias | gamma | beta), straight copies
+    for (int o = 0; o < p.n_out; ++o)
+        for (int idx = threadIdx.x * 4; idx < SETF; idx += 256 * DWM_WAVES) st4(dw_lds + o * SETF + idx, ld4(p.packed[o] + idx));
+    const float* const pre = dw_lds + p.n_out * SETF;
+    bool any_pre = false;
+#pragma unroll
+    for (int o = 0; o < DWM_SETS; ++o) any_pre |= o < p.n_out && p.pre_ln[o] != 0;
+    if (any_pre)
+        for (int c = threadIdx.x; c < C; c += 64 * DWM_WAVES) {
+            dw_lds[p.n_out * SETF + c] = p.pre_gamma[c];
+            dw_lds[p.n_out * SETF + C + c] = p.pre_beta[c];
+        }
+    __syncthreads();
+    // XCD-aware renumbering: a contiguous range of strips per XCD (dwconv_ln_kernel)
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, qq = nwg >> 3, rem = nwg & 7;
+    const int lid = (xcd < rem ? xcd * (qq + 1) : rem * (qq + 1) + (xcd - rem) * qq) + (bid >> 3);
+    const int64_t ws = (int64_t)lid * DWM_WAVES + wave;
+    // the strip's sequence: its frame count and its first row (stride 1: input and output rows are the same rows)
+    int T, to0;
+    int64_t row0;
+    if (sg.count) {
+        int g, b, strip;
+        if (!vrd::seg_find(sg, ws, g, b, strip)) return;
+        T = sg.T[g], to0 = strip * rw;
+        row0 = sg.row[g] + (int64_t)b * T;
+    } else {
+        const int b = (int)(ws / strips_per_seq);
+        if (b >= p.B) return;
+        T = p.Tin, to0 = (int)(ws - (int64_t)b * strips_per_seq) * rw;
+        row0 = (int64_t)b * T;
+    }
+    const int to1 = min(to0 + rw, T);
+
+    // ---- a strip of padded frames only: every row of a set is LayerNorm(0) = beta (0 without LayerNorm), ReLU applied
+    if (p.mask_out) {
+        const int64_t r0 = row0 + to0;
+        const bool mine = lane < to1 - to0 && p.mask_out[r0 + lane] != 0;
+        if (!__any(mine)) {
+#pragma unroll
+            for (int o = 0; o < DWM_SETS; ++o) {
+                if (o >= p.n_out) break;
+                const float* const lb = dw_lds + o * SETF + (NT + 2) * C;
+                float4 val[NV];
+#pragma unroll
+                for (int i = 0; i < NV; ++i) {
+                    val[i] = *reinterpret_cast<const float4*>(lb + lane_chan<NV, true>(i, lane));
+                    if (p.relu[o]) {
+                        val[i].x = fmaxf(val[i].x, 0.f); val[i].y = fmaxf(val[i].y, 0.f);
+                        val[i].z = fmaxf(val[i].z, 0.f); val[i].w = fmaxf(val[i].w, 0.f);
+                    }
+                }
+                for (int to = to0; to < to1; ++to) {
+                    const int64_t row = row0 + to;
+                    if (p.out_pair[o]) {
+                        vrd::store_pair8(p.y[o] + row * p.ldy[o], lane * 8, val[0], val[NV - 1], p.out_pair[o], &rt);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < NV; ++i) st4(p.y[o] + row * p.ldy[o] + lane_chan<NV, true>(i, lane), val[i]);
+                    }
+                }
+            }
+            rt.report(rflag, vrd::RANGE_LAYERNORM);
+            return;
+        }
+    }
+    auto load_row = [&](int ti) {           // frames outside [0, T) are the convolution's zero padding, in both forms
+        DwmRow r;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            r.v[i] = ti >= 0 && ti < T ? ld4(p.x + (row0 + ti) * p.ldx + lane_chan<NV, true>(i, lane)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        return r;
+    };
+    auto normed = [&](const DwmRow& r, int ti) {
+        DwmRow n = r;
+        if (any_pre && ti >= 0 && ti < T) ln_rows<NV, true>(n.v, pre, pre + C, lane, false);
+        return n;
+    };
+    DwmRow raw[3], nrm[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) raw[k] = load_row(to0 + k - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) nrm[k] = normed(raw[k], to0 + k - 1);
+    for (int to = to0; to < to1; ++to) {
+        // request the row the next output adds to the window before working on this one
+        const bool more = to + 1 < to1;
+        DwmRow nxt;
+        if (more) nxt = load_row(to + 2);
+        const int64_t row = row0 + to;
+        const float mk = p.mask_out ? (float)p.mask_out[row] : 1.f;
+#pragma unroll
+        for (int o = 0; o < DWM_SETS; ++o) {
+            if (o >= p.n_out) break;
+            if (p.pre_ln[o]) dwm_set_row(p, o, dw_lds + o * SETF, nrm, mk, row, lane, &rt);
+            else dwm_set_row(p, o, dw_lds + o * SETF, raw, mk, row, lane, &rt);
+        }
+        if (more) {
+            raw[0] = raw[1], raw[1] = raw[2], raw[2] = nxt;
+            nrm[0] = nrm[1], nrm[1] = nrm[2], nrm[2] = normed(nxt, to + 2);
+        }
+    }
+    rt.report(rflag, vrd::RANGE_LAYERNORM);
+}
+
+// ------------------------------------------------------------------------------------------
 // MaxPool1d(kernel 3, stride 2, padding 1 with -inf) * downsampled mask
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void maxpool_mask_kernel(const float* __restrict__ x, int64_t ldx, int B, int Tin, int C,
@@ -953,6 +1113,46 @@ int vrd_dwconv_ln(const vrd_dwconv_ln_args* a, void* stream) {
     else if (a->ksize == 3) VRD_DW(2, 3, 1);
     else VRD_DW(2, 1, 1);
 #undef VRD_DW
+    VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+int vrd_dwconv_ln_multi(const vrd_dwconv_ln_multi_args* a, void* stream) {
+    VRD_CHECK_ARG(a && a->x, "vrd_dwconv_ln_multi: null args");
+    VRD_CHECK_ARG(a->C == 512, "vrd_dwconv_ln_multi: C must be 512 (got %d)", a->C);
+    VRD_CHECK_ARG(a->n_out >= 1 && a->n_out <= DWM_SETS, "vrd_dwconv_ln_multi: n_out must be 1..%d (got %d)", DWM_SETS, a->n_out);
+    VRD_CHECK_ARG(a->segs || (a->B > 0 && a->Tin > 0), "vrd_dwconv_ln_multi: bad B / Tin");
+    VRD_CHECK_ARG(a->ldx >= a->C && a->ldx % 4 == 0 && aligned16(a->x), "vrd_dwconv_ln_multi: bad x layout");
+    bool any_pre = false, any_f16 = false;
+    for (int o = 0; o < a->n_out; ++o) {
+        VRD_CHECK_ARG(a->packed[o] && a->y[o] && aligned16(a->packed[o]) && aligned16(a->y[o]) && a->ldy[o] % 4 == 0 && a->ldy[o] >= a->C,
+                      "vrd_dwconv_ln_multi: bad output set %d", o);
+        VRD_CHECK_ARG(a->out_pair[o] == VRD_PAIR_NONE || a->out_pair[o] == VRD_PAIR_BF16 || a->out_pair[o] == VRD_PAIR_F16,
+                      "vrd_dwconv_ln_multi: bad pair format of set %d", o);
+        any_pre |= a->pre_ln[o] != 0;
+        any_f16 |= a->out_pair[o] == VRD_PAIR_F16;
+    }
+    VRD_CHECK_ARG(!any_pre || (a->pre_gamma && a->pre_beta && aligned16(a->pre_gamma) && aligned16(a->pre_beta)),
+                  "vrd_dwconv_ln_multi: a set reads normalised rows but the input LayerNorm's gamma / beta are missing or misaligned");
+    const int rw = DW_RW;
+    vrd::SegTable sg;
+    sg.count = 0;
+    int64_t rows = (int64_t)a->B * a->Tin, total_strips = (int64_t)a->B * ((a->Tin + rw - 1) / rw);
+    if (a->segs) {
+        total_strips = vrd::seg_table(sg, a->segs, 1, rw);
+        VRD_CHECK_ARG(total_strips >= 0, "vrd_dwconv_ln_multi: bad row groups (1..%d groups)", VRD_MAX_SEGS);
+        rows = 0;
+        for (int g = 0; g < sg.count; ++g) rows += (int64_t)sg.n[g] * sg.T[g];
+    }
+    const int64_t wgs = (total_strips + DWM_WAVES - 1) / DWM_WAVES;
+    VRD_CHECK_ARG(wgs < ((int64_t)1 << 31), "vrd_dwconv_ln_multi: grid too large");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    vrd::ProfScope prof(VRD_K_DWCONV_LN, s, 0.0, 4.0 * (double)rows * a->C * (1 + a->n_out));
+    const size_t lds = ((size_t)a->n_out * 6 + 2) * a->C * sizeof(float);
+    if (lds > 48 * 1024)
+        if (int rc = vrd::reserve_lds(reinterpret_cast<const void*>(dwconv_ln_multi_kernel), lds, "vrd_dwconv_ln_multi")) return rc;
+    hipLaunchKernelGGL(dwconv_ln_multi_kernel, dim3((unsigned)wgs), dim3(64 * DWM_WAVES), lds, s, *a, (a->Tin + rw - 1) / rw, rw,
+                       any_f16 ? vrd::range_flag() : nullptr, sg);
     VRD_LAUNCH_CHECK();
     return 0;
 }

@@ -12,7 +12,37 @@ from torch import nn
 
 from . import ragged
 from .blocks import ConvMLP, LayerNorm, Layout, MaskedConv1D, TransformerBlock, _from_cl, _mask2d, _ops, get_sinusoid_encoding
-from .local_transformer import MaskedConvTransformerDecoderLayer
+from .local_transformer import MaskedConvTransformerDecoderLayer, MaskedMHCA_QKV
+
+# The subject / object layers of pair_stage read each original stream three times per stage (see _sos_stream).  From
+# SOS_MERGE_MIN_ROWS rows per stream on (VRDONE_SOS_MERGE_MIN_ROWS), inference reads it once: SOS_MERGE_FORM "c" = one
+# vrd_dwconv_ln_multi launch of five sets, "b" = two (the stream's own q / k / v, then the other layer's k / v).  Same bits as
+# the three vrd_dwconv_ln launches; below the threshold, and under autograd, nothing changes.  Module values: tests and A/B
+# runs flip them in one process.
+SOS_MERGE_MIN_ROWS = int(__import__("os").environ.get("VRDONE_SOS_MERGE_MIN_ROWS", str(1 << 15)))
+SOS_MERGE_FORM = __import__("os").environ.get("VRDONE_SOS_MERGE_FORM", "c")
+
+
+def _sos_merge(s_attn, o_attn, rows):
+    if torch.is_grad_enabled() or rows < SOS_MERGE_MIN_ROWS:
+        return False
+    mods = [m for layer in (s_attn, o_attn) for m in (layer.self_attn, layer.multihead_attn)]
+    return all(isinstance(m, MaskedMHCA_QKV) and m.n_embd == 512 and
+               all(getattr(m, f"{n}_conv").conv.kernel_size == (3,) for n in ("query", "key", "value")) for m in mods)
+
+
+def _sos_stream(lay, x, mask, own, other):
+    """The depthwise-conv + LayerNorm branches that read the stream x: its own layer's self-attention q / k (behind ln1) and v
+    (raw), and the other layer's cross-attention k / v (raw) -> (self_ready of `own`, cross_ready of `other`) for the layers' cl"""
+    sa, ca = own.self_attn, other.multihead_attn
+    sets = [dict(sa._branch_set("query"), normed=True), dict(sa._branch_set("key"), normed=True), sa._branch_set("value"),
+            ca._branch_set("key"), ca._branch_set("value")]
+    pre_ln = (own.ln1.weight, own.ln1.bias)
+    if SOS_MERGE_FORM == "b":
+        res = ragged.dwconv_ln_multi(lay, x, sets[:3], mask, pre_ln=pre_ln) + ragged.dwconv_ln_multi(lay, x, sets[3:], mask)
+    else:
+        res = ragged.dwconv_ln_multi(lay, x, sets, mask, pre_ln=pre_ln)
+    return dict(zip(("query", "key", "value"), res[:3])), dict(zip(("key", "value"), res[3:]))
 
 
 class MaskConvTransformerBackbone(nn.Module):
@@ -202,8 +232,14 @@ class MaskConvTransformerBackbone(nn.Module):
             s, o = lay.halves(so)
             nxt = lay2.new(D, mask)
             out_s, out_o = lay.halves(nxt)
-            s2, _ = s_attn.cl(s, o, mask, mask, stream_add=s, out=out_s, qlay=lay, klay=lay)      # s + s_attn(s, o)
-            o2, _ = o_attn.cl(o, s, mask, mask, stream_add=o, out=out_o, qlay=lay, klay=lay)      # uses the pre-update s
+            kw_s, kw_o = {}, {}
+            if _sos_merge(s_attn, o_attn, lay.rows):
+                # each original stream is read ONCE for its three readers (its own self-attention q / k and v, the other
+                # layer's cross-attention k / v) instead of once per reader
+                kw_s["self_ready"], kw_o["cross_ready"] = _sos_stream(lay, s, mask, s_attn, o_attn)
+                kw_o["self_ready"], kw_s["cross_ready"] = _sos_stream(lay, o, mask, o_attn, s_attn)
+            s2, _ = s_attn.cl(s, o, mask, mask, stream_add=s, out=out_s, qlay=lay, klay=lay, **kw_s)      # s + s_attn(s, o)
+            o2, _ = o_attn.cl(o, s, mask, mask, stream_add=o, out=out_o, qlay=lay, klay=lay, **kw_o)      # uses the pre-update s
             so = ops.join(nxt, (s2, o2), dim=lay.axis)
 
         s, o = lay.halves(so)

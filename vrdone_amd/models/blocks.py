@@ -249,11 +249,15 @@ class _ConvAttention(nn.Module):
                 groups.append((x, m, use_ln, ks, [name]))
         return groups
 
-    def _prep(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv"):
+    def _prep(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", ready=None):
         """dwconv * mask -> LN for the three branches (one launch per group of _groups).
-        pre_ln (gamma, beta): inputs named in pre_ln_on ('q', 'k', 'v') are LayerNorm'ed as they are read."""
-        outs = {}
+        pre_ln (gamma, beta): inputs named in pre_ln_on ('q', 'k', 'v') are LayerNorm'ed as they are read.
+        ready: {branch name: its output}, branches the caller already computed (backbones.pair_stage's merged pass)."""
+        outs = dict(ready or {})
         for x, m, use_ln, _, names in self._groups(q_in, k_in, v_in, q_mask, kv_mask, pre_ln, pre_ln_on):
+            names = [n for n in names if n not in outs]
+            if not names:
+                continue
             res = ragged.dwconv_ln(qlay if x is q_in else klay, x, [self._branch_set(n) for n in names], m, stride=stride,
                                    pre_ln=pre_ln if use_ln else None)
             outs.update(zip(names, res))
@@ -268,11 +272,13 @@ class _ConvAttention(nn.Module):
             ((k, self.key.weight, self.key.bias), dict(out_pair=out_pair, skip_rows=kv_mask)),
             ((v, self.value.weight, self.value.bias), dict(out_pair=out_pair, skip_rows=kv_mask))]))
 
-    def _attend(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", **epilogue):
+    def _attend(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", ready=None, **epilogue):
         """The module's forward: the queries q_in in the layout qlay attend to the keys / values k_in / v_in in klay; q_mask /
-        kv_mask are the masks behind the depthwise convs' stride; epilogue kwargs go to the output-projection GEMM."""
+        kv_mask are the masks behind the depthwise convs' stride; epilogue kwargs go to the output-projection GEMM.
+        ready: branch outputs of the depthwise-conv stage that the caller computed (see _prep)."""
         ops = _ops()
-        q, k, v = self._prep(q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=stride, pre_ln=pre_ln, pre_ln_on=pre_ln_on)
+        q, k, v = self._prep(q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=stride, pre_ln=pre_ln, pre_ln_on=pre_ln_on,
+                             ready=ready)
         qlay, klay = qlay.strided(stride), klay.strided(stride)
         # global attention on the split-precision flash kernel consumes q/k/v as pair rows (one choice for all buckets)
         qkv_pair = self._half_win is None and ops.flash_pair_ok(self.n_head, self.n_embd, qlay.min_frames())

@@ -118,11 +118,14 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         """Per-row stochastic-depth factors for a branch shaped like tgt (B, Tq, C), or None."""
         return dp.row_factors(tgt.shape[0], tgt.shape[1], tgt.device) if isinstance(dp, AffineDropPath) else None
 
-    def cl(self, tgt, memory, tgt_mask, memory_mask, query_pos=None, stream_add=None, out=None, qlay=None, klay=None):
+    def cl(self, tgt, memory, tgt_mask, memory_mask, query_pos=None, stream_add=None, out=None, qlay=None, klay=None,
+           self_ready=None, cross_ready=None):
         """tgt (B, Tq, C), memory (B, Tk, C); masks (B, T) or None (= all valid).  query_pos: (Tq, C)
         rows added to the normalised target.  stream_add: extra tensor added to the cross-attention
         output (the SOS update s + s_mutual of reference backbones.py:220-221), fused into the GEMM.
-        qlay / klay: the layouts of the rows of tgt and of memory (default: the batch form)."""
+        qlay / klay: the layouts of the rows of tgt and of memory (default: the batch form).
+        self_ready / cross_ready: {branch: rows} of the self- / cross-attention's depthwise-conv branches that the caller
+        computed from tgt / memory (backbones.pair_stage reads each stream once for all its readers); fused form only."""
         ops = _ops()
         qlay, klay = Layout.of(qlay, tgt), Layout.of(klay, memory)
         self_lays, cross_lays = dict(qlay=qlay, klay=qlay), dict(qlay=qlay, klay=klay)
@@ -131,9 +134,10 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         fuse1 = query_pos is None and isinstance(self.self_attn, MaskedMHCA_QKV)
         fuse2 = query_pos is None and isinstance(self.multihead_attn, MaskedMHCA_QKV)
         last = not self.with_ffn
+        assert (self_ready is None or fuse1) and (cross_ready is None or fuse2)
         if fuse1:
             tgt, _ = self.self_attn.cl_qkv(tgt, tgt, tgt, tgt_mask, tgt_mask, pre_ln=(self.ln1.weight, self.ln1.bias),
-                                           pre_ln_on="qk", scale=self._scale(self.drop_path_attn1),
+                                           pre_ln_on="qk", scale=self._scale(self.drop_path_attn1), ready=self_ready,
                                            row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True, **self_lays)
         else:
             t2 = self.ln1.cl(tgt, post_add=query_pos)
@@ -143,7 +147,7 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
                   res_masked=True, res2=stream_add if last else None, out=out if last else None, **cross_lays)
         if fuse2:
             tgt, _ = self.multihead_attn.cl_qkv(tgt, memory, memory, tgt_mask, memory_mask,
-                                                pre_ln=(self.ln2.weight, self.ln2.bias), pre_ln_on="q", **kw)
+                                                pre_ln=(self.ln2.weight, self.ln2.bias), pre_ln_on="q", ready=cross_ready, **kw)
         else:
             t2 = self.ln2.cl(tgt, post_add=query_pos)
             tgt, _ = self.multihead_attn.cl_qkv(t2, memory, memory, tgt_mask, memory_mask, **kw)

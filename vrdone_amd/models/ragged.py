@@ -202,6 +202,24 @@ def dwconv_ln(lay, x, sets, mask_out, *, stride=1, x_up=None, pre_ln=None):
     return [ops.Pair(b, Cout) if ops._fmt(st.get("pair")) else b for st, b in zip(sets, bufs)]
 
 
+def dwconv_ln_multi(lay, x, sets, mask_out, *, pre_ln=None):
+    """ops.dwconv_ln_multi over the buckets of x's layout `lay` (stride 1): up to five sets from one pass over the rows of x"""
+    ops = _ops()
+    segs = _merged(lay.segs)
+    if len(segs) == 1:
+        res = ops.dwconv_ln_multi(lay.part(x, segs[0]), sets, mask_out=lay.part(mask_out, segs[0]), pre_ln=pre_ln)
+        return [lay.whole(r) for r in res]
+    Cout = sets[0]["weight"].shape[0]
+    bufs = [torch.empty(1, lay.rows, Cout, device=x.device, dtype=torch.float32) for _ in sets]
+    for g0 in range(0, len(segs), _MAX_SEGS):
+        part = segs[g0:g0 + _MAX_SEGS]
+        r0, r1 = part[0][0], part[-1][0] + part[-1][1] * part[-1][2]
+        ops.dwconv_ln_multi(x[:, r0:r1], [dict(st, out=b[:, r0:r1]) for st, b in zip(sets, bufs)],
+                            mask_out=None if mask_out is None else mask_out[:, r0:r1], pre_ln=pre_ln,
+                            segs=[(off - r0, n, T) for off, n, T in part])
+    return [ops.Pair(b, Cout) if ops._fmt(st.get("pair")) else b for st, b in zip(sets, bufs)]
+
+
 def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False):
     """Global (half_win None) or banded attention of the queries in `qlay` over the keys in `klay`: bucket by bucket, or the
     buckets as the row groups of one kernel call (banded attention; global attention on pair rows with ATTN_SEGS).

@@ -1056,6 +1056,41 @@ def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=
     return outs
 
 
+def dwconv_ln_multi(x, sets, *, mask_out=None, pre_ln=None, segs=None):
+    """dwconv_ln for up to five 512-channel k = 3 sets over one stream, read once (vrd_dwconv_ln_multi; inference only).  A set
+    with normed=True reads the rows behind the input LayerNorm pre_ln = (gamma, beta), the others read them as they are; the other
+    keys of a set and `segs` are dwconv_ln's.  Every output has the bits of the dwconv_ln launch with that set and input form."""
+    assert not recording(x, *(t for st in sets for t in (st["weight"], st.get("bias"), st.get("gamma"), st.get("beta"))),
+                         *(pre_ln or ())), "the multi-set pass has no backward: training takes dwconv_ln"
+    B, Tin, Cx = x.shape
+    px, rows, cols, ldx = _rows(x)
+    a = _hip.DwconvLnMultiArgs()
+    if segs is not None:
+        assert B == 1 and sum(n * T for _, n, T in segs) == Tin
+        a.segs = C.pointer(_hip.RowSegs.of(segs))
+    a.x, a.ldx, a.B, a.Tin, a.C = px, ldx, B, Tin, cols
+    a.mask_out = _mask_ptr(mask_out, B * Tin)
+    a.n_out = len(sets)
+    if any(s.get("normed") for s in sets):
+        a.pre_gamma, a.pre_beta = _param_ptr(pre_ln[0], x, "LayerNorm weight"), _param_ptr(pre_ln[1], x, "LayerNorm bias")
+    outs, blocks = [], []
+    for i, s in enumerate(sets[:_hip.DWCONV_MULTI_SETS]):
+        assert tuple(s["weight"].shape) == (cols, 1, 3) and (s.get("gamma") is None) == (s.get("beta") is None)
+        o = s.get("out")
+        if o is None:
+            o = torch.empty(B, Tin, cols, device=x.device, dtype=torch.float32)
+        po, ro, co, ldo = _rows(o)
+        assert ro == B * Tin and co == cols
+        _param_ptr(s["weight"], x, "depthwise weight")          # (the checks only: the kernel reads the set's image)
+        blocks.append(_dwconv_block(s["weight"], s.get("bias"), s.get("gamma"), s.get("beta")))      # (held until the launch is queued)
+        a.packed[i] = blocks[-1].data_ptr()
+        a.has_ln[i], a.relu[i], a.pre_ln[i] = int(s.get("gamma") is not None), int(bool(s.get("relu"))), int(bool(s.get("normed")))
+        a.y[i], a.ldy[i], a.out_pair[i] = po, ldo, _fmt(s.get("pair"))
+        outs.append(_as_pair(o, cols, a.out_pair[i]))
+    _hip.check(lib.vrd_dwconv_ln_multi(C.byref(a), _stream()), "vrd_dwconv_ln_multi")
+    return outs
+
+
 def _rel_pe_ptr(rel_pe, like, n_head, half_win):
     if rel_pe is None:
         return None
