@@ -585,6 +585,67 @@ typedef struct {
 } vrd_match_args;
 int vrd_match_relations(const vrd_match_args* a, void* stream);
 
+/* ---- eval proposals, vrdone_amd/proposals.py prepare_test_videos (the reference dataloader's `_test_getitem`,
+ * dataloaders/vidvrd.py:552-636 and the pair loop behind it): box clamp, vIoU de-dup of the tracklets and the pair tables of
+ * every video of a call, in four launches over one set of flat tables.  Added without a version change, like the scoring entries.
+ *
+ * Video v owns tracklets trk_first[v] .. trk_first[v + 1] - 1 of the tracklet table, whose row k is [first row in `boxes`, first
+ * frame, frames, category, video]; the bytes tri_first[v] .. tri_first[v + 1] - 1 of `shadow`, one per unordered tracklet pair
+ * i < j of the video in row-major order of the upper triangle (n (n - 1) / 2 of them for n tracklets); and the candidates
+ * cand_first[v] .. cand_first[v + 1] - 1, each a (subject, object) pair of tracklet numbers counted inside the video.
+ * video_max[v] = (w - 1, h - 1) of the video's frame, the clamp bounds as the host rounds them to f32.  Offsets are clamped to
+ * the tables and a tracklet whose rows leave `boxes` is not read, so a broken table reads and writes nothing outside the
+ * buffers; it shows as video_err 2.  The library allocates nothing: `shadow` is the caller's scratch.
+ *
+ *   clamp   one wave per tracklet: x0, y0 = max(., 0), x1 = min(., w - 1), y1 = min(., h - 1) in place (a NaN stays one, as with
+ *           torch.clamp); trk_err[k] = 1 when a row ends with x1 <= x0 or y1 <= y0 or a NaN, 2 for a tracklet outside the buffers.
+ *   shadow  one wave per tracklet pair, over the clamped boxes.  Different categories or no shared frame: 0.  Else, over the
+ *           shared frames, inter = sum of max(min(x1) - max(x0) + 1, 0) * max(min(y1) - max(y0) + 1, 0) and area_i, area_j =
+ *           sums of (x1 - x0 + 1) * (y1 - y0 + 1): the per-frame terms in f32 with every operation rounded (no fused multiply-
+ *           add), accumulated in f64, lanes striding over frames and finished in a fixed order -- a repeat is bit-equal.
+ *           shadow[pair] bit 0: inter / area_j > threshold and i's duration contains j's ("i shadows j"); bit 1: the mirrored
+ *           condition ("j shadows i").
+ *   walk    one wave per video: the reference's greedy double loop over those bytes.  Rows i in order, also a dropped i; a
+ *           dropped j is skipped; at the first live j with bit 1 and not bit 0, i is dropped and its row ends; every live j in
+ *           front of that one (or in the whole row) with bit 0 is dropped.  dropped[k] = 0 / 1; video_err[v] = 1 when one of
+ *           the video's trk_err is set, 2 for broken offsets, else 0.
+ *   pairs   one workgroup per video: candidate (s, o) is kept when neither tracklet is dropped, shared = min(ends) - max(starts)
+ *           >= min_frames and steps = len(range(stride_offset[v], shared, feat_stride)) >= 2.  The kept ones, in their order,
+ *           are written to the front of the video's slice of s_row / o_row (first row of the pair's subject / object frames,
+ *           counted from the video's own first row), lens (steps), kept_s / kept_o; the rest of the slice is cleared (0, -1 for
+ *           the ids); count[v] = how many were kept.
+ * The four entries take the same struct and must run in this order on one stream. */
+typedef struct {
+    float* boxes;                   /* (rows, 4) x0, y0, x1, y1; 16-byte aligned; clamped in place */
+    int64_t rows;
+    const int64_t* trk;             /* (n_trk, 5) */
+    const float* video_max;         /* (n_videos, 2) */
+    const int32_t* trk_first;       /* (n_videos + 1) */
+    const int64_t* tri_first;       /* (n_videos + 1) */
+    const int64_t* cand_first;      /* (n_videos + 1) */
+    const int32_t* cand_s;          /* (n_cand) */
+    const int32_t* cand_o;          /* (n_cand) */
+    const int32_t* stride_offset;   /* (n_videos) */
+    int32_t n_videos, n_trk;
+    int64_t n_tri, n_cand;
+    int32_t feat_stride, min_frames;
+    double threshold;
+    uint8_t* trk_err;               /* (n_trk) */
+    uint8_t* shadow;                /* (n_tri) scratch */
+    uint8_t* dropped;               /* (n_trk) */
+    int64_t* s_row;                 /* (n_cand) */
+    int64_t* o_row;                 /* (n_cand) */
+    int32_t* lens;                  /* (n_cand) */
+    int32_t* kept_s;                /* (n_cand) */
+    int32_t* kept_o;                /* (n_cand) */
+    int32_t* count;                 /* (n_videos) */
+    int32_t* video_err;             /* (n_videos) */
+} vrd_proposal_args;
+int vrd_proposal_clamp(const vrd_proposal_args* a, void* stream);
+int vrd_proposal_shadow(const vrd_proposal_args* a, void* stream);
+int vrd_proposal_walk(const vrd_proposal_args* a, void* stream);
+int vrd_proposal_pairs(const vrd_proposal_args* a, void* stream);
+
 /* ====================================================================================================================
  * Backward kernels (training step: the reference differentiates its ATen graph with autograd, train.py:186;
  * models/maskvrd.py:168-198).  All f32 rows (no pair rows).  Parameter gradients are ACCUMULATED (+=) into buffers the

@@ -171,6 +171,15 @@ class MatchArgs(C.Structure):                         # vrd_match_args
                 ("threshold", C.c_double), ("detected", c_u8p), ("hit", c_i32p)]
 
 
+class ProposalArgs(C.Structure):                      # vrd_proposal_args
+    _fields_ = [("boxes", c_f32p), ("rows", C.c_int64), ("trk", C.c_void_p), ("video_max", c_f32p), ("trk_first", c_i32p),
+                ("tri_first", C.c_void_p), ("cand_first", C.c_void_p), ("cand_s", c_i32p), ("cand_o", c_i32p),
+                ("stride_offset", c_i32p), ("n_videos", C.c_int32), ("n_trk", C.c_int32), ("n_tri", C.c_int64),
+                ("n_cand", C.c_int64), ("feat_stride", C.c_int32), ("min_frames", C.c_int32), ("threshold", C.c_double),
+                ("trk_err", c_u8p), ("shadow", c_u8p), ("dropped", c_u8p), ("s_row", C.c_void_p), ("o_row", C.c_void_p),
+                ("lens", c_i32p), ("kept_s", c_i32p), ("kept_o", c_i32p), ("count", c_i32p), ("video_err", c_i32p)]
+
+
 class AssembleArgs(C.Structure):
     _fields_ = [("streams", c_f32p), ("snippets", c_f32p), ("stream_row", C.c_void_p), ("lens", C.c_void_p),
                 ("P", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("L", C.c_int32), ("piece", C.c_int32), ("reach", C.c_int32),
@@ -227,6 +236,11 @@ _SIGNATURES = {
     # ---- relation scoring (csrc/vrd_score.hip; vrdone_amd/evaluate.py DeviceRelationScorer)
     "vrd_relation_viou": (C.c_int, [C.POINTER(ViouArgs), C.c_void_p]),
     "vrd_match_relations": (C.c_int, [C.POINTER(MatchArgs), C.c_void_p]),
+    # ---- eval proposals (csrc/vrd_proposals.hip; vrdone_amd/proposals.py prepare_test_videos)
+    "vrd_proposal_clamp": (C.c_int, [C.POINTER(ProposalArgs), C.c_void_p]),
+    "vrd_proposal_shadow": (C.c_int, [C.POINTER(ProposalArgs), C.c_void_p]),
+    "vrd_proposal_walk": (C.c_int, [C.POINTER(ProposalArgs), C.c_void_p]),
+    "vrd_proposal_pairs": (C.c_int, [C.POINTER(ProposalArgs), C.c_void_p]),
     # ---- backward kernels (training step)
     "vrd_gemm_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                  c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),

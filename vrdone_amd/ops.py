@@ -1350,3 +1350,58 @@ def match_relations(pred_first, cand_first, cand, ov, n_gt, threshold):
     a.threshold, a.detected, a.hit = float(threshold), detected.data_ptr(), hit.data_ptr()
     _hip.check(lib.vrd_match_relations(C.byref(a), _stream()), "vrd_match_relations")
     return hit
+
+
+# ---- eval proposals (csrc/vrd_proposals.hip): what vrdone_amd.proposals.prepare_test_videos launches
+_PROPOSAL_TABLES = (   # field of vrd_proposal_args -> (dtype, elements as a function of the counts)
+    ("boxes", torch.float32, lambda n: 4 * n["rows"]), ("trk", torch.int64, lambda n: 5 * n["trk"]),
+    ("video_max", torch.float32, lambda n: 2 * n["videos"]), ("trk_first", torch.int32, lambda n: n["videos"] + 1),
+    ("tri_first", torch.int64, lambda n: n["videos"] + 1), ("cand_first", torch.int64, lambda n: n["videos"] + 1),
+    ("cand_s", torch.int32, lambda n: n["cand"]), ("cand_o", torch.int32, lambda n: n["cand"]),
+    ("stride_offset", torch.int32, lambda n: n["videos"]), ("trk_err", torch.uint8, lambda n: n["trk"]),
+    ("shadow", torch.uint8, lambda n: n["tri"]), ("dropped", torch.uint8, lambda n: n["trk"]),
+    ("s_row", torch.int64, lambda n: n["cand"]), ("o_row", torch.int64, lambda n: n["cand"]),
+    ("lens", torch.int32, lambda n: n["cand"]), ("kept_s", torch.int32, lambda n: n["cand"]),
+    ("kept_o", torch.int32, lambda n: n["cand"]), ("count", torch.int32, lambda n: n["videos"]),
+    ("video_err", torch.int32, lambda n: n["videos"]))
+
+
+def proposal_args(tables, feat_stride, min_frames, threshold):
+    """vrd_proposal_args over `tables`: {field: contiguous device tensor} for every pointer of the struct (include/vrdone_hip.h).
+    The counts come from the tensors -- videos from trk_first, tracklets from trk (n, 5), tracklet pairs from shadow, candidates
+    from cand_s, box rows from boxes (rows, 4) -- and every other table must hold exactly what they ask for."""
+    n = {"videos": tables["trk_first"].numel() - 1, "trk": tables["trk"].shape[0], "tri": tables["shadow"].numel(),
+         "cand": tables["cand_s"].numel(), "rows": tables["boxes"].shape[0]}
+    dev = tables["boxes"].device
+    a = _hip.ProposalArgs()
+    for name, dtype, size in _PROPOSAL_TABLES:
+        t = tables[name]
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError("vrdone_amd ops need HIP tensors (no CPU path exists for the hot path)")
+        if t.dtype != dtype or not t.is_contiguous() or t.numel() != size(n):
+            raise ValueError(f"proposal_args: {name} must be a contiguous {dtype} tensor of {size(n)} elements, "
+                             f"got {t.dtype} {tuple(t.shape)}")
+        setattr(a, name, t.data_ptr())
+    a.rows, a.n_videos, a.n_trk, a.n_tri, a.n_cand = n["rows"], n["videos"], n["trk"], n["tri"], n["cand"]
+    a.feat_stride, a.min_frames, a.threshold = int(feat_stride), int(min_frames), float(threshold)
+    return a
+
+
+def proposal_clamp(a):
+    """Clamp every tracklet's boxes to its video's frame, in place; trk_err says where a box came out empty (vrd_proposal_clamp)."""
+    _hip.check(lib.vrd_proposal_clamp(C.byref(a), _stream()), "vrd_proposal_clamp")
+
+
+def proposal_shadow(a):
+    """One byte per same-video tracklet pair i < j: bit 0 "i shadows j", bit 1 "j shadows i" (vrd_proposal_shadow)."""
+    _hip.check(lib.vrd_proposal_shadow(C.byref(a), _stream()), "vrd_proposal_shadow")
+
+
+def proposal_walk(a):
+    """The reference's greedy de-dup walk over the shadow bytes: dropped (n_trk,), video_err (n_videos,) (vrd_proposal_walk)."""
+    _hip.check(lib.vrd_proposal_walk(C.byref(a), _stream()), "vrd_proposal_walk")
+
+
+def proposal_pairs(a):
+    """The pair tables of every video: kept candidates compacted to the front of each video's slice (vrd_proposal_pairs)."""
+    _hip.check(lib.vrd_proposal_pairs(C.byref(a), _stream()), "vrd_proposal_pairs")

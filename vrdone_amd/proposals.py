@@ -12,6 +12,8 @@ device (`vrd_gather_pairs`), straight into the backbone's operand buffers.  The 
 proposal with `pair_source` in place of `so_features_list`; everything else (`sids`, `oids`, `cat_ids`, `cat_scores`,
 `traj_durations`, `bboxes_list`, `so_offset`) is what `_test_getitem` returns.
 """
+import threading
+
 import numpy as np
 import torch
 
@@ -20,17 +22,19 @@ class PairSource:
     """Per-tracklet rows on the device + per-pair tables: pair p = `lens[p]` frames, frame t = row s_row[p] + t*stride of
     the subject's tracklet and o_row[p] + t*stride of the object's in the concatenated (sum L, .) arrays."""
 
-    def __init__(self, vis, clip, boxes, s_row, o_row, lens, stride, wh, first_row=None):
+    def __init__(self, vis, clip, boxes, s_row, o_row, lens, stride, wh, first_row=None, host_tables=None):
         self.vis, self.clip, self.boxes = vis, clip, boxes
         self.s_row, self.o_row, self.lens_dev = s_row, o_row, lens
-        self.lens = lens.tolist()
+        # host_tables: (s_row, o_row, lens) as numpy arrays, from a caller that has them on the host already
+        # (prepare_test_videos): spares the copy back, a synchronisation per source
+        self.lens = lens.tolist() if host_tables is None else host_tables[2].tolist()
         self.stride, self.wh = int(stride), (float(wh[0]), float(wh[1]))
         self.n_visual = vis.shape[1]
         self.n_clip = 0 if clip is None else clip.shape[1]
         # first_row (n_tracklets + 1,): tracklet k owns rows [first_row[k], first_row[k + 1]) -- what lets the model run its
         # per-entity stage once per tracklet (stream_plan); None: pairs only
         self.first_row = None if first_row is None else np.asarray(first_row, dtype=np.int64)
-        self._rows_host = None
+        self._rows_host = None if host_tables is None else (host_tables[0], host_tables[1])
         # frame sizes of a source that holds several videos (concat): video j owns the tracklet rows [video_row[j],
         # video_row[j + 1]) and its pairs' boxes are normalised by video_wh[j]; pair_wh (P, 2) on the device.  None: one video
         self.video_row = self.video_wh = self.pair_wh = None
@@ -241,6 +245,242 @@ def prepare_test_proposal(raw, feat_stride, stride_offset, proposal_min_frames, 
     else:
         out["pair_source"] = src
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The same preparation for many videos in one call, on the device (csrc/vrd_proposals.hip): `pack_test_videos` lays the
+# raw dicts out as flat tables, `prepare_test_videos` uploads them with the tracklet rows in ONE copy, runs the clamp, the
+# de-dup and the pair tables in four launches and reads the counts, the kept ids and the error flags back in ONE copy.
+# --------------------------------------------------------------------------------------------------------------------
+class ProposalTables:
+    """pack_test_videos' result.  `tables`: the host side of vrd_proposal_args' input tables (include/vrdone_hip.h), numpy --
+    trk (n_trk, 5) int64 [first row, first frame, frames, category, video], video_max (n_videos, 2) float32 [w - 1, h - 1],
+    trk_first (n_videos + 1,) int32, tri_first / cand_first (n_videos + 1,) int64, cand_s / cand_o (n_cand,) int32 (tracklet
+    numbers inside the video), stride_offset (n_videos,) int32.  video_row (n_videos + 1,): video v owns the rows
+    [video_row[v], video_row[v + 1]) of the concatenated box / feature arrays.  widths: (visual, CLIP or None).  An empty raw
+    ({}) keeps its place as a video without tracklets, so a video's index is its position in the call."""
+
+    def __init__(self, tables, video_row, widths, video_wh):
+        self.tables, self.video_row, self.widths, self.video_wh = tables, video_row, widths, video_wh
+        self.n_videos = len(video_wh)
+
+
+def pack_test_videos(raws, stride_offsets=0):
+    """The flat tables over all videos of `raws` (each what load_test_video returns, or {}); stride_offsets: an int, or one per
+    video.  Host only, touches no feature row.  ValueError on videos of different feature widths, on a candidate id outside its
+    video's tracklets, on tracklets whose boxes / features do not have one row per frame, on a negative offset."""
+    raws = list(raws)
+    nv = len(raws)
+    if isinstance(stride_offsets, (int, np.integer)):
+        offsets = [int(stride_offsets)] * nv
+    else:
+        offsets = [int(x) for x in stride_offsets]
+        if len(offsets) != nv:
+            raise ValueError(f"pack_test_videos: {len(offsets)} stride offsets for {nv} videos")
+    if any(x < 0 for x in offsets):
+        raise ValueError("pack_test_videos: a stride offset is negative")
+    trk, cand_s, cand_o, widths = [], [], [], set()
+    video_max, video_wh = np.zeros((nv, 2), dtype=np.float32), [None] * nv
+    trk_first, tri_first, cand_first, video_row = (np.zeros(nv + 1, dtype=np.int64) for _ in range(4))
+    for v, raw in enumerate(raws):
+        n = 0
+        if raw:
+            spans = np.asarray(raw["traj_durations"], dtype=np.int64).reshape(-1, 2)
+            n = len(spans)
+            frames = spans[:, 1] - spans[:, 0]
+            boxes, vis, clip = raw["bboxes_list"], raw["visual_features_list"], raw.get("clip_features_list")
+            cats = np.asarray(raw["cat_ids"], dtype=np.int64).reshape(-1)
+            if not (len(boxes) == len(vis) == len(cats) == n and (clip is None or len(clip) == n)) or n == 0:
+                raise ValueError(f"pack_test_videos: video {v}: the per-tracklet lists have different lengths (or are empty)")
+            for k in range(n):
+                rows = (int(frames[k]),)
+                if tuple(boxes[k].shape) != rows + (4,) or boxes[k].dtype != torch.float32 or tuple(vis[k].shape[:1]) != rows or \
+                        vis[k].dim() != 2 or (clip is not None and (clip[k].dim() != 2 or tuple(clip[k].shape[:1]) != rows)) or rows[0] < 0:
+                    raise ValueError(f"pack_test_videos: video {v}: tracklet {k} needs one float32 box row and one feature row per "
+                                     f"frame of its duration")
+            widths.update((vis[k].shape[1], None if clip is None else clip[k].shape[1]) for k in range(n))
+            s, o = (np.asarray(raw[key], dtype=np.int64).reshape(-1) for key in ("sids", "oids"))
+            if len(s) != len(o):
+                raise ValueError(f"pack_test_videos: video {v}: {len(s)} subject ids, {len(o)} object ids")
+            if len(s) and (min(s.min(), o.min()) < 0 or max(s.max(), o.max()) >= n):
+                raise ValueError(f"pack_test_videos: video {v}: a candidate pair names a tracklet outside the video's {n}")
+            first = video_row[v] + np.concatenate([[0], np.cumsum(frames)])
+            trk.append(np.stack([first[:-1], spans[:, 0], frames, cats, np.full(n, v, dtype=np.int64)], axis=1))
+            cand_s.append(s)
+            cand_o.append(o)
+            w, h = raw["video_wh"]
+            video_wh[v] = (w, h)
+            video_max[v] = (w - 1, h - 1)                      # rounded to f32 as torch.clamp_ rounds its scalar bound
+            video_row[v + 1] = first[-1]
+        else:
+            video_row[v + 1] = video_row[v]
+        trk_first[v + 1] = trk_first[v] + n
+        tri_first[v + 1] = tri_first[v] + n * (n - 1) // 2
+        cand_first[v + 1] = cand_first[v] + (len(cand_s[-1]) if raw else 0)
+    if len(widths) > 1:
+        raise ValueError(f"pack_test_videos: the videos have different feature widths (visual, CLIP): {sorted(widths, key=str)}")
+    if trk_first[-1] >= 2 ** 31:
+        raise ValueError("pack_test_videos: more than 2^31 - 1 tracklets in one call")
+    cat = lambda parts, dtype, shape: (np.concatenate(parts) if parts else np.zeros(shape, dtype=np.int64)).astype(dtype)     # noqa: E731
+    tables = {"trk": cat(trk, np.int64, (0, 5)), "video_max": video_max, "trk_first": trk_first.astype(np.int32),
+              "tri_first": tri_first, "cand_first": cand_first, "cand_s": cat(cand_s, np.int32, (0,)),
+              "cand_o": cat(cand_o, np.int32, (0,)), "stride_offset": np.asarray(offsets, dtype=np.int32).reshape(nv)}
+    return ProposalTables(tables, video_row, widths.pop() if widths else (0, None), video_wh)
+
+
+def _carve(parts, align=16):
+    """Byte offsets of `parts` [(name, numpy dtype, shape)] laid one after the other, each on an `align`-byte line: ({name:
+    (first byte, bytes, dtype, shape)}, total bytes)."""
+    at, out = 0, {}
+    for name, dtype, shape in parts:
+        nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+        out[name] = (at, nbytes, np.dtype(dtype), tuple(shape))
+        at += -(-nbytes // align) * align
+    return out, at
+
+
+_TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32,
+             np.dtype(np.uint8): torch.uint8}
+
+
+def _carved(buf, layout, name):
+    at, nbytes, dtype, shape = layout[name]
+    return buf[at:at + nbytes].view(_TORCH_OF[dtype]).view(shape)
+
+
+# The page-locked host buffer an upload is assembled in: kept between calls and grown on demand.  A fresh pageable buffer of a
+# call's size (100 MB for 16 small videos at visual width 1024) costs its page faults at every call and travels through the
+# driver's own staging copy; this one goes to the device in one DMA.  A call ends with a synchronisation behind that copy, so
+# the next call may overwrite the buffer; the lock keeps two threads from sharing it.
+_staging, _staging_lock = [None], threading.Lock()
+
+
+def _staging_buffer(nbytes):
+    if _staging[0] is None or _staging[0].numel() < nbytes:
+        _staging[0] = None                                       # (release the old one first)
+        _staging[0] = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=True)
+    return _staging[0][:nbytes]
+
+
+class ProposalRun:
+    """run_proposal_kernels' result: `packed` (ProposalTables), `dev` {name: device tensor} -- the uploaded rows (boxes clamped in
+    place, vis, clip), the uploaded tables and every table the kernels wrote (trk_err, shadow, dropped, s_row, o_row, lens,
+    kept_s, kept_o, count, video_err) --, `host` {name: numpy} the copy of s_row .. video_err read back, `boxes_cpu` per video
+    the list of clamped CPU boxes (None for an empty raw)."""
+
+    def __init__(self, packed, dev, host, boxes_cpu):
+        self.packed, self.dev, self.host, self.boxes_cpu = packed, dev, host, boxes_cpu
+
+
+def run_proposal_kernels(raws, feat_stride, stride_offsets, proposal_min_frames, device, viou_threshold=0.9):
+    """The device half of prepare_test_videos (same arguments, same errors): pack, upload once, launch the four kernels, read
+    back once.  Returns a ProposalRun, or None when the call holds no tracklet."""
+    from . import ops
+    if device is None or torch.device(device).type != "cuda":
+        raise ValueError("prepare_test_videos runs on the device: for device=None (the flat CPU form) or a CPU device call "
+                         "prepare_test_proposal per video")
+    if int(feat_stride) < 1:
+        raise ValueError(f"prepare_test_videos: feat_stride {feat_stride} < 1")
+    raws = list(raws)
+    t = pack_test_videos(raws, stride_offsets)
+    tab, nv = t.tables, t.n_videos
+    n_trk, n_cand, n_tri, R = tab["trk"].shape[0], len(tab["cand_s"]), int(tab["tri_first"][-1]), int(t.video_row[-1])
+    if n_trk == 0:
+        return None
+    V, Cc = t.widths
+    # ---- one host buffer, one upload: the rows first (boxes on 16-byte lines for the kernels' float4 accesses), then the tables
+    rows = [("boxes", np.float32, (R, 4)), ("vis", np.float32, (R, V))] + ([] if Cc is None else [("clip", np.float32, (R, Cc))])
+    layout, nbytes = _carve(rows + [(k, a.dtype, a.shape) for k, a in tab.items()])
+    with _staging_lock:
+        host = _staging_buffer(nbytes)
+        full = [raw for raw in raws if raw]
+        for name, key in (("boxes", "bboxes_list"), ("vis", "visual_features_list"), ("clip", "clip_features_list"))[:len(rows)]:
+            parts = [x for raw in full for x in raw[key]]
+            dst = _carved(host, layout, name)
+            if all(x.dtype == torch.float32 for x in parts):
+                torch.cat(parts, dim=0, out=dst)
+            else:
+                dst.copy_(torch.cat(parts, dim=0))
+        for k, a in tab.items():
+            _carved(host, layout, k).copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        host_boxes = _carved(host, layout, "boxes")
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            buf.copy_(host, non_blocking=True)                         # the call's one upload
+            out_layout, out_bytes = _carve([("s_row", np.int64, (n_cand,)), ("o_row", np.int64, (n_cand,)), ("lens", np.int32, (n_cand,)),
+                                            ("kept_s", np.int32, (n_cand,)), ("kept_o", np.int32, (n_cand,)), ("count", np.int32, (nv,)),
+                                            ("video_err", np.int32, (nv,))])
+            tmp_layout, tmp_bytes = _carve([("shadow", np.uint8, (n_tri,)), ("dropped", np.uint8, (n_trk,)), ("trk_err", np.uint8, (n_trk,))])
+            out, tmp = torch.empty(out_bytes, dtype=torch.uint8, device=dev), torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+            d = {k: _carved(buf, layout, k) for k in layout}
+            d.update({k: _carved(out, out_layout, k) for k in out_layout})
+            d.update({k: _carved(tmp, tmp_layout, k) for k in tmp_layout})
+            args = ops.proposal_args(d, feat_stride, proposal_min_frames, viou_threshold)
+            ops.proposal_clamp(args)
+            ops.proposal_shadow(args)
+            ops.proposal_walk(args)
+            ops.proposal_pairs(args)
+            # (the host's share while the device works: the clamped CPU boxes of `bboxes_list`, same bounds, same comparisons)
+            boxes_cpu = [None] * nv
+            for v, raw in enumerate(raws):
+                if raw:
+                    b = host_boxes[t.video_row[v]:t.video_row[v + 1]].clone()
+                    b[:, 0:2].clamp_(min=0)
+                    b[:, 2].clamp_(max=float(tab["video_max"][v, 0]))
+                    b[:, 3].clamp_(max=float(tab["video_max"][v, 1]))
+                    boxes_cpu[v] = list(torch.split(b, tab["trk"][tab["trk_first"][v]:tab["trk_first"][v + 1], 2].tolist()))
+            res = out.cpu()                                            # the call's one synchronisation
+    h = {k: _carved(res, out_layout, k).numpy() for k in out_layout}
+    bad = np.nonzero(h["video_err"])[0]
+    if len(bad):
+        v = int(bad[0])
+        if h["video_err"][v] == 1:
+            raise ValueError(f"prepare_test_videos: video {v}: a tracklet box is empty after clamping to the frame")
+        raise RuntimeError(f"prepare_test_videos: video {v}: the kernels refused its tables")
+    return ProposalRun(t, d, h, boxes_cpu)
+
+
+def prepare_test_videos(raws, feat_stride, stride_offsets, proposal_min_frames, device, viou_threshold=0.9):
+    """prepare_test_proposal for many videos in one call, on the device: raws is a list of the dicts `load_test_video` returns
+    (or {}), stride_offsets an int or one int per video.  Returns a list with one entry per video: the dict
+    prepare_test_proposal(raw, ..., device) returns -- {} where it returns {}, and for a raw that is {} -- with a `pair_source`
+    whose vis / clip / boxes are views of the one uploaded array and whose s_row / o_row / first_row count from the video's own
+    first row, so forward_test, forward_test_videos, PairSource.concat and DeviceRelationScorer take them as they are.
+
+    One host-to-device copy (the tracklet rows of all videos and the flat tables of pack_test_videos), four launches (box clamp;
+    the shadow bits of every same-video tracklet pair; the reference's greedy de-dup walk; the pair tables, compacted per video)
+    and one device-to-host copy (the pair tables, the per-video counts and the error flags), whatever the number of videos,
+    tracklets or pairs.  `bboxes_list` holds the boxes clamped on the host, bit-equal to the device's copy.  The upload is
+    assembled in a page-locked host buffer that the module keeps between calls (as large as the largest call so far).
+
+    ValueError: videos of different feature widths, a candidate id outside its video's tracklets (before anything is uploaded);
+    a box that is empty after clamping (found by the clamp kernel, read with the results; the message names the video).
+    `device` must be a HIP device: the flat CPU form of prepare_test_proposal (device=None, for DataLoader workers) stays
+    host-only -- build it with prepare_test_proposal."""
+    raws = list(raws)
+    run = run_proposal_kernels(raws, feat_stride, stride_offsets, proposal_min_frames, device, viou_threshold)
+    if run is None:
+        return [{} for _ in raws]
+    t, d, h, boxes_cpu = run.packed, run.dev, run.host, run.boxes_cpu
+    tab, Cc = t.tables, t.widths[1]
+    results = []
+    for v, raw in enumerate(raws):
+        k = int(h["count"][v])
+        if not raw or k == 0:
+            results.append({})
+            continue
+        c0, c1 = int(tab["cand_first"][v]), int(tab["cand_first"][v]) + k
+        r0, r1 = int(t.video_row[v]), int(t.video_row[v + 1])
+        first_row = tab["trk"][tab["trk_first"][v]:tab["trk_first"][v + 1], 0] - r0
+        src = PairSource(d["vis"][r0:r1], None if Cc is None else d["clip"][r0:r1], d["boxes"][r0:r1], d["s_row"][c0:c1],
+                         d["o_row"][c0:c1], d["lens"][c0:c1], feat_stride, t.video_wh[v],
+                         first_row=np.concatenate([first_row, [r1 - r0]]), host_tables=tuple(h[n][c0:c1].copy() for n in ("s_row", "o_row", "lens")))
+        results.append({"sids": torch.from_numpy(h["kept_s"][c0:c1].astype(np.int64)), "oids": torch.from_numpy(h["kept_o"][c0:c1].astype(np.int64)),
+                        "cat_ids": raw["cat_ids"], "cat_scores": raw["cat_scores"], "traj_durations": raw["traj_durations"],
+                        "bboxes_list": boxes_cpu[v], "so_offset": torch.full((k,), int(tab["stride_offset"][v]), dtype=torch.int64),
+                        "pair_source": src})
+    return results
 
 
 # --------------------------------------------------------------------------------------------------------------------

@@ -76,12 +76,17 @@ def synth_video(n_tracklets, c_in, min_len, max_len, seed=7, device="cpu"):
             "traj_durations": torch.tensor(span, device=device), "so_offset": torch.zeros(len(sids), dtype=torch.long, device=device)}
 
 
-def synth_raw_video(n_tracklets, n_visual, min_len, max_len, seed=7, n_clip=0, wh=(1280, 720)):
+def synth_raw_video(n_tracklets, n_visual, min_len, max_len, seed=7, n_clip=0, wh=(1280, 720), n_categories=None, n_shadowed=0):
     """One synthetic video in the form the reference's `_prepare_test` hands to `_test_getitem`
     (dataloaders/vidvrd.py:459-550) and vrdone_amd.proposals.prepare_test_proposal takes: per-TRACKLET visual (and CLIP)
     features and boxes on the host, durations [start, end), distinct categories, every ordered pair of tracklets that
-    share a frame."""
+    share a frame.
+    n_categories: the categories are drawn from 1 .. n_categories instead (several tracklets per category: the vIoU de-dup
+    has pairs to compare).  n_shadowed: that many more tracklets behind the n_tracklets, each a same-category near-copy of
+    one of those -- a sub-span of its duration, its boxes moved by a pixel or two -- which the de-dup drops.  Both draw from
+    a generator of their own: with the defaults the video is what it was without them, bit for bit."""
     g = torch.Generator().manual_seed(seed)
+    g_extra = torch.Generator().manual_seed(seed + 7919)
     video_len = max_len + 8
     spans, boxes, vis, clip = [], [], [], []
     for _ in range(n_tracklets):
@@ -93,14 +98,34 @@ def synth_raw_video(n_tracklets, n_visual, min_len, max_len, seed=7, n_clip=0, w
         vis.append(torch.randn(n, n_visual, generator=g))
         if n_clip:
             clip.append(torch.randn(n, n_clip, generator=g))
+    cat_ids = torch.arange(1, n_tracklets + 1)
+    if n_categories is not None:
+        cat_ids = torch.randint(1, n_categories + 1, (n_tracklets,), generator=g_extra)
+    copied = []
+    for _ in range(n_shadowed):
+        src = int(torch.randint(0, n_tracklets, (1,), generator=g_extra))
+        n = spans[src][1] - spans[src][0]
+        cut = torch.randint(0, n // 4 + 1, (2,), generator=g_extra).tolist() if n >= 4 else [0, 0]
+        a, e = cut[0], n - cut[1]
+        spans.append((spans[src][0] + a, spans[src][0] + e))
+        boxes.append(boxes[src][a:e] + (torch.rand(e - a, 4, generator=g_extra) * 3.0 - 1.5))
+        vis.append(torch.randn(e - a, n_visual, generator=g_extra))
+        if n_clip:
+            clip.append(torch.randn(e - a, n_clip, generator=g_extra))
+        copied.append(src)
+    cat_scores = torch.rand(n_tracklets, generator=g)
+    if copied:
+        cat_ids = torch.cat([cat_ids, cat_ids[copied]])
+        cat_scores = torch.cat([cat_scores, torch.rand(n_shadowed, generator=g_extra)])
+    n_all = n_tracklets + n_shadowed
     sids, oids = [], []
-    for s in range(n_tracklets):
-        for o in range(n_tracklets):
+    for s in range(n_all):
+        for o in range(n_all):
             if s != o and min(spans[s][1], spans[o][1]) > max(spans[s][0], spans[o][0]):
                 sids.append(s)
                 oids.append(o)
-    out = {"sids": torch.tensor(sids), "oids": torch.tensor(oids), "cat_ids": torch.arange(1, n_tracklets + 1),
-           "cat_scores": torch.rand(n_tracklets, generator=g), "bboxes_list": boxes,
+    out = {"sids": torch.tensor(sids), "oids": torch.tensor(oids), "cat_ids": cat_ids,
+           "cat_scores": cat_scores, "bboxes_list": boxes,
            "traj_durations": torch.tensor(spans, dtype=torch.int64), "visual_features_list": vis, "video_wh": wh}
     if n_clip:
         out["clip_features_list"] = clip
