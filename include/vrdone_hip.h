@@ -762,6 +762,38 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
                        float* dq, float* dk, float* dv,
                        int64_t ldd, float* scratch, void* stream);
 
+/* ---- training dropout (models/blocks.py:975-979,988,1057,1059: attn_drop, proj_drop and the two MLP dropouts of a
+ * TransformerBlock).  No mask is stored between forward and backward: a keep decision is a pure function of
+ *   seed  one 64-bit word in DEVICE memory (read by the kernels: the launch that wrote it precedes them on the stream),
+ *   site  a 32-bit word naming the dropout module (zlib crc32 of its name in the reference's module tree, or any integer),
+ *   id    the element's 64-bit index, which continues through a training step (row0 below),
+ * namely word (id & 3) of Philox4x32-10 with key = seed and counter = (id >> 2 low word, high word, site, 0);
+ * keep iff word >= floor(p * 2^32); kept values are multiplied by 1 / (1 - p) (f32).  0 <= p < 1.  vrdone_amd/dropout.py is the
+ * host mirror.  These entry points read and write f32 rows only and never touch the f16 operand-range flag, like
+ * vrd_local_attn with out_pair = VRD_PAIR_NONE and vrd_local_attn_bwd. */
+
+/* keep[i] = the decision of id first_id + i, i < n (one byte each): the hook that pins the device to the host mirror. */
+int vrd_dropout_mask(const uint64_t* seed, unsigned site, int64_t first_id, int64_t n, float p, uint8_t* keep, void* stream);
+
+/* out[r, c] = x[r, c] * keep(id) / (1 - p) with id = (row0 + r) * C + c, r < rows, c < C (C % 4 == 0; 16-byte aligned rows;
+ * out may be x).  The forward of a row site and, applied to dy, its backward. */
+int vrd_dropout_rows(const float* x, int64_t ldx, int64_t rows, int C, const uint64_t* seed, unsigned site, int64_t row0, float p,
+                     float* out, int64_t ldo, void* stream);
+
+/* vrd_local_attn (f32 rows out) with dropout on the window probabilities behind the masked-query zeroing: out = sum_j f_j P_j v_j,
+ * f_j the factor of id ((row0 + b*T + t) * n_head + head) * (2*half_win+1) + j -- the flat index of the reference's `att`.  Same
+ * envelope as vrd_local_attn; p = 0 IS vrd_local_attn (the same bits).  One wave per query row: a training-only kernel. */
+int vrd_local_attn_drop(const float* q, const float* k, const float* v, int64_t ld, const uint8_t* mask, const float* rel_pe, int B,
+                        int T, int C, int n_head, int half_win, const uint64_t* seed, unsigned site, int64_t row0, float p, float* out,
+                        int64_t ldo, void* stream);
+
+/* Its backward, arguments and scratch as vrd_local_attn_bwd: dP_j = f_j dO . v_j, dS_j = P_j (dP_j - sum_k P_k dP_k); dv sums the
+ * dropped probabilities f_j P_j (the scratch's first half), dq / dk / d rel_pe follow from dS.  p = 0 IS vrd_local_attn_bwd. */
+int vrd_local_attn_drop_bwd(const float* q, const float* k, const float* v, int64_t ld, const float* dO, int64_t lddo,
+                            const uint8_t* mask, const float* rel_pe, int B, int T, int C, int n_head, int half_win,
+                            const uint64_t* seed, unsigned site, int64_t row0, float p, float* dq, float* dk, float* dv, int64_t ldd,
+                            float* scratch, void* stream);
+
 /* Global attention backward, first half (vrd_attention; models/local_transformer.py:44-63,163-183): the probabilities
  * P (B, n_head, Tq, Tk) and the gradient dS w.r.t. the scaled scores.  Then dq = head_dim^-0.5 * dS K, dk = head_dim^-0.5
  * * dS^T Q, dv = P^T dO are three vrd_bmm calls.  Tk <= 1024, head_dim <= 128. */

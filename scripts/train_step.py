@@ -99,8 +99,9 @@ def synthetic_entries(cfg, n_pairs, seed=0, keys_per_video=4):
 
 def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, ema_decay=0.999, verbose=True, drop_path=True,
         graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False, fused_tail=False, torch_fused=False,
-        feed=None, heads=None):
-    """heads: n_head = fuse_head of the config replaced (16 at width 512: head_dim 32 in the SOS layers' global attention).
+        feed=None, heads=None, dropattn=0.0, dropout=0.0):
+    """dropattn / dropout: the config's attention / projection dropout rates (the backbone's TransformerBlocks).
+    heads: n_head = fuse_head of the config replaced (16 at width 512: head_dim 32 in the SOS layers' global attention).
     feed: None (one fixed synthetic batch), "lists" or "source" (per step from synthetic cache entries, see the module text).
     fused_tail: clip + AdamW as vrdone_amd.optim.FusedAdamW.step(max_grad_norm=clip) (three launches) instead of torch's
     clip_grad_norm_ + AdamW.step; torch_fused: torch's own AdamW(fused=True), the second baseline of that comparison.
@@ -112,6 +113,8 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
     cfg = configs.model_config(config)
     if heads:
         cfg = dict(cfg, n_head=heads, fuse_head=heads)
+    if dropattn or dropout:
+        cfg = dict(cfg, dropattn=dropattn, dropout=dropout)
     torch.manual_seed(seed)
     model = synth.load_synthetic_weights(MaskVRD(cfg, device=device)).to(device).train()
     if not drop_path:
@@ -240,8 +243,11 @@ if __name__ == "__main__":
     ap.add_argument("--device-source", action="store_true", help="per step: proposals.train_tables + a device-resident TrainSource (prints data_ms)")
     ap.add_argument("--entry-lists", action="store_true", help="per step: proposals.train_getitem on the same cache entries, lists moved to the device (prints data_ms)")
     ap.add_argument("--heads", type=int, help="n_head and fuse_head of the config (16: head_dim 32 at width 512)")
+    ap.add_argument("--dropattn", type=float, default=0.0, help="the config's `dropattn`: dropout on the banded attention's probabilities")
+    ap.add_argument("--dropout", type=float, default=0.0, help="the config's `dropout`: projection and MLP dropout of the TransformerBlocks")
     args = ap.parse_args()
     assert not (args.device_source and args.entry_lists)
     print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile,
                          deterministic=args.deterministic, fused_tail=args.fused_tail, torch_fused=args.torch_fused,
-                         feed="source" if args.device_source else "lists" if args.entry_lists else None, heads=args.heads)))
+                         feed="source" if args.device_source else "lists" if args.entry_lists else None, heads=args.heads,
+                         dropattn=args.dropattn, dropout=args.dropout)))

@@ -7,8 +7,8 @@ ops.* dispatch here when autograd is recording (torch.is_grad_enabled()) and an 
 mode every activation is a plain f32 channels-last tensor (no pair rows, no writes into concatenation slabs, no padding
 skip), and a fused eval op is run as its differentiable parts, each of which saves what its backward needs:
 
-    conv_gemm(x, W, b, act, row_mask, scale, row_scale, res, res2)
-        = ScaleResidual( Activation( Linear(x, W, b, row_mask) ), scale, row_scale, row_mask, res, res2 )
+    conv_gemm(x, W, b, act, row_mask, scale, row_scale, res, res2, drop)
+        = ScaleResidual( Dropout( Activation( Linear(x, W, b, row_mask) ), drop ), scale, row_scale, row_mask, res, res2 )
     dwconv_ln(x, sets, mask_out, stride, x_up, pre_ln)
         = [ LayerNorm_o( DepthwiseConv_o( LayerNorm_pre(x) (+ up2(x_up)) ) ) ]
 
@@ -289,6 +289,30 @@ class Activation(_Differentiable):
         return activation(x, ctx.act, dy=_dense(dy)), None
 
 
+def dropout_rows(x, drop):
+    """x * keep / (1 - p) over the rows of x, whose first row is number drop.row0 of the site (vrd_dropout_rows)."""
+    px, rows, cols, ldx = _rows(x)
+    out = _new_like_rows(x)
+    po, _, _, ldo = _rows(out)
+    check(lib.vrd_dropout_rows(px, ldx, rows, cols, drop.seed.data_ptr(), drop.site, drop.row0, drop.p, po, ldo, _stream()),
+          "vrd_dropout_rows")
+    return out
+
+
+class Dropout(_Differentiable):
+    """Dropout of a row site (models.blocks.Drop: seed tensor, site, first row's number, rate).  Nothing is saved but the call: the
+    backward computes the same keep decisions again, on dy.  (A masked row stays zero, so the row mask needs no second pass.)"""
+
+    @staticmethod
+    def forward(ctx, x, drop):
+        ctx.drop = drop                        # (holds the seed tensor until the backward has run)
+        return dropout_rows(x, drop)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dropout_rows(_dense(dy), ctx.drop), None
+
+
 class ScaleResidual(_Differentiable):
     """out = v * scale[c] * row_scale[r] * mask[r] + res * (mask if res_masked) + res2."""
 
@@ -409,11 +433,24 @@ class DepthwiseConv(_Differentiable):
 
 class LocalAttention(_Differentiable):
     @staticmethod
-    def forward(ctx, q, k, v, mask, n_head, half_win, rel_pe=None):
+    def forward(ctx, q, k, v, mask, n_head, half_win, rel_pe=None, drop=None):
+        """drop: None, or the attn_drop call (models.blocks.Drop) -- dropout on the window probabilities, forward and backward on
+        the kernels that compute the keep decisions from (seed, site, row, head, slot)."""
         rel = None if rel_pe is None else rel_pe.detach()
-        out = ops.local_attention(q, k, v, mask, n_head, half_win, rel_pe=rel)
+        if drop is None:
+            out = ops.local_attention(q, k, v, mask, n_head, half_win, rel_pe=rel)
+        else:
+            B, T, Cc = q.shape
+            pq, rows, _, ld = _rows(q)
+            pk, _, _, ldk = _rows(k)
+            pv, _, _, ldv = _rows(v)
+            assert ld == ldk == ldv
+            out = torch.empty(B, T, Cc, device=q.device, dtype=torch.float32)
+            check(lib.vrd_local_attn_drop(pq, pk, pv, ld, _mask_ptr(mask, rows), ops._rel_pe_ptr(rel, q, n_head, half_win), B, T, Cc,
+                                          n_head, half_win, drop.seed.data_ptr(), drop.site, drop.row0, drop.p, out.data_ptr(), Cc,
+                                          _stream()), "vrd_local_attn_drop")
         ctx.save_for_backward(q, k, v, rel)
-        ctx.mask, ctx.n_head, ctx.half_win = mask, n_head, half_win
+        ctx.mask, ctx.n_head, ctx.half_win, ctx.drop = mask, n_head, half_win, drop
         return out
 
     @staticmethod
@@ -425,14 +462,21 @@ class LocalAttention(_Differentiable):
         W = 2 * ctx.half_win + 1
         dq, dk, dv = (torch.empty(B, T, Cc, device=q.device, dtype=torch.float32) for _ in range(3))
         scratch = torch.empty(2 * B * T * ctx.n_head * W, device=q.device, dtype=torch.float32)
-        check(lib.vrd_local_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc, _mask_ptr(ctx.mask, B * T),
-                                     ops._rel_pe_ptr(rel, q, ctx.n_head, ctx.half_win), B, T, Cc, ctx.n_head, ctx.half_win,
-                                     dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Cc, scratch.data_ptr(), _stream()),
-              "vrd_local_attn_bwd")
+        d = ctx.drop
+        if d is None:
+            check(lib.vrd_local_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc, _mask_ptr(ctx.mask, B * T),
+                                         ops._rel_pe_ptr(rel, q, ctx.n_head, ctx.half_win), B, T, Cc, ctx.n_head, ctx.half_win,
+                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Cc, scratch.data_ptr(), _stream()),
+                  "vrd_local_attn_bwd")
+        else:
+            check(lib.vrd_local_attn_drop_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc, _mask_ptr(ctx.mask, B * T),
+                                              ops._rel_pe_ptr(rel, q, ctx.n_head, ctx.half_win), B, T, Cc, ctx.n_head, ctx.half_win,
+                                              d.seed.data_ptr(), d.site, d.row0, d.p, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Cc,
+                                              scratch.data_ptr(), _stream()), "vrd_local_attn_drop_bwd")
         d_rel = None
         if rel is not None and ctx.needs_input_grad[6]:      # the bias is added to every row's scores: d rel_pe = sum of dS
             d_rel = scratch[B * T * ctx.n_head * W:].view(B * T, ctx.n_head, W).sum(0).view(rel.shape)
-        return dq, dk, dv, None, None, None, d_rel
+        return dq, dk, dv, None, None, None, d_rel, None
 
 
 def _flash_attention_route(split, head_dim, Tq, Tk):
@@ -585,10 +629,12 @@ class FromChannelsLast(_Differentiable):
 
 # ---------------------------------------------------------------------------------- differentiable ops (ops.* call these)
 def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, row_scale=None, res=None, res_masked=False,
-              res2=None):
+              res2=None, drop=None):
     v = Linear.apply(x, weight, bias, row_mask)
     if act != ACT_NONE:
         v = Activation.apply(v, act)          # act(0) = 0 for ReLU and GELU: masking before the activation = after it
+    if drop is not None:
+        v = Dropout.apply(v, drop)            # (masking and dropout commute: the row mask stays in Linear)
     if scale is not None or row_scale is not None or res is not None or res2 is not None:
         v = ScaleResidual.apply(v, scale, row_scale, row_mask, res, res_masked, res2)
     return v

@@ -13,13 +13,15 @@ Two call forms per module:
     that need the (sequences, frames) structure (models/ragged.py); everything else works row by row.
 Under torch.no_grad() (eval, validation) the modules run the fused inference kernels; with autograd recording
 they run the differentiable composition of vrdone_amd/autograd.py (HIP forward and backward kernels, plain f32 rows),
-and in training mode AffineDropPath samples its per-sample keep factors (reference blocks.py:1107-1120).
+and in training mode AffineDropPath samples its per-sample keep factors (reference blocks.py:1107-1120).  Under the same rule
+(``module.training and torch.is_grad_enabled()``) the TransformerBlocks apply `attn_pdrop` / `proj_pdrop` (_StepDropout below).
 """
 import math
 
 import torch
 from torch import nn
 
+from .. import dropout as _dropout
 from . import ragged
 from .ragged import Layout, _ops
 from .transformer import _get_activation_fn  # noqa: F401  (re-exported like the reference)
@@ -108,7 +110,8 @@ class ConvMLP(nn.Module):
     def __init__(self, input_dim, hidden_dim, output_dim, num_layers, kernel_size=1, act_layer='gelu', drop=0.0,
                  with_bias=True):
         super().__init__()
-        assert kernel_size == 1 and act_layer == 'gelu' and drop == 0.0
+        assert kernel_size == 1 and act_layer == 'gelu'
+        assert drop == 0.0, "ConvMLP: drop > 0 is not built (dropout exists for the backbone's TransformerBlocks only)"
         self.num_layers = num_layers
         dims = [input_dim] + [hidden_dim] * (num_layers - 1) + [output_dim]
         self.layers = nn.ModuleList(nn.Conv1d(a, b, 1, bias=with_bias) for a, b in zip(dims[:-1], dims[1:]))
@@ -196,6 +199,89 @@ class AffineDropPath(nn.Module):
         return y if rf is None else y * rf.view(-1, 1, 1)
 
 
+class Drop:
+    """One dropout call as the kernels take it: the step's seed (a one-element int64 tensor on the device, read through its
+    pointer), the module's site word, the number of the call's first row in the module's step-long row count, the rate."""
+    __slots__ = ("seed", "site", "row0", "p")
+
+    def __init__(self, seed, site, row0, p):
+        self.seed, self.site, self.row0, self.p = seed, int(site), int(row0), float(p)
+
+
+class _DropoutStep:
+    """The 64-bit seed of the training step at hand, one per device.  begin_dropout_step draws it from torch's generator ON the
+    device (inside a recording when training graphs are on: the draw is replayed, every replay gets a fresh seed -- the mechanism
+    of _FactorPool) or fills in the pinned value, and resets the sample counters of the modules it is given."""
+
+    def __init__(self):
+        self.seeds = {}
+
+    @staticmethod
+    def _key(device):
+        device = torch.device(device)
+        return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+    def begin(self, root, device, pinned=None):
+        device = self._key(device)
+        if pinned is None:
+            seed = torch.empty(1, dtype=torch.int64, device=device).random_()
+        else:
+            v = int(pinned) & 0xFFFFFFFFFFFFFFFF
+            seed = torch.full((1,), v - (1 << 64) if v >> 63 else v, dtype=torch.int64, device=device)
+        self.seeds[device] = seed
+        for mod in root.modules():
+            if isinstance(mod, _StepDropout):
+                mod._drop_samples = 0
+        return seed
+
+    def seed(self, device):
+        seed = self.seeds.get(self._key(device))
+        if seed is None:
+            raise RuntimeError("dropout: no training step was begun on this device -- MaskVRD.forward_training does it; a module "
+                               "trained on its own calls vrdone_amd.models.blocks.begin_dropout_step(module, device[, seed]) first")
+        return seed
+
+
+_dropout_step = _DropoutStep()
+
+
+def begin_dropout_step(root, device, seed=None):
+    """Start a training step for the dropout sites under `root`: seed None draws the step's 64-bit seed on the device, an integer
+    pins it (tests, goldens); the modules' sample counters restart at 0.  Returns the seed tensor."""
+    return _dropout_step.begin(root, device, seed)
+
+
+class _StepDropout:
+    """Mixin of a module that owns dropout sites (vrdone_amd/dropout.py: the keep decision is a pure function of the step's seed,
+    the site and the element id; nothing is stored).  Dropout acts only when `module.training and torch.is_grad_enabled()`, the
+    rule of AffineDropPath.row_factors.  The module counts the samples it has seen in the step: a second call continues the
+    first one's rows."""
+
+    def _init_dropout(self, rates):
+        self._drop_rates = {k: float(v) for k, v in rates.items()}
+        for k, v in self._drop_rates.items():
+            assert 0.0 <= v < 1.0, f"{type(self).__name__}: the dropout rate {k} = {v} lies outside [0, 1)"
+        self._drop_samples = 0
+        self.set_dropout_names("")
+
+    def set_dropout_names(self, prefix):
+        """prefix: this module's name in the reference's module tree (e.g. "backbone.stem.0.attn"): its sites are crc32 of
+        prefix + "." + the dropout module's name there."""
+        self.drop_sites = {k: _dropout.site_id(f"{prefix}.{k}" if prefix else k) for k in self._drop_rates}
+
+    def dropout_active(self):
+        return self.training and torch.is_grad_enabled() and any(self._drop_rates.values())
+
+    def _drops(self, n_samples, rows_per_sample, device):
+        """{site name: Drop} of this call (only sites with a rate > 0; {} when dropout does not act), advancing the sample count."""
+        if not self.dropout_active():
+            return {}
+        seed = _dropout_step.seed(device)
+        row0 = self._drop_samples * rows_per_sample
+        self._drop_samples += n_samples
+        return {k: Drop(seed, self.drop_sites[k], row0, p) for k, p in self._drop_rates.items() if p > 0.0}
+
+
 class Scale(nn.Module):
     """Learnable scalar (reference models/blocks.py:1084-1102); not on the hot path, kept because
     utils/train_utils.py:8 imports it."""
@@ -208,12 +294,12 @@ class Scale(nn.Module):
         return x * self.scale
 
 
-class _ConvAttention(nn.Module):
+class _ConvAttention(nn.Module, _StepDropout):
     """Parameter tree shared by the conv-attention modules: depthwise conv + LayerNorm per
     q/k/v branch, then 1x1 projections (creation order = reference state_dict order)."""
     _half_win = None                # half the window of the banded forms; None = global attention
 
-    def _build(self, n_embd, n_head, q_kernel, kv_kernel, stride):
+    def _build(self, n_embd, n_head, q_kernel, kv_kernel, stride, attn_pdrop=0.0, proj_pdrop=0.0):
         assert n_embd % n_head == 0
         self.n_embd, self.n_head = n_embd, n_head
         self.n_channels = n_embd // n_head
@@ -225,8 +311,9 @@ class _ConvAttention(nn.Module):
         self.key = nn.Conv1d(n_embd, n_embd, 1)
         self.query = nn.Conv1d(n_embd, n_embd, 1)
         self.value = nn.Conv1d(n_embd, n_embd, 1)
-        self.attn_drop, self.proj_drop = nn.Dropout(0.0), nn.Dropout(0.0)
+        self.attn_drop, self.proj_drop = nn.Dropout(attn_pdrop), nn.Dropout(proj_pdrop)      # (the reference's modules; the kernels drop)
         self.proj = nn.Conv1d(n_embd, n_embd, 1)
+        self._init_dropout({"attn_drop": attn_pdrop, "proj_drop": proj_pdrop})
 
     def _branch_set(self, name):
         conv, norm = getattr(self, f"{name}_conv"), getattr(self, f"{name}_norm")
@@ -272,11 +359,16 @@ class _ConvAttention(nn.Module):
             ((k, self.key.weight, self.key.bias), dict(out_pair=out_pair, skip_rows=kv_mask)),
             ((v, self.value.weight, self.value.bias), dict(out_pair=out_pair, skip_rows=kv_mask))]))
 
-    def _attend(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", ready=None, **epilogue):
+    def _attend(self, q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=1, pre_ln=None, pre_ln_on="qkv", ready=None, drops=None,
+                **epilogue):
         """The module's forward: the queries q_in in the layout qlay attend to the keys / values k_in / v_in in klay; q_mask /
         kv_mask are the masks behind the depthwise convs' stride; epilogue kwargs go to the output-projection GEMM.
-        ready: branch outputs of the depthwise-conv stage that the caller computed (see _prep)."""
+        ready: branch outputs of the depthwise-conv stage that the caller computed (see _prep).
+        drops: {"attn_drop" / "proj_drop": Drop} of a training call (_StepDropout._drops)."""
         ops = _ops()
+        drops = drops or {}
+        if "proj_drop" in drops:
+            epilogue["drop"] = drops["proj_drop"]
         q, k, v = self._prep(q_in, k_in, v_in, q_mask, kv_mask, qlay, klay, stride=stride, pre_ln=pre_ln, pre_ln_on=pre_ln_on,
                              ready=ready)
         qlay, klay = qlay.strided(stride), klay.strided(stride)
@@ -284,7 +376,7 @@ class _ConvAttention(nn.Module):
         qkv_pair = self._half_win is None and ops.flash_pair_ok(self.n_head, self.n_embd, qlay.min_frames())
         q, k, v = self._project(q, k, v, out_pair=qkv_pair, q_mask=q_mask, kv_mask=kv_mask)
         att = ragged.attention(q, k, v, kv_mask, q_mask, self.n_head, qlay, klay, half_win=self._half_win,
-                               rel_pe=getattr(self, "rel_pe", None), pair=ops.pair_mode())
+                               rel_pe=getattr(self, "rel_pe", None), pair=ops.pair_mode(), drop=drops.get("attn_drop"))
         return ops.conv_gemm(att, self.proj.weight, self.proj.bias, row_mask=q_mask, **epilogue), q_mask
 
     def _cl_strided(self, x, mask, mask_out=None, pre_ln=None, lay=None, **epilogue):
@@ -294,7 +386,8 @@ class _ConvAttention(nn.Module):
         if mask_out is None:
             mask_out = mask if s == 1 else mask[:, ::s].contiguous()
         lay = Layout.of(lay, mask)
-        return self._attend(x, x, x, mask_out, mask_out, lay, lay, stride=s, pre_ln=pre_ln, **epilogue)
+        drops = self._drops(mask_out.shape[0], mask_out.shape[1], mask_out.device)
+        return self._attend(x, x, x, mask_out, mask_out, lay, lay, stride=s, pre_ln=pre_ln, drops=drops, **epilogue)
 
 
 def make_rel_pe(n_embd, n_head, window_size):
@@ -313,13 +406,12 @@ class LocalMaskedMHCA(_ConvAttention):
         super().__init__()
         assert window_size > 1 and window_size % 2 == 1
         assert n_qx_stride == n_kv_stride and n_kv_stride in (1, 2)
-        assert attn_pdrop == 0.0 and proj_pdrop == 0.0
         self.window_size, self.window_overlap = window_size, window_size // 2
         self._half_win = self.window_overlap
         self.use_rel_pe = use_rel_pe
         self.n_qx_stride, self.n_kv_stride = n_qx_stride, n_kv_stride
         ks = n_kv_stride + 1 if n_kv_stride > 1 else 3
-        self._build(n_embd, n_head, ks, ks, n_kv_stride)
+        self._build(n_embd, n_head, ks, ks, n_kv_stride, attn_pdrop, proj_pdrop)
         self.rel_pe = make_rel_pe(n_embd, n_head, window_size) if use_rel_pe else None
 
     # (the reference's sliding-chunk form needs T / s to be a multiple of 2 * window_overlap, blocks.py:828, and its callers
@@ -340,10 +432,11 @@ class MaskedMHCA(_ConvAttention):
     def __init__(self, n_embd, n_head, n_qx_stride=1, n_kv_stride=1, attn_pdrop=0.0, proj_pdrop=0.0):
         super().__init__()
         assert n_qx_stride == n_kv_stride and n_kv_stride in (1, 2), "built for equal query / key-value strides 1 or 2"
-        assert attn_pdrop == 0.0 and proj_pdrop == 0.0
+        assert attn_pdrop == 0.0, ("MaskedMHCA: attn_pdrop (`dropattn`) > 0 is not built for global attention -- the flash kernels "
+                                   "never form the probabilities it acts on; proj_pdrop (`dropout`) is")
         self.n_qx_stride, self.n_kv_stride = n_qx_stride, n_kv_stride
         ks = n_kv_stride + 1 if n_kv_stride > 1 else 3
-        self._build(n_embd, n_head, ks, ks, n_kv_stride)
+        self._build(n_embd, n_head, ks, ks, n_kv_stride, 0.0, proj_pdrop)
 
     cl = _ConvAttention._cl_strided
 
@@ -357,7 +450,9 @@ class MaskedMHA(nn.Module):
 
     def __init__(self, n_embd, n_head, attn_pdrop=0.0, proj_pdrop=0.0):
         super().__init__()
-        assert n_embd % n_head == 0 and attn_pdrop == 0.0 and proj_pdrop == 0.0
+        assert n_embd % n_head == 0
+        assert attn_pdrop == 0.0, "MaskedMHA: attn_pdrop > 0 is not built (dropout exists for the backbone's TransformerBlocks only)"
+        assert proj_pdrop == 0.0, "MaskedMHA: proj_pdrop > 0 is not built (dropout exists for the backbone's TransformerBlocks only)"
         self.n_embd, self.n_head = n_embd, n_head
         self.n_channels = n_embd // n_head
         self.scale = 1.0 / math.sqrt(self.n_channels)
@@ -382,7 +477,7 @@ class MaskedMHA(nn.Module):
         return _from_cl(y), mask
 
 
-class TransformerBlock(nn.Module):
+class TransformerBlock(nn.Module, _StepDropout):
     """LN -> local conv attention -> (max-pool) skip, LN -> MLP; reference models/blocks.py:992-1080."""
 
     def __init__(self, n_embd, n_head, n_ds_strides=(1, 1), n_out=None, n_hidden=None, act_layer=nn.GELU,
@@ -411,6 +506,14 @@ class TransformerBlock(nn.Module):
         else:
             self.drop_path_attn = nn.Identity()
             self.drop_path_mlp = nn.Identity()
+        self._init_dropout({"mlp.2": proj_pdrop, "mlp.4": proj_pdrop})
+
+    def set_dropout_names(self, prefix):
+        """prefix: the block's name in the reference's module tree ("backbone.stem.0"): names its four sites, `attn.attn_drop`,
+        `attn.proj_drop`, `mlp.2` and `mlp.4` under it."""
+        _StepDropout.set_dropout_names(self, prefix)
+        if hasattr(self, "attn"):
+            self.attn.set_dropout_names(f"{prefix}.attn" if prefix else "attn")
 
     @staticmethod
     def _scale(dp):
@@ -434,9 +537,12 @@ class TransformerBlock(nn.Module):
                             scale=self._scale(self.drop_path_attn), row_scale=self._drop(self.drop_path_attn, m_out),
                             res=skip, res_masked=True)
         h = self.ln2.cl(y, pair=ops.pair_mode())
-        h = ops.conv_gemm(h, self.mlp[0].weight, self.mlp[0].bias, act=ops.ACT_GELU, out_pair=ops.pair_mode(), skip_rows=m_out)
+        drops = self._drops(m_out.shape[0], m_out.shape[1], m_out.device)
+        kw0 = {"drop": drops["mlp.2"]} if drops else {}          # (only a training call knows the argument: at rate 0 nothing changes)
+        kw1 = {"drop": drops["mlp.4"]} if drops else {}
+        h = ops.conv_gemm(h, self.mlp[0].weight, self.mlp[0].bias, act=ops.ACT_GELU, out_pair=ops.pair_mode(), skip_rows=m_out, **kw0)
         y = ops.conv_gemm(h, self.mlp[3].weight, self.mlp[3].bias, row_mask=m_out, scale=self._scale(self.drop_path_mlp),
-                          row_scale=self._drop(self.drop_path_mlp, m_out), res=y, out=out)
+                          row_scale=self._drop(self.drop_path_mlp, m_out), res=y, out=out, **kw1)
         return y, m_out
 
     def forward(self, x, mask, pos_embd=None):

@@ -31,7 +31,10 @@ class MaskedMHCA_QKV(_ConvAttention):
 
     def __init__(self, n_embd, n_head, n_qx_stride=0, n_kv_stride=1, attn_pdrop=0.0, proj_pdrop=0.0):
         super().__init__()
-        assert n_qx_stride in (0, 1) and n_kv_stride in (0, 1) and attn_pdrop == 0.0 and proj_pdrop == 0.0
+        assert n_qx_stride in (0, 1) and n_kv_stride in (0, 1)
+        # (dropout exists for the backbone's TransformerBlocks: the reference's backbone hands its SOS layers no dropout argument)
+        assert attn_pdrop == 0.0, f"{type(self).__name__}: attn_pdrop > 0 is not built"
+        assert proj_pdrop == 0.0, f"{type(self).__name__}: proj_pdrop > 0 is not built"
         self.n_qx_stride, self.n_kv_stride = n_qx_stride, n_kv_stride
         self._build(n_embd, n_head, _qkv_kernel(n_qx_stride), _qkv_kernel(n_kv_stride), 1)
 
@@ -76,6 +79,10 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
                  use_rel_pe=False):
         super().__init__()
         assert n_qx_stride >= 0 and n_kv_stride >= 0 and act_layer is nn.GELU
+        # the predictor's own `attn_pdrop` / `proj_pdrop` keys end here (attention and FFN dropout of the decoder layers)
+        assert attn_pdrop == 0.0, "MaskedConvTransformerDecoderLayer: attn_pdrop > 0 (the predictor's `attn_pdrop`) is not built"
+        assert proj_pdrop == 0.0, ("MaskedConvTransformerDecoderLayer: proj_pdrop > 0 (the predictor's `proj_pdrop`: projection and "
+                                   "FFN dropout) is not built")
         self.with_ffn = with_ffn
         self.ln1 = LayerNorm(n_embd)
         self.ln2 = LayerNorm(n_embd)

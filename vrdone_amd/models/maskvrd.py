@@ -16,7 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .backbones import MaskConvTransformerBackbone, MaskConvTransformerBackboneWithCLIP
-from .blocks import _factor_pool, _ops
+from .blocks import TransformerBlock, _factor_pool, _ops, begin_dropout_step
 from .. import train_graph
 from . import eval_batches, losses
 from .fpns import FPN1D_Fuse
@@ -88,6 +88,15 @@ class MaskVRD(nn.Module):
         self.share_tracklets = True     # forward_test from a PairSource: entity stage once per tracklet (eval_batches.SharedStreams)
         self.device_matching = True       # Hungarian assignment on the device (vrd_assign); False: scipy on the host
         self.device_criterion = True      # ... and the losses straight from its result, no trip to the host (_criterion_on_device)
+        # `dropattn` / `dropout`: the backbone's TransformerBlocks drop by (step seed, site, element id) (vrdone_amd/dropout.py); a
+        # site is named after its module in the reference's tree, which the checkpoint layout makes this tree's names too
+        for name, mod in self.named_modules():
+            if isinstance(mod, TransformerBlock):
+                mod.set_dropout_names(name)
+        self.dropout_rates = (float(config['dropattn']), float(config['dropout']))
+        # None: every training step draws its 64-bit seed on the device from torch's generator; an integer pins it (tests, goldens:
+        # the counterpart of AffineDropPath.keep)
+        self.dropout_seed = None
 
     @torch.no_grad()
     def _config_eval(self, infer_config):
@@ -278,9 +287,7 @@ class MaskVRD(nn.Module):
                     return eval_batches.mask_vrd_rows(self, batched_inputs, masks2d, plan["buckets"], with_aux)
                 return self._mask_vrd_tight(batched_inputs, masks2d, plan, with_aux)
         if self.training and torch.is_grad_enabled():
-            # a training step: the split-precision operands of all dense conv weights (forward and input-gradient form) in one
-            # launch instead of one per weight and form (they are rebuilt after every optimiser update)
-            _ops().presplit_weights(self._dense_conv_weights(), self.__dict__.setdefault("_split_plans", {}))
+            self._begin_training_pass(batched_inputs.device)
         outs = []
         step = self._chunk_size(B)
         for b0 in range(0, B, step):
@@ -289,6 +296,15 @@ class MaskVRD(nn.Module):
             outs.append(self._heads(*self.backbone.cl(x, m), with_aux))
         return self._merge(outs)
 
+    def _begin_training_pass(self, device):
+        """What a differentiable pass over the network starts with, inside a recording when training graphs are on: the derived
+        weight operands and, for a model that drops, the step's seed and the restart of its modules' sample counters."""
+        # the split-precision operands of all dense conv weights (forward and input-gradient form) in one launch instead of one
+        # per weight and form (they are rebuilt after every optimiser update)
+        _ops().presplit_weights(self._dense_conv_weights(), self.__dict__.setdefault("_split_plans", {}))
+        if any(self.dropout_rates):
+            begin_dropout_step(self, device, self.dropout_seed)
+
     def _mask_vrd_parts(self, vis, clip, so_box, ent, masks2d, with_aux=None):
         """`_mask_vrd` from the backbone's operand buffers (ops.gather_train) instead of the (B, C_in, T) boundary tensor:
         what `_mask_vrd` runs behind `backbone._unpack`, in one launch wave."""
@@ -296,7 +312,7 @@ class MaskVRD(nn.Module):
         if B > self._chunk_size(B):
             raise ValueError(f"a device-built training batch runs as one launch wave: {B} sequences exceed pair_chunk = {self.pair_chunk}")
         if self.training and torch.is_grad_enabled():
-            _ops().presplit_weights(self._dense_conv_weights(), self.__dict__.setdefault("_split_plans", {}))
+            self._begin_training_pass(masks2d.device)
         return self._heads(*self.backbone.cl_parts(vis, clip, so_box, ent, masks2d), with_aux)
 
     def __deepcopy__(self, memo):

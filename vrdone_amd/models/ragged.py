@@ -220,12 +220,17 @@ def dwconv_ln_multi(lay, x, sets, mask_out, *, pre_ln=None):
     return [ops.Pair(b, Cout) if ops._fmt(st.get("pair")) else b for st, b in zip(sets, bufs)]
 
 
-def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False):
+def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False, drop=None):
     """Global (half_win None) or banded attention of the queries in `qlay` over the keys in `klay`: bucket by bucket, or the
     buckets as the row groups of one kernel call (banded attention; global attention on pair rows with ATTN_SEGS).
-    q_mask: rows the caller masks afterwards (global attention only)."""
+    q_mask: rows the caller masks afterwards (global attention only).
+    drop: the attn_drop call of a training step (blocks.Drop; banded attention in the batch form only)."""
     ops = _ops()
     qsegs, ksegs = qlay.segs, klay.segs
+    if drop is not None:
+        assert half_win is not None and len(qsegs) == 1 and qlay.axis == 0, "attention dropout: banded attention in the batch form"
+        return qlay.whole(ops.local_attention(qlay.part(q, qsegs[0]), klay.part(k, ksegs[0]), klay.part(v, ksegs[0]),
+                                              klay.part(kv_mask, ksegs[0]), n_head, half_win, rel_pe=rel_pe, drop=drop))
     # buckets of one frame count on both sides (the predictor's query self-attention: every bucket is n x Q rows) are one launch
     if len(_merged(qsegs)) == 1 and len(_merged(ksegs)) == 1:
         qsegs, ksegs = _merged(qsegs), _merged(ksegs)

@@ -857,7 +857,7 @@ def launch_gemm(a):
 
 
 def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, res=None, res_masked=False,
-              res2=None, out=None, out_pair=False, skip_rows=None, row_scale=None, split_fmt=None):
+              res2=None, out=None, out_pair=False, skip_rows=None, row_scale=None, split_fmt=None, drop=None):
     """Dense Conv1d (k = 1 or 3, stride 1, zero padding k//2) with the fused epilogue of
     vrd_gemm.  x: (B, T, Cin) tensor or Pair; weight: the Conv1d parameter (N, Cin, k).
     out_pair: write the result as pair rows of width N (returns a Pair).
@@ -865,18 +865,21 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
     row_mask, which is then the default; without row_mask those rows hold bias-only filler, so pass it only where
     no valid row ever reads a padded one: projections feeding masked attention, an MLP's hidden layer).
     row_scale (rows,): per-row factor on the branch term (stochastic depth, blocks.py:1107-1120); autograd path only.
+    drop: a training step's dropout call (models.blocks.Drop) on the activated GEMM output, before scale / residuals (proj_drop and
+    the MLP dropouts, blocks.py:988,1057,1059); autograd path only.
     split_fmt: element format of the split products instead of the mode's (the unfused backward GEMMs pass PAIR_BF16; 0 = exact
     f32 products whatever the mode, None = the mode's format).
     Under autograd (`recording`) the op runs as autograd.conv_gemm and returns a fresh tensor (`out` is ignored)."""
     # row_scale (stochastic depth, sampled whenever the model trains) lives in the autograd form's epilogue: it goes there even
     # when nothing of this call needs a gradient (a frozen sub-module under requires_grad_(False), reference blocks.py:1107-1120
     # drops paths regardless)
-    if not isinstance(x, Pair) and (recording(x, weight, bias, scale, res, res2) or row_scale is not None):
+    if not isinstance(x, Pair) and (recording(x, weight, bias, scale, res, res2) or row_scale is not None or drop is not None):
         from . import autograd
         assert not out_pair
         return autograd.conv_gemm(x, weight, bias, act=act, row_mask=row_mask, scale=scale, row_scale=row_scale, res=res,
-                                  res_masked=res_masked, res2=res2)
+                                  res_masked=res_masked, res2=res2, drop=drop)
     assert row_scale is None, "row_scale (drop-path sampling) exists for plain f32 rows only"
+    assert drop is None, "dropout exists for plain f32 rows only"
     a, result = gemm_args(x, weight, bias, act=act, row_mask=row_mask, scale=scale, res=res, res_masked=res_masked, res2=res2, out=out,
                           out_pair=out_pair, skip_rows=skip_rows, split_fmt=split_fmt)
     launch_gemm(a)
@@ -1099,11 +1102,13 @@ def _rel_pe_ptr(rel_pe, like, n_head, half_win):
     return rel_pe.data_ptr()
 
 
-def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, out=None, segs=None):
+def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, out=None, segs=None, drop=None):
     """rel_pe: None or the module's (1, 1, n_head, window) relative position bias (reference blocks.py:739-743).
     out: (B, T, C) contiguous rows to write instead of a fresh tensor (inference path).
     segs (inference path): q / k / v / mask are a ragged row space (1, R, ...): [(first row, sequences, frames)] (vrd_row_segs).
-    half_win: window // 2 of an odd window from 3 to 19."""
+    half_win: window // 2 of an odd window from 3 to 19.
+    drop (training): the attn_drop call (models.blocks.Drop: seed tensor, site, first row's number, rate) -- dropout on the window
+    probabilities; such a call runs as autograd.LocalAttention whether or not an input needs a gradient (it drops regardless)."""
     if not (isinstance(half_win, int) and 1 <= half_win <= 9):
         raise ValueError(f"local_attention: the window must be odd, from 3 to 19 (half_win = window // 2 an integer from 1 to 9), "
                          f"got half_win {half_win!r}")
@@ -1111,9 +1116,10 @@ def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, ou
     if not (width in (256, 512) and isinstance(n_head, int) and n_head > 0 and width % n_head == 0 and width // n_head in (32, 64, 128)):
         raise ValueError(f"local_attention: built for width 256 or 512 with head_dim = width / n_head of 32, 64 or 128 "
                          f"(16, 8 or 4 heads at 512; 8, 4 or 2 at 256), got width {width}, n_head {n_head!r}")
-    if recording(q, k, v, rel_pe):
+    if recording(q, k, v, rel_pe) or drop is not None:
         from . import autograd
-        return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe)
+        assert drop is None or (segs is None and not pair)
+        return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe, drop)
     B, T, Cc = q.shape
     rel = _rel_pe_ptr(rel_pe, q, n_head, half_win)
     pq, rows, cols, ld = _rows(q)

@@ -167,13 +167,16 @@ def recordings(model):
 
 def _mode_key(model):
     """Everything that shapes the captured launch sequence besides the batch shape: precision mode, launch-wave size, the
-    stochastic-depth probabilities and pinned keep vectors of every AffineDropPath, which parameters train, and (last) the
-    deterministic mode (its gradient kernels take other launches and scratch)."""
-    from .models.blocks import AffineDropPath
+    stochastic-depth probabilities and pinned keep vectors of every AffineDropPath, the dropout rates and the pinned dropout seed
+    (a recording holds the seed tensor its kernels read: a free seed is drawn inside it, a pinned one is filled in there), which
+    parameters train, and (last) the deterministic mode (its gradient kernels take other launches and scratch)."""
+    from .models.blocks import AffineDropPath, _StepDropout
     drops = tuple((mod.drop_prob, None if mod.keep is None else mod.keep.data_ptr()) for mod in model.modules()
                   if isinstance(mod, AffineDropPath))
     trainable = tuple(p.requires_grad for p in model.parameters())
-    return (bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops, trainable, ops.get_deterministic())
+    dropout = (tuple(tuple(mod._drop_rates.values()) for mod in model.modules() if isinstance(mod, _StepDropout)),
+               getattr(model, "dropout_seed", None))
+    return (bool(model.deep_supervision), ops.get_precision(), int(model.pair_chunk), drops, dropout, trainable, ops.get_deterministic())
 
 
 def recording_key(model, x, m):
