@@ -490,7 +490,8 @@ int vrd_maxpool_mask(const float* x, int64_t ldx, int B, int Tin, int C, const u
 
 /* ---- mask head, models/predictor.py:103-104,110-111 --------------------------------------
  * seg[b,q,t] = sum_c emb[b,q,c] * feat[b,t,c]; -10 where out_mask[b,t] == 0.
- * emb: (B*Q) x Dp rows; feat: (B*T) x Dp rows; seg: (B, Q, T) contiguous. */
+ * emb: (B*Q) x Dp rows; feat: (B*T) x Dp rows; seg: (B, Q, T) contiguous.  1 <= Q <= 64: above 16 the queries pass
+ * 16 at a time against the resident frame tile, each output the same sum in the same order as at Q <= 16. */
 int vrd_mask_head(const float* emb, int64_t ld_emb, const float* feat, int64_t ld_feat,
                   const uint8_t* out_mask, int B, int Q, int T, int Dp, float fill,
                   float* seg, void* stream);
@@ -845,10 +846,17 @@ int vrd_maxpool_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, 
 
 /* ---- training tail on the device ----------------------------------------------------------------------
  * Hungarian assignment of the matcher (models/maskvrd.py:484-492: `.cpu()` + scipy linear_sum_assignment per pair).
- * cost: (sum N, Q) rows = relations (leading dimension ld), row r of pair p = first[p] + r, count[p] = N_p <= Q <= 16.
+ * cost: (sum N, Q) rows = relations (leading dimension ld), row r of pair p = first[p] + r, count[p] = N_p <= Q <= 64.
  * query_of[first[p] + r] = the query relation r of pair p is assigned to (the minimum-cost assignment; pairs with
- * count 0 are skipped).  Double-precision potentials; the result equals scipy's whenever the optimum is unique. */
+ * count 0 are skipped).  Double-precision potentials; the result equals scipy's whenever the optimum is unique.
+ * Q <= 16: one thread per pair; 16 < Q <= 64: forwards to vrd_assign_wave. */
 int vrd_assign(const float* cost, int64_t ld, const int32_t* first, const int32_t* count, int P, int Q, int32_t* query_of, void* stream);
+/* The same assignment with one wave per pair, 1 <= Q <= 64: lane j owns query j's column, the column scan, the potential
+ * update and the argmin are wave operations; the argmin compares (value, column), so a tie goes to the lowest column as in the
+ * one-thread form, and the two return the same assignment on every input, tied ones included.  Refusals as vrd_assign's: a NaN
+ * or -inf entry in a pair's block, no usable column, or count[p] > Q give -1 for all of the pair's relations. */
+int vrd_assign_wave(const float* cost, int64_t ld, const int32_t* first, const int32_t* count, int P, int Q, int32_t* query_of,
+                    void* stream);
 
 /* EMA of a whole state dict in one launch (utils/train_utils.py:21-29): for every tensor t and element i,
  * ema[t][i] = decay * ema[t][i] + one_minus_decay * model[t][i], both products and the sum rounded to f32 (the reference's
@@ -890,7 +898,7 @@ int vrd_scale_tensors(float* const* grad, const int64_t* numel, const int32_t* v
 /* ---- the training criterion for all decoder layers of a step --------------------------------------------
  * Replaces the tensor code of models/maskvrd.py:417-496 (bipartite_match: the three cost matrices), :498-588 (loss_labels,
  * loss_masks on the final head and the auxiliary heads) and models/losses.py:4-354 (masked focal / dice, plain and fuzzy
- * targets).  Layer l's predictions: logits[l] (B, Q, K1), masks[l] (B, Q, T), contiguous f32.  Ground truth of the batch:
+ * targets).  Layer l's predictions: logits[l] (B, Q, K1), masks[l] (B, Q, T), contiguous f32, 1 <= Q <= 64.  Ground truth of the batch:
  * G relations; owner[g] = pair of relation g; tgt_ids[g] its predicate class; tgt_masks (G, T) 0/1; out_valid (B, T) the
  * pairs' valid frames; segs (G, 2) [start, end) frames -- non-null selects the fuzzy targets of losses.py:214-227 with
  * scale_range.  alpha < 0 switches the focal weighting off, like the reference's. */

@@ -1,0 +1,153 @@
+"""`predictor.num_queries` from 1 to 64, the parts that need no GPU: the constructor's envelope, the new entry point's declaration,
+export and binding, the fixtures of scripts/make_golden_queries.py against tests/queries_cases.py, the assignment case table at
+the new query counts, and the oracle against the reference at 24, 33 and 64 queries."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import head_cases as H
+import queries_cases as QC
+from conftest import GOLDEN, REPO, load_case
+from oracle import vrd_oracle as O
+
+LOGIT_TOL, MASK_TOL = 2e-5, 2e-4        # tests/test_oracle_golden.py
+
+
+@pytest.mark.parametrize("Q", [1, 17, 64])
+def test_constructor_accepts_up_to_64_queries(Q):
+    from vrdone_amd.models.maskvrd import MaskVRD
+    mc, _, keys = load_case("vidvrd")
+    mc = QC.model_config(mc, Q)
+    model = MaskVRD(mc, device="cpu")
+    assert model.predictor.num_queries == Q and model.MAX_QUERIES == QC.MAX_QUERIES == 64
+    assert [(k, tuple(v.shape)) for k, v in model.state_dict().items()] == QC.state_keys(keys, mc)
+
+
+@pytest.mark.parametrize("Q", [65, 0, 1000])
+def test_constructor_refuses_other_query_counts_by_name(Q):
+    from vrdone_amd.models.maskvrd import MaskVRD
+    mc, _, _ = load_case("vidvrd")
+    with pytest.raises(ValueError, match=rf"predictor\.num_queries must be 1\.\.64 \(got {Q}\)"):
+        MaskVRD(QC.model_config(mc, Q), device="cpu")
+
+
+def test_assign_wave_is_declared_exported_and_bound():
+    from vrdone_amd import _hip
+    header = open(os.path.join(REPO, "include", "vrdone_hip.h")).read()
+    plain = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    protos = dict(re.findall(r"\bint\s+(vrd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", plain))
+    norm = lambda s: " ".join(s.split())        # noqa: E731
+    assert norm(protos["vrd_assign_wave"]) == norm(protos["vrd_assign"])           # the arguments of vrd_assign
+    assert _hip._SIGNATURES["vrd_assign_wave"] == _hip._SIGNATURES["vrd_assign"]
+    lib = ctypes.CDLL(os.path.join(REPO, "vrdone_amd", "csrc", "libvrdone_hip.so"))
+    assert hasattr(lib, "vrd_assign_wave") and hasattr(_hip.lib, "vrd_assign_wave")
+    assert _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
+    assert re.search(r"#define\s+VRD_ABI_VERSION\s+36\b", header)
+    assert "`vrd_assign_wave`" in open(os.path.join(REPO, "INTEGRATION.md")).read()
+
+
+def test_library_refuses_query_counts_outside_the_envelope_by_name():
+    """Argument checks run before any launch: no GPU is needed to be refused."""
+    from vrdone_amd import _hip
+    buf = (ctypes.c_float * 4)()
+    ptr = ctypes.addressof(buf)
+    for fn, Q in (("vrd_assign_wave", 65), ("vrd_assign", 65), ("vrd_assign_wave", 0)):
+        rc = getattr(_hip.lib, fn)(ptr, 65, ptr, ptr, 1, Q, ptr, None)
+        assert rc != 0
+        with pytest.raises(Exception, match=r"vrd_assign_wave: Q must be 1\.\.64" if Q else r"Q must be 1\.\.64"):
+            _hip.check(rc, fn)
+    rc = _hip.lib.vrd_mask_head(ptr, 256, ptr, 256, ptr, 1, 65, 1, 256, -10.0, ptr, None)
+    assert rc != 0
+    with pytest.raises(Exception, match=r"num queries must be 1\.\.64 \(got 65\)"):
+        _hip.check(rc, "vrd_mask_head")
+
+
+def test_fixtures_load_and_match_the_cases():
+    g = QC.load_npz("queries_model")
+    for case, spec in QC.MODEL_CASES.items():
+        mc, _, _ = load_case(spec["base"])
+        B, Q, T, K1 = len(spec["lens"]), spec["Q"], spec["T"], mc["num_classes"] + 1
+        assert g[f"{case}/pred_logits"].shape == g[f"{case}/f64m32_pred_logits"].shape == (B, Q, K1)
+        assert g[f"{case}/pred_masks"].shape == g[f"{case}/f64m32_pred_masks"].shape == (B, Q, T)
+        assert g[f"{case}/pred_logits"].dtype == np.float32 and g[f"{case}/f64m32_pred_masks"].dtype == np.float32
+        for i in range(3):
+            assert g[f"{case}/aux{i}_pred_logits"].shape == (B, Q, -(-K1 // QC.CLASS_STRIDE))
+            assert g[f"{case}/aux{i}_pred_masks"].shape == (B, Q, -(-T // QC.MASK_T_STRIDE))
+        assert 2 in spec["lens"] and T in spec["lens"]
+        pad = np.arange(T)[None, None, :] >= np.asarray(spec["lens"])[:, None, None]
+        assert (g[f"{case}/pred_masks"][np.broadcast_to(pad, (B, Q, T))] == -10.0).all()
+        # the float64 run differs from the float32 one by the reference's own rounding, and by no more
+        assert 0 < np.abs(g[f"{case}/f64m32_pred_logits"]).max() < 5e-5 and 0 < np.abs(g[f"{case}/f64m32_pred_masks"]).max() < 5e-4
+    with open(os.path.join(GOLDEN, "forward_test_vidvrd_q24.json")) as f:
+        ft = json.load(f)
+    with open(os.path.join(GOLDEN, "forward_test_vidvrd.json")) as f:
+        ft9 = json.load(f)
+    assert ft["n_pairs"] == ft9["n_pairs"] and ft["pair_lengths"] == ft9["pair_lengths"]          # the same proposal
+    assert len(ft["triplets"]) == len(ft9["triplets"]) and ft["triplets"] != ft9["triplets"]
+    with open(os.path.join(GOLDEN, "train_step_vidvrd_q24.json")) as f:
+        meta = json.load(f)
+    mc, _, keys = load_case("vidvrd")
+    mc = QC.model_config(mc, 24)
+    lens, _, _, data = QC.train_batch(mc)
+    sizes = [len(p) for p in data["preds_list"]]
+    assert meta["lengths"] == lens and meta["sizes"] == sizes and meta["num_queries"] == 24
+    assert (meta["B"], meta["T"], meta["sample_stride"]) == (QC.TRAIN_Q24["B"], QC.TRAIN_Q24["T"], QC.GRAD_STRIDE)
+    assert max(sizes) == 24 and min(sizes) == 1
+    assert [(k, tuple(s)) for k, s in meta["state_keys"]] == QC.state_keys(keys, mc)
+    case = meta["cases"]["nodrop"]
+    assert len(case["indices"]) == 4                          # the final head and three auxiliary layers
+    for call in case["indices"]:
+        assert [len(i) for i, _ in call] == sizes and all(sorted(j) == list(range(n)) for (_, j), n in zip(call, sizes))
+        assert all(len(set(i)) == len(i) and max(i) < 24 for i, _ in call)
+    gt = QC.load_npz("train_step_vidvrd_q24")
+    assert set(gt) == {f"nodrop/{k}" for k in case["grad_stats"]} and len(gt) > 300
+    assert gt["nodrop/predictor.query_embed.weight"].shape == QC.sample(torch.zeros(24, 256)).shape
+
+
+TIED_KINDS = ("int", "identical_columns", "base_noise")
+
+
+@pytest.mark.parametrize("Q", [17, 32, 33, 64])
+@pytest.mark.parametrize("kind", H.ASSIGN_KINDS)
+def test_assignment_case_table_is_not_vacuous_above_16_queries(kind, Q):
+    """What the GPU test of the wave kernel checks against: unique optima where scipy's very queries are demanded, refused blocks
+    where -1 is, ties where only the total is."""
+    cost, sizes = H.assign_inputs(kind, Q)
+    expect = H.assign_expect(cost, sizes)
+    assert 65 <= len(sizes) <= 72 and max(sizes) == Q and cost.shape == (sum(sizes), Q)
+    solved = [e for e in expect if e is not None]                  # (a pair without relations counts as solved, uniquely)
+    refused = sum(e is None for e in expect)
+    unique = sum(e[2] for e in solved)
+    if kind in TIED_KINDS:
+        # quantised costs and twin columns tie in every pair of two relations or more; costs equal to a few ulp in most
+        multi = [e for e, n in zip(expect, sizes) if n >= 2]
+        tied = sum(not e[2] for e in multi)
+        assert refused == 0 and len(multi) >= 62 and (tied >= len(multi) // 2 if kind == "base_noise" else tied == len(multi))
+    elif kind == "inf40":
+        assert 25 <= refused <= 26 and 39 <= unique <= 46 and refused + len(solved) == len(sizes)
+    else:
+        assert refused == 0 and unique == len(solved) == len(sizes)
+
+
+@pytest.mark.parametrize("case", list(QC.MODEL_CASES))
+def test_oracle_matches_the_reference_at_more_queries(case):
+    """The oracle as it stands (it reads the query count off the embedding) against the reference's float32 run, at
+    tests/test_oracle_golden.py's bounds."""
+    spec = QC.MODEL_CASES[case]
+    mc, _, keys = load_case(spec["base"])
+    mc = QC.model_config(mc, spec["Q"])
+    sd = O.synth_state_dict(QC.state_keys(keys, mc), eos_coef=mc["loss_coeff_dict"]["eos_coef"])
+    g = QC.load_npz("queries_model")
+    x, m = O.synth_pairs(len(spec["lens"]), QC.c_in(mc), spec["T"], spec["lens"], seed=spec["seed"])
+    with torch.no_grad():
+        out = O.mask_vrd(sd, mc, x, m)
+    for pre, lg, mk in QC.heads(out):
+        if pre:
+            lg, mk = lg[..., ::QC.CLASS_STRIDE], mk[..., ::QC.MASK_T_STRIDE]
+        np.testing.assert_allclose(lg.numpy(), g[f"{case}/{pre}pred_logits"], atol=LOGIT_TOL, rtol=0)
+        np.testing.assert_allclose(mk.numpy(), g[f"{case}/{pre}pred_masks"], atol=MASK_TOL, rtol=0)

@@ -278,6 +278,7 @@ _SIGNATURES = {
     "vrd_attention_rows": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_int, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "vrd_assign": (C.c_int, [c_f32p, C.c_int64, c_i32p, c_i32p, C.c_int, C.c_int, c_i32p, C.c_void_p]),
+    "vrd_assign_wave": (C.c_int, [c_f32p, C.c_int64, c_i32p, c_i32p, C.c_int, C.c_int, c_i32p, C.c_void_p]),
     "vrd_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32p, c_i32p, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     # ---- gradient-norm clip + AdamW over pointer tables (csrc/vrd_optim.hip; vrdone_amd/optim.py)
     "vrd_grad_sumsq": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -64,9 +64,12 @@ __device__ __forceinline__ Lse wave_lse(const float* __restrict__ row, int K, in
     return {mx, logf(s)};
 }
 
+// one wave per query, at most COST_WAVES of them in a workgroup (1024 threads); more queries take further groups along grid z
+constexpr int COST_WAVES = 16;
 __global__ void criterion_costs_kernel(vrd_criterion_args a, float* __restrict__ cost) {
     const int g = blockIdx.x, l = blockIdx.y;
-    const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.z * COST_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= a.Q) return;                            // (wave-uniform; the last group of a query count above COST_WAVES)
     const int b = a.owner[g];
     const float* x = a.masks[l] + ((int64_t)b * a.Q + q) * a.T;
     const uint8_t* valid = a.out_valid + (int64_t)b * a.T;
@@ -117,7 +120,7 @@ __device__ __forceinline__ FocalAt focal_at(const vrd_criterion_args& a, int g, 
 }
 
 // Compensated (Kahan) running sum.  A wave of the loss kernel adds up to B * Q / 16 terms one after another: at the 12,000 rows
-// the kernel's table admits, a plain f32 sum is 5e-6 off the class loss, twenty times the tensor form's error.
+// the kernel's table admits (whatever the split between B and Q <= 64), a plain f32 sum is 5e-6 off the class loss, twenty times the tensor form's error.
 struct KahanSum {
     float s = 0.f, c = 0.f;
     __device__ __forceinline__ void add(float v) {
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(64) void criterion_backward_kernel(vrd_criterion_ar
 int check_args(const vrd_criterion_args* a, const char* what) {
     VRD_CHECK_ARG(a, "%s: null arguments", what);
     VRD_CHECK_ARG(a->n_layers >= 1 && a->n_layers <= 4, "%s: 1 .. 4 layers (got %d)", what, a->n_layers);
-    VRD_CHECK_ARG(a->B > 0 && a->Q >= 1 && a->Q <= 16 && a->K1 >= 2 && a->T >= 1 && a->G >= 1, "%s: bad sizes", what);
+    VRD_CHECK_ARG(a->B > 0 && a->Q >= 1 && a->Q <= 64 && a->K1 >= 2 && a->T >= 1 && a->G >= 1, "%s: bad sizes", what);
     for (int l = 0; l < a->n_layers; ++l) VRD_CHECK_ARG(a->logits[l] && a->masks[l], "%s: null prediction pointer (layer %d)", what, l);
     VRD_CHECK_ARG(a->out_valid && a->tgt_ids && a->tgt_masks && a->owner, "%s: null ground-truth pointer", what);
     VRD_CHECK_ARG(!a->segs || (a->scale_range > 0.f && a->scale_range <= 1.0f), "%s: scale_range must be in (0, 1]", what);
@@ -275,7 +278,8 @@ int vrd_criterion_costs(const vrd_criterion_args* a, float* cost, void* stream) 
     VRD_CHECK_ARG(cost, "vrd_criterion_costs: null output");
     hipStream_t s = static_cast<hipStream_t>(stream);
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 0.0);
-    hipLaunchKernelGGL(criterion_costs_kernel, dim3(a->G, a->n_layers), dim3(64 * a->Q), 0, s, *a, cost);
+    const int waves = a->Q < COST_WAVES ? a->Q : COST_WAVES;
+    hipLaunchKernelGGL(criterion_costs_kernel, dim3(a->G, a->n_layers, (a->Q + COST_WAVES - 1) / COST_WAVES), dim3(64 * waves), 0, s, *a, cost);
     VRD_LAUNCH_CHECK();
     return 0;
 }

@@ -834,6 +834,45 @@ __global__ __launch_bounds__(256) void mask_head_kernel(const float* __restrict_
     }
 }
 
+// More than MH_QMAX queries (up to MH_QCAP): the queries pass through `es` MH_QMAX at a time against the resident frame tile.
+// Every output is the fmaf chain of mask_head_kernel over c = 0..255, so a query gets the same bits whichever kernel runs it.
+// (es stays 16 rows: 64 would not fit the static LDS next to fs, and would halve the residency of the small kernel.)
+constexpr int MH_QCAP = 64;
+
+__global__ __launch_bounds__(256) void mask_head_groups_kernel(const float* __restrict__ emb, int64_t ld_emb,
+                                                               const float* __restrict__ feat, int64_t ld_feat,
+                                                               const uint8_t* __restrict__ out_mask, int Q, int T, float fill,
+                                                               float* __restrict__ seg) {
+    __shared__ float fs[MH_TT][MH_D + 1];
+    __shared__ float es[MH_QMAX][MH_D];
+    const int b = blockIdx.y, t0 = blockIdx.x * MH_TT, tid = threadIdx.x;
+    for (int i = tid; i < MH_TT * (MH_D / 4); i += 256) {
+        const int r = i / (MH_D / 4), c = (i % (MH_D / 4)) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t0 + r < T) v = ld4(feat + ((int64_t)b * T + t0 + r) * ld_feat + c);
+        fs[r][c] = v.x; fs[r][c + 1] = v.y; fs[r][c + 2] = v.z; fs[r][c + 3] = v.w;
+    }
+    const int tt = tid & 31, qg = tid >> 5;
+    const bool live = t0 + tt < T;                  // (no early return: every thread meets the barriers below)
+    const bool on = live && out_mask[(int64_t)b * T + t0 + tt] != 0;
+    for (int q0 = 0; q0 < Q; q0 += MH_QMAX) {
+        const int nq = min(MH_QMAX, Q - q0);
+        __syncthreads();                            // the previous group's es has been read (and, first time, fs is written)
+        for (int i = tid; i < nq * (MH_D / 4); i += 256) {
+            const int r = i / (MH_D / 4), c = (i % (MH_D / 4)) * 4;
+            st4(&es[r][c], ld4(emb + ((int64_t)b * Q + q0 + r) * ld_emb + c));
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int q = qg; q < nq; q += 8) {
+            float s = 0.f;
+#pragma unroll 8
+            for (int c = 0; c < MH_D; ++c) s = fmaf(es[q][c], fs[tt][c], s);
+            seg[((int64_t)b * Q + q0 + q) * T + t0 + tt] = on ? s : fill;
+        }
+    }
+}
+
 inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
 
 // ---- padding map: 32-row blocks dealt into segments of seg_len list entries (the last one may be shorter), inside a
@@ -1174,12 +1213,16 @@ int vrd_mask_head(const float* emb, int64_t ld_emb, const float* feat, int64_t l
                   int Q, int T, int Dp, float fill, float* seg, void* stream) {
     VRD_CHECK_ARG(emb && feat && out_mask && seg, "vrd_mask_head: null pointer");
     VRD_CHECK_ARG(Dp == MH_D, "vrd_mask_head: mask dim must be %d (got %d)", MH_D, Dp);
-    VRD_CHECK_ARG(Q >= 1 && Q <= MH_QMAX, "vrd_mask_head: num queries must be 1..%d (got %d)", MH_QMAX, Q);
+    VRD_CHECK_ARG(Q >= 1 && Q <= MH_QCAP, "vrd_mask_head: num queries must be 1..%d (got %d)", MH_QCAP, Q);
     VRD_CHECK_ARG(B > 0 && B <= 65535 && T > 0, "vrd_mask_head: bad B/T");
     VRD_CHECK_ARG(ld_emb % 4 == 0 && ld_feat % 4 == 0 && aligned16(emb) && aligned16(feat), "vrd_mask_head: bad layout");
     hipStream_t s = static_cast<hipStream_t>(stream);
     vrd::ProfScope prof(VRD_K_MASK_HEAD, s, 2.0 * B * (double)Q * T * Dp, 4.0 * B * ((double)T * Dp + (double)Q * Dp + (double)Q * T));
-    hipLaunchKernelGGL(mask_head_kernel, dim3((T + MH_TT - 1) / MH_TT, B), dim3(256), 0, s, emb, ld_emb, feat, ld_feat, out_mask, Q, T, fill, seg);
+    const dim3 grid((T + MH_TT - 1) / MH_TT, B);
+    if (Q <= MH_QMAX)
+        hipLaunchKernelGGL(mask_head_kernel, grid, dim3(256), 0, s, emb, ld_emb, feat, ld_feat, out_mask, Q, T, fill, seg);
+    else
+        hipLaunchKernelGGL(mask_head_groups_kernel, grid, dim3(256), 0, s, emb, ld_emb, feat, ld_feat, out_mask, Q, T, fill, seg);
     VRD_LAUNCH_CHECK();
     return 0;
 }

@@ -4,7 +4,8 @@
 //                   linear_sum_assignment once per pair.  Here every pair's (N_i relations x Q queries) block is solved by
 //                   one thread with the O(n^2 m) shortest-augmenting-path form of the Hungarian algorithm (potentials
 //                   u, v; N_i <= Q <= 16), in double precision; only the assignment (one int per relation) leaves the
-//                   device.  The optimum is the one scipy finds whenever it is unique.
+//                   device.  The optimum is the one scipy finds whenever it is unique.  Above 16 queries (to 64) it
+//                   forwards to vrd_assign_wave: the same search with one wave per pair, lane j holding column j.
 //  vrd_ema_update   utils/train_utils.py:21-29 walks the ~520 state-dict tensors with three elementwise launches
 //                   each; here ONE launch updates all of them through a chunk table:
 //                   ema = decay * ema + (1 - decay) * model, each product and the sum rounded to f32 like the
@@ -81,6 +82,89 @@ __global__ __launch_bounds__(64) void assign_kernel(const float* __restrict__ co
         if (match[j]) query_of[r0 + match[j] - 1] = j - 1;
 }
 
+// The same algorithm with one WAVE per pair, for up to 64 queries.  Lane j owns column j + 1 (v, minv, way, used, match) and
+// row j + 1 (u, and whether the row is in the alternating tree: the serial form's `u[match[j]] += delta` over used columns
+// touches exactly those rows, the row under assignment -- column 0's -- among them).  Column scan and delta update are one
+// step for all lanes; the argmin is a butterfly over (minv, column) compared lexicographically, so a tie goes to the lowest
+// column like the serial loop's strict `<`.  Every f64 operation is the serial kernel's, in its order: the two agree on
+// u, v, hence on every tie.  The pair's cost block sits in LDS (16 KB), nothing in scratch.
+constexpr int AW_MAX = 64;
+
+__device__ __forceinline__ int wave_bcast_i(int v, int src) { return __shfl(v, src, 64); }
+__device__ __forceinline__ double wave_bcast_d(double v, int src) { return __shfl(v, src, 64); }
+
+__global__ __launch_bounds__(64) void assign_wave_kernel(const float* __restrict__ cost, int64_t ld, const int32_t* __restrict__ first,
+                                                         const int32_t* __restrict__ count, int Q, int32_t* __restrict__ query_of) {
+    __shared__ float cs[AW_MAX][AW_MAX];
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int n = count[p], r0 = first[p];
+    if (n <= 0) return;
+    if (n > Q) {                  // (wave-uniform) no complete assignment: the host routes such pairs to scipy
+        for (int i = lane; i < n; i += 64) query_of[r0 + i] = -1;
+        return;
+    }
+    const bool col = lane < Q;                       // this lane has a column
+    bool bad = false;
+    for (int i = 0; i < n; ++i) {
+        const float c = col ? cost[(int64_t)(r0 + i) * ld + lane] : 0.f;
+        bad |= !(c == c) || c == -INFINITY;
+        cs[i][lane] = c;
+    }
+    __syncthreads();
+    if (__any(bad)) {             // a NaN or a -inf anywhere in the block: unassigned, like scipy's refusal
+        if (lane < n) query_of[r0 + lane] = -1;
+        return;
+    }
+    double u = 0.0, v = 0.0, minv;
+    int match = 0, way = 0;
+    bool used;
+    for (int i = 1; i <= n; ++i) {
+        int j0 = 0;                                  // (uniform) 0 = the virtual column that holds row i
+        minv = 1e300, used = false;
+        bool in_tree = lane == i - 1;                // rows whose u moves with delta
+        for (int step = 0;; ++step) {
+            if (j0) used |= lane == j0 - 1;
+            const int i0 = j0 ? wave_bcast_i(match, j0 - 1) : i;
+            in_tree |= lane == i0 - 1;
+            const double u0 = wave_bcast_d(u, i0 - 1);
+            double key = 1e300;
+            int arg = 0;
+            if (col && !used) {
+                const double cur = (double)cs[i0 - 1][lane] - u0 - v;
+                if (cur < minv) minv = cur, way = j0;
+                if (minv < 1e300) key = minv, arg = lane + 1;
+            }
+#pragma unroll
+            for (int o = 32; o; o >>= 1) {
+                const double k2 = __shfl_xor(key, o, 64);
+                const int a2 = __shfl_xor(arg, o, 64);
+                // a lane without a candidate has arg 0 and key 1e300, above every candidate's key
+                if (a2 && (!arg || k2 < key || (k2 == key && a2 < arg))) key = k2, arg = a2;
+            }
+            // no usable column (all remaining costs +inf), or -- never, with n <= Q -- more steps than columns: unassigned
+            if (arg == 0 || step >= Q) {
+                if (lane < n) query_of[r0 + lane] = -1;
+                return;
+            }
+            const double delta = key;
+            if (in_tree) u += delta;
+            if (col) {
+                if (used) v -= delta;
+                else minv -= delta;
+            }
+            j0 = arg;
+            if (wave_bcast_i(match, j0 - 1) == 0) break;
+        }
+        for (int hop = 0; j0 && hop < Q; ++hop) {    // flip the augmenting path back to column 0 (at most Q columns on it)
+            const int j1 = wave_bcast_i(way, j0 - 1);
+            const int m1 = j1 ? wave_bcast_i(match, j1 - 1) : i;
+            if (lane == j0 - 1) match = m1;
+            j0 = j1;
+        }
+    }
+    if (col && match) query_of[r0 + match - 1] = lane;
+}
+
 constexpr int EMA_CHUNK = 4096;
 __global__ __launch_bounds__(256) void ema_kernel(float* const* __restrict__ ema, const float* const* __restrict__ model,
                                                   const int64_t* __restrict__ numel, const int32_t* __restrict__ chunk_tensor,
@@ -100,10 +184,22 @@ extern "C" {
 
 int vrd_assign(const float* cost, int64_t ld, const int32_t* first, const int32_t* count, int P, int Q, int32_t* query_of, void* stream) {
     VRD_CHECK_ARG(cost && first && count && query_of, "vrd_assign: null pointer");
-    VRD_CHECK_ARG(P > 0 && Q >= 1 && Q <= AS_MAX && ld >= Q, "vrd_assign: Q must be 1..%d (got %d)", AS_MAX, Q);
+    if (Q > AS_MAX) return vrd_assign_wave(cost, ld, first, count, P, Q, query_of, stream);
+    VRD_CHECK_ARG(P > 0 && Q >= 1 && Q <= AS_MAX && ld >= Q, "vrd_assign: Q must be 1..%d (got %d)", AW_MAX, Q);
     hipStream_t s = static_cast<hipStream_t>(stream);
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 0.0);
     hipLaunchKernelGGL(assign_kernel, dim3((P + 63) / 64), dim3(64), 0, s, cost, ld, first, count, P, Q, query_of);
+    VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+int vrd_assign_wave(const float* cost, int64_t ld, const int32_t* first, const int32_t* count, int P, int Q, int32_t* query_of,
+                    void* stream) {
+    VRD_CHECK_ARG(cost && first && count && query_of, "vrd_assign_wave: null pointer");
+    VRD_CHECK_ARG(P > 0 && Q >= 1 && Q <= AW_MAX && ld >= Q, "vrd_assign_wave: Q must be 1..%d (got %d)", AW_MAX, Q);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 0.0);
+    hipLaunchKernelGGL(assign_wave_kernel, dim3(P), dim3(64), 0, s, cost, ld, first, count, Q, query_of);
     VRD_LAUNCH_CHECK();
     return 0;
 }

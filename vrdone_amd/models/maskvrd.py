@@ -24,6 +24,8 @@ from .predictor import MaskedTransformerPredictor
 
 
 class MaskVRD(nn.Module):
+    MAX_QUERIES = 64          # predictor.num_queries: 1..64 (mask head, device matcher and criterion kernels)
+
     def __init__(self, config, device):
         super().__init__()
         self.visual_dim = config['visual_dim']
@@ -78,6 +80,11 @@ class MaskVRD(nn.Module):
         self.neck = FPN1D_Fuse(in_channels=[self.embd_dim] * n_levels, out_channel=config['fpn_dim'],
                                scale_factor=self.scale_factor, start_level=config['fpn_start_level'],
                                with_ln=config['fpn_with_ln'], norm_first=config['fpn_norm_first'])
+        # one wave holds a pair's queries in the device matcher (vrd_assign_wave), 64 rows of mask embeddings pass the mask head
+        # (vrd_mask_head): the reference has no cap, this code base's is 64
+        n_queries = config['predictor']['num_queries']
+        if not 1 <= int(n_queries) <= self.MAX_QUERIES:
+            raise ValueError(f"predictor.num_queries must be 1..{self.MAX_QUERIES} (got {n_queries})")
         self.predictor = MaskedTransformerPredictor(**config['predictor'])
         self.deep_supervision = config['predictor']['deep_supervision']
         self.device = device
@@ -458,7 +465,7 @@ class MaskVRD(nn.Module):
         # the fused criterion keeps one int per (pair, query) row in its workgroup's 48 KiB of LDS (vrd_criterion_losses): batches
         # beyond ~12 k rows take the tensor form below, like anything else it does not cover
         fits = pred_logits.shape[0] * Q * 4 + 256 <= 48 * 1024
-        if (self.device_matching and self.device_criterion and pred_logits.is_cuda and sizes and 0 < max(sizes) <= Q <= 16 and fits
+        if (self.device_matching and self.device_criterion and pred_logits.is_cuda and sizes and 0 < max(sizes) <= Q <= 64 and fits
                 and 'bipartite_match' not in self.__dict__):          # (tests pin the matching by replacing the method)
             loss_dict = self._criterion_on_device(pred_logits, pred_masks, out_mask, aux, sizes, gt_preds, gt_masks, gt_segs)
         else:
@@ -556,7 +563,7 @@ class MaskVRD(nn.Module):
                 self.cost_factor['cost_dice'] * c_dice)                             # (sum N_i, Q)
         Q = cost.shape[1]
         indices = []
-        if cost.is_cuda and sizes and 0 < max(sizes) <= Q <= 16 and self.device_matching:
+        if cost.is_cuda and sizes and 0 < max(sizes) <= Q <= 64 and self.device_matching:
             # every pair's assignment on the device (vrd_assign); one small copy brings the result back in the reference's
             # format: per pair (query indices ascending, the relation each one got)
             q_of = _ops().assign(cost.contiguous(), sizes).cpu().long()

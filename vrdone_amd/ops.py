@@ -1254,17 +1254,19 @@ def assign_tables(sizes, dev):
     return torch.tensor(first, dtype=torch.int32, device=dev), torch.tensor(sizes, dtype=torch.int32, device=dev)
 
 
-def assign(cost, sizes, tables=None):
+def assign(cost, sizes, tables=None, wave=False):
     """Minimum-cost assignment of every pair's relations to its queries on the device (vrd_assign): cost (sum N, Q) f32,
-    rows grouped pair by pair, sizes = [N_p] (each <= Q <= 16); tables = assign_tables(sizes, device) when the caller
-    assigns several cost matrices of the same batch.  Returns the query of every relation, (sum N,) int32."""
+    rows grouped pair by pair, sizes = [N_p] (each <= Q <= 64); tables = assign_tables(sizes, device) when the caller
+    assigns several cost matrices of the same batch.  Returns the query of every relation, (sum N,) int32.
+    Up to 16 queries one thread solves a pair, above that one wave (vrd_assign_wave); wave=True asks for the wave form at
+    any Q -- the two follow one pivoting rule and agree on every input."""
     assert cost.is_cuda and cost.dtype == torch.float32 and cost.dim() == 2 and cost.stride(1) == 1
     G, Q = cost.shape
-    assert sum(sizes) == G and max(sizes) <= Q <= 16
+    assert sum(sizes) == G and max(sizes) <= Q <= 64
     first_d, count_d = tables if tables is not None else assign_tables(sizes, cost.device)
     out = torch.full((G,), -1, dtype=torch.int32, device=cost.device)
-    _hip.check(lib.vrd_assign(cost.data_ptr(), cost.stride(0), first_d.data_ptr(), count_d.data_ptr(), len(sizes), Q,
-                              out.data_ptr(), _stream()), "vrd_assign")
+    fn, name = (lib.vrd_assign_wave, "vrd_assign_wave") if wave else (lib.vrd_assign, "vrd_assign")
+    _hip.check(fn(cost.data_ptr(), cost.stride(0), first_d.data_ptr(), count_d.data_ptr(), len(sizes), Q, out.data_ptr(), _stream()), name)
     return out
 
 
