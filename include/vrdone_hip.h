@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VRD_ABI_VERSION 36
+#define VRD_ABI_VERSION 37
 
 /* `flags` of the parameter-gradient entry points (vrd_gemm_wgrad, vrd_gemm_wgrad_x3, vrd_colsum, vrd_dwconv_wgrad,
  * vrd_layernorm_bwd).  VRD_DETERMINISTIC: the result is a function of the inputs and the shapes alone -- the same bits
@@ -684,6 +684,20 @@ int vrd_gemm_wgrad(const float* G, int64_t ldg, const float* X, int64_t ldx, con
 int vrd_gemm_wgrad_x3(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
                       int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, const float* g_scale,
                       void* stream, int flags);
+
+/* The plan vrd_gemm_wgrad_x3 takes for these arguments -- the ones its choice reads: pointers (alignment only), leading
+ * dimensions, sizes, whether there is a dbias, the scratch and the flags; the call itself asks the same function.  Host code only,
+ * nothing is launched.  plan[0..6]: form (VRD_WGRAD_WAVE: a wave per 64 x 64 tile of dW; VRD_WGRAD_LDS128 / VRD_WGRAD_LDS256: a
+ * workgroup per 128 x 128 / 256 x 256 tile staged through LDS), vec (LDS forms: float4 loads), tiles (grid.x), chunk (rows per
+ * chunk; wave form: per wave, four waves to a workgroup), chunks (grid.y), tile_partials (the chunks' tiles go through the
+ * scratch and a second launch sums them in chunk order; else `+=` with one chunk, float atomics with several), total_floats (the
+ * scratch the deterministic mode asks for). */
+#define VRD_WGRAD_WAVE 0
+#define VRD_WGRAD_LDS128 1
+#define VRD_WGRAD_LDS256 2
+#define VRD_WGRAD_PLAN_INTS 7
+int vrd_gemm_wgrad_x3_plan(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int N, int Cin, int taps, const float* dW,
+                           int has_bias, const float* scratch, int64_t scratch_floats, int flags, int64_t* plan);
 
 /* scale[0] = 2^e, scale[1] = 2^-e with e such that max |x| * 2^e lies in [2^13, 2^14) over the (rows x cols) matrix x (e = 0 for
  * an all-zero or non-finite matrix; |e| <= 100): the power-of-two factor that puts a tensor of unknown range -- a gradient -- into

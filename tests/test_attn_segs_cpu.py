@@ -1,5 +1,5 @@
 """Global attention over a ragged row space in one call (vrd_attention_pair_segs) without a GPU: the entry is declared, exported
-and bound at ABI 36, its host-side argument checks refuse by name, and ragged.attention takes the route only when it is switched
+and bound at ABI 37, its host-side argument checks refuse by name, and ragged.attention takes the route only when it is switched
 on (ragged.ATTN_SEGS / VRDONE_ROWS_ATTN_SEGS=1), for pair-row operands, in runs of 32 row groups."""
 import ctypes
 import os
@@ -15,7 +15,7 @@ NAME = "vrd_attention_pair_segs"
 def test_entry_is_declared_exported_and_bound():
     from vrdone_amd import _hip
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "vrdone_hip.h")).read(), flags=re.S)
-    assert "#define VRD_ABI_VERSION 36" in header and _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
+    assert "#define VRD_ABI_VERSION 37" in header and _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
     proto = re.search(r"int vrd_attention_pair_segs\(([^)]*)\);", header).group(1)
     names = [a.split()[-1].lstrip("*") for a in proto.split(",")]
     assert names == ["q", "ldq", "k", "v", "ldkv", "kv_mask", "q_mask", "qsegs", "ksegs", "n_head", "head_dim", "out", "ldo", "out_pair",

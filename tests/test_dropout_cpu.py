@@ -79,7 +79,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for name in NEW:
         assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
         assert name in _hip._SIGNATURES and hasattr(_hip.lib, name), name
-    assert re.search(r"#define VRD_ABI_VERSION 36\b", header) and _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
+    assert re.search(r"#define VRD_ABI_VERSION 37\b", header) and _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
     # the entry points these mirror keep their prototypes
     assert len(_hip._SIGNATURES["vrd_local_attn"][1]) == 15 and len(_hip._SIGNATURES["vrd_local_attn_bwd"][1]) == 19
     assert len(_hip._SIGNATURES["vrd_local_attn_drop"][1]) == 18 and len(_hip._SIGNATURES["vrd_local_attn_drop_bwd"][1]) == 23

@@ -54,10 +54,10 @@ def test_environment_variable_selects_f16x1_in_a_fresh_interpreter():
 
 def test_abi_version_and_products_field():
     from vrdone_amd import _hip
-    assert _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
+    assert _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
     assert _hip.GemmArgs._fields_[-1] == ("products", ctypes.c_int32)
     header = open(os.path.join(REPO, "include", "vrdone_hip.h")).read()
-    assert "#define VRD_ABI_VERSION 36" in header
+    assert "#define VRD_ABI_VERSION 37" in header
     body = re.search(r"typedef struct \{([^}]*)\} vrd_gemm_args", header).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     assert body.strip().rstrip(";").split()[-1] == "products"

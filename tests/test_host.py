@@ -78,7 +78,7 @@ def test_c_abi_exports_every_declared_symbol():
     header = open(os.path.join(REPO, "include", "vrdone_hip.h")).read()
     declared = set(re.findall(r"\b(vrd_[a-z0-9_]+)\s*\(", header))
     declared -= {"vrd_act", "vrd_kernel_id"}
-    assert len(declared) >= 14
+    assert len(declared) >= 14 and {"vrd_gemm_family", "vrd_gemm_wgrad_x3_plan"} <= declared      # (the two plan queries)
     path = os.path.join(REPO, "vrdone_amd", "csrc", "libvrdone_hip.so")
     assert os.path.exists(path), "build the extension first (python -c 'import __graft_entry__ as g; g.build()')"
     lib = ctypes.CDLL(path)
@@ -98,6 +98,11 @@ def test_ctypes_signatures_match_the_header_prototypes():
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     protos = dict(re.findall(r"\b(?:int|const char\*|void)\s+(vrd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header))
     assert set(_hip._SIGNATURES) <= set(protos), sorted(set(_hip._SIGNATURES) - set(protos))
+    # the weight-gradient plan query takes the arguments of the call whose plan it reports, less what the plan does not read
+    # (row_mask, T, dbias as a flag, g_scale, stream), plus the plan array
+    call, query = _hip._SIGNATURES["vrd_gemm_wgrad_x3"][1], _hip._SIGNATURES["vrd_gemm_wgrad_x3_plan"][1]
+    assert len(query) == len(call) - 3 and query[-1] == ctypes.POINTER(ctypes.c_int64)
+    assert int(re.search(r"#define VRD_WGRAD_PLAN_INTS (\d+)", header).group(1)) == _hip.WGRAD_PLAN_INTS
 
     def kind(param):
         param = " ".join(param.split())

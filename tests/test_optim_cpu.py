@@ -118,7 +118,7 @@ def test_hyper_parameter_row_is_torchs_scalars():
 def test_new_entry_points_are_declared_bound_and_exported():
     from vrdone_amd import _hip
     header = open(os.path.join(REPO, "include", "vrdone_hip.h")).read()
-    assert "#define VRD_ABI_VERSION 36" in header and _hip.ABI_VERSION == 36        # added, not changed: the ABI number stays
+    assert "#define VRD_ABI_VERSION 37" in header and _hip.ABI_VERSION == 37        # (37: vrd_gemm_wgrad_x3_plan came with a bump; these entry points had come without one)
     assert "#define VRD_ADAMW_GROUP_FLOATS 8" in header
     declared = set(re.findall(r"\bint\s+(vrd_[a-z0-9_]+)\s*\(", header))
     lib = ctypes.CDLL(os.path.join(REPO, "vrdone_amd", "csrc", "libvrdone_hip.so"))

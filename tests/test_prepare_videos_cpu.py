@@ -48,8 +48,8 @@ def test_struct_mirror_has_the_header_layout():
 
 def test_abi_version_is_unchanged():
     from vrdone_amd import _hip
-    assert _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
-    assert re.search(r"#define\s+VRD_ABI_VERSION\s+36\b", open(os.path.join(REPO, "include", "vrdone_hip.h")).read())
+    assert _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
+    assert re.search(r"#define\s+VRD_ABI_VERSION\s+37\b", open(os.path.join(REPO, "include", "vrdone_hip.h")).read())
 
 
 def test_null_struct_is_refused_by_name():

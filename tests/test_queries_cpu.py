@@ -46,8 +46,8 @@ def test_assign_wave_is_declared_exported_and_bound():
     assert _hip._SIGNATURES["vrd_assign_wave"] == _hip._SIGNATURES["vrd_assign"]
     lib = ctypes.CDLL(os.path.join(REPO, "vrdone_amd", "csrc", "libvrdone_hip.so"))
     assert hasattr(lib, "vrd_assign_wave") and hasattr(_hip.lib, "vrd_assign_wave")
-    assert _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
-    assert re.search(r"#define\s+VRD_ABI_VERSION\s+36\b", header)
+    assert _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
+    assert re.search(r"#define\s+VRD_ABI_VERSION\s+37\b", header)
     assert "`vrd_assign_wave`" in open(os.path.join(REPO, "INTEGRATION.md")).read()
 
 

@@ -22,7 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_abi_declares_exports_and_binds_the_two_entry_points():
     from vrdone_amd import _hip
     header = open(os.path.join(REPO, "include", "vrdone_hip.h")).read()
-    assert re.search(r"#define VRD_ABI_VERSION 36\b", header) and _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
+    assert re.search(r"#define VRD_ABI_VERSION 37\b", header) and _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
     assert len(_hip.KERNEL_NAMES) == 14
     for name, struct in (("vrd_relation_viou", "vrd_viou_args"), ("vrd_match_relations", "vrd_match_args")):
         assert re.search(r"int %s\(const %s\* a, void\* stream\);" % (name, struct), header), name

@@ -25,8 +25,8 @@ def test_declared_exported_and_bound():
 
 def test_abi_number_stays():
     from vrdone_amd import _hip
-    assert _hip.ABI_VERSION == 36 and _hip.lib.vrd_abi_version() == 36
-    assert re.search(r"#define\s+VRD_ABI_VERSION\s+36\b", open(HEADER).read())
+    assert _hip.ABI_VERSION == 37 and _hip.lib.vrd_abi_version() == 37
+    assert re.search(r"#define\s+VRD_ABI_VERSION\s+37\b", open(HEADER).read())
 
 
 def test_struct_is_bound_field_for_field():

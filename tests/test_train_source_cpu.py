@@ -192,6 +192,6 @@ def test_gather_train_binding_matches_the_header():
     names = [part.strip().split()[-1].lstrip("*") for decl in body.split(";") if decl.strip() for part in decl.split(",")]
     assert names == [f[0] for f in _hip.GatherTrainArgs._fields_]
     assert "vrd_gather_train" in _hip._SIGNATURES and hasattr(_hip.lib, "vrd_gather_train")
-    assert "#define VRD_ABI_VERSION 36" in header and _hip.ABI_VERSION == 36
+    assert "#define VRD_ABI_VERSION 37" in header and _hip.ABI_VERSION == 37
     a = _hip.GatherTrainArgs()
     assert _hip.lib.vrd_gather_train(a, None) != 0 and b"vrd_gather_train" in _hip.lib.vrd_last_error()

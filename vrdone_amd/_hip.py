@@ -246,6 +246,8 @@ _SIGNATURES = {
                                  c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
     "vrd_gemm_wgrad_x3": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                     c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_int]),
+    "vrd_gemm_wgrad_x3_plan": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
+                                         c_f32p, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     "vrd_scratch_required": (C.c_int, [C.POINTER(C.c_int64)]),
     "vrd_absmax_scale": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, C.c_void_p]),
     "vrd_dwconv_wgrad": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p, C.c_int64,
@@ -294,7 +296,9 @@ _SIGNATURES = {
                                   C.c_void_p]),
 }
 
-ABI_VERSION = 36
+ABI_VERSION = 37
+WGRAD_WAVE, WGRAD_LDS128, WGRAD_LDS256 = 0, 1, 2      # VRD_WGRAD_*: plan[0] of vrd_gemm_wgrad_x3_plan
+WGRAD_PLAN_INTS = 7                                   # (form, vec, tiles, chunk, chunks, tile_partials, total_floats)
 
 # `flags` of the parameter-gradient entry points (include/vrdone_hip.h): bit-reproducible sums, no float atomics; such a call
 # fails with ERR_SCRATCH (before any launch) when its scratch is short, and lib.vrd_scratch_required() says how many floats it needs

@@ -803,6 +803,25 @@ int vrd_gemm_wgrad(const float* G, int64_t ldg, const float* X, int64_t ldx, con
     return plan.tile_partials ? launch_wgrad_reduce(dst, plan.chunks, NK, dW, s) : 0;
 }
 
+// The plan vrd_gemm_wgrad_x3 takes for these arguments (plan_wgrad_x3, the function the call itself asks), as numbers: host code only
+int vrd_gemm_wgrad_x3_plan(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int N, int Cin, int taps, const float* dW,
+                           int has_bias, const float* scratch, int64_t scratch_floats, int flags, int64_t* plan) {
+    VRD_CHECK_ARG(G && X && dW && plan, "vrd_gemm_wgrad_x3_plan: null pointer");
+    VRD_CHECK_ARG(M > 0 && N > 0 && Cin > 0 && (taps == 1 || taps == 3), "vrd_gemm_wgrad_x3_plan: bad sizes M=%lld N=%d Cin=%d taps=%d", (long long)M, N, Cin, taps);
+    VRD_CHECK_ARG(ldg >= N && ldx >= Cin, "vrd_gemm_wgrad_x3_plan: leading dimension too small");
+    VRD_CHECK_FLAGS("vrd_gemm_wgrad_x3_plan");
+    WgradPlan p;
+    if (int rc = plan_wgrad_x3(p, G, ldg, X, ldx, M, N, Cin, taps, dW, has_bias != 0, scratch, scratch_floats, (flags & VRD_DETERMINISTIC) != 0)) return rc;
+    plan[0] = p.form == WG_LDS256 ? VRD_WGRAD_LDS256 : p.form == WG_LDS128 ? VRD_WGRAD_LDS128 : VRD_WGRAD_WAVE;
+    plan[1] = p.vec ? 1 : 0;
+    plan[2] = p.tiles;
+    plan[3] = p.chunk;
+    plan[4] = p.chunks;
+    plan[5] = p.tile_partials ? 1 : 0;
+    plan[6] = p.total_floats;
+    return 0;
+}
+
 int vrd_gemm_wgrad_x3(const float* G, int64_t ldg, const float* X, int64_t ldx, const uint8_t* row_mask, int64_t M, int N, int Cin,
                       int taps, int T, float* dW, float* dbias, float* scratch, int64_t scratch_floats, const float* g_scale,
                       void* stream, int flags) {

@@ -886,18 +886,25 @@ def conv_gemm(x, weight, bias=None, *, act=ACT_NONE, row_mask=None, scale=None, 
     return result
 
 
-def conv_dgrad(dy, weight, *, row_mask=None, a_scale=None, fmt=None):
+def dgrad_args(dy, weight, *, row_mask=None, a_scale=None, fmt=None, out=None):
+    """(a, dx): the vrd_gemm_args of conv_dgrad(dy, weight, ...) and the tensor its launch will have written (`out`, or a new
+    one).  Nothing is launched (as gemm_args)."""
+    N, Cin, k = weight.shape
+    assert (N * k) % 32 == 0 and not isinstance(dy, Pair)
+    wt = split_conv_weight_dgrad(weight, fmt)
+    a, dx = _gemm_struct(dy, Cin, N, k, None, wt, row_mask=row_mask, out=out)
+    if wt.fmt == _hip.PAIR_F16:      # dy is a gradient: its f16 planes need its own power-of-two factor
+        assert a_scale is not None
+        a.a_scale = a_scale.data_ptr()
+    return a, dx
+
+
+def conv_dgrad(dy, weight, *, row_mask=None, a_scale=None, fmt=None, out=None):
     """The conv's input gradient as a GEMM on the parameter's transposed operand (split_conv_weight_dgrad, format `fmt`): the
     weight (N, Cin, k) acts as the (Cin, N, k) tap-flipped conv on the f32 rows of the gradient dy (N channels).  Split-precision
     only (autograd.Linear checks).  a_scale: in the f16 format the rows of dy are split at the power-of-two factor of
     grad_scale(dy) (vrd_gemm_args.a_scale)."""
-    N, Cin, k = weight.shape
-    assert (N * k) % 32 == 0 and not isinstance(dy, Pair)
-    wt = split_conv_weight_dgrad(weight, fmt)
-    a, dx = _gemm_struct(dy, Cin, N, k, None, wt, row_mask=row_mask)
-    if wt.fmt == _hip.PAIR_F16:      # dy is a gradient: its f16 planes need its own power-of-two factor
-        assert a_scale is not None
-        a.a_scale = a_scale.data_ptr()
+    a, dx = dgrad_args(dy, weight, row_mask=row_mask, a_scale=a_scale, fmt=fmt, out=out)
     launch_gemm(a)
     return dx
 
