@@ -88,7 +88,7 @@ const char* vrd_last_error(void);
  * documented safe bound (4094 decodes exactly).  Every kernel that WRITES pair rows in this format, or splits f32 rows into
  * such planes while staging, therefore reports: it ORs a tag naming its family into one 32-bit flag word per device --
  *    1  boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs, vrd_gather_train
- *    2  vrd_layernorm, vrd_conv_ln, vrd_dwconv_ln_multi (its pair-row output sets only)
+ *    2  vrd_layernorm, vrd_layernorm_pos, vrd_position_rows, vrd_conv_ln, vrd_dwconv_ln_multi (its pair-row output sets only)
  *    4  vrd_dwconv_ln (its pair-row output sets only; f32 output sets of the same call do not count)
  *    8  pair-row outputs of vrd_gemm / vrd_gemm_batch (every kernel and epilogue of the family)
  *   16  f32 rows split while staged: A of vrd_gemm / vrd_gemm_batch (the value times a_scale[0] where a_scale is given),
@@ -372,6 +372,26 @@ typedef struct {
     int32_t T[VRD_MAX_SEGS];
     int64_t row[VRD_MAX_SEGS];
 } vrd_row_segs;
+
+/* ---- absolute position rows from per-sequence tables (models/backbones.py:180-196 of the reference) ----
+ * The position row of a frame depends on the length its pair is padded to in the REFERENCE (the table is re-interpolated to that
+ * length from max_len on), not on the length it is computed at here: pos_table (pos_rows x C, leading dimension ld_pos) holds the
+ * tables of the call's reference lengths one behind the other, pos_first[s] (device memory, int32) the first table row of
+ * sequence s, mask one byte per row.  The rows are the groups of `segs` (host memory; sequences counted through the groups in
+ * order; rows between or behind the groups are neither read nor written), or, segs == NULL, rows / T sequences of T rows.  For
+ * sequence s, frame t, row r:
+ *     vrd_layernorm_pos:  y[r,:] = [relu](LN(x[r,:]) * gamma + beta) + (mask[r] ? pos_table[pos_first[s] + t, :] : 0)
+ *     vrd_position_rows:  y[r,:] = mask[r] ? pos_table[pos_first[s] + t, :] : 0
+ * vrd_layernorm_pos forms the sum the way vrd_layernorm forms its post_add sum: the result has the bits of vrd_layernorm fed
+ * the materialised rows.  y: f32 rows or pair rows (out_pair; VRD_PAIR_F16 reports under tag 2, like vrd_layernorm).  C in
+ * {256, 512}; a group, and the whole launch without groups, holds fewer than 2^31 rows; a table row outside [0, pos_rows) reads
+ * as zeros. */
+int vrd_layernorm_pos(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int C, const float* gamma, const float* beta,
+                      int relu, const float* pos_table, int64_t ld_pos, int64_t pos_rows, const int32_t* pos_first, const uint8_t* mask,
+                      const vrd_row_segs* segs, int T, int out_pair /* enum vrd_pair_format */, void* stream);
+int vrd_position_rows(float* y, int64_t ldy, int64_t rows, int C, const float* pos_table, int64_t ld_pos, int64_t pos_rows,
+                      const int32_t* pos_first, const uint8_t* mask, const vrd_row_segs* segs, int T,
+                      int out_pair /* enum vrd_pair_format */, void* stream);
 
 /* ---- depthwise conv (+ nearest-upsample add) * mask -> LayerNorm, fused -----------------
  * for o in [0, n_out): y_o[b,t',:] = LN_o( mask_out[b,t'] * (bias_o + sum_k w_o[c,g,k] *

@@ -213,6 +213,11 @@ _SIGNATURES = {
     "vrd_conv_ln": (C.c_int, [C.POINTER(ConvLnArgs), C.c_void_p]),
     "vrd_layernorm": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int,
                                 c_f32p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    # position rows from per-sequence tables (pos_table, ld_pos, pos_rows, pos_first, mask, segs or NULL, T)
+    "vrd_layernorm_pos": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, c_f32p, C.c_int,
+                                    c_f32p, C.c_int64, C.c_int64, c_i32p, c_u8p, C.POINTER(RowSegs), C.c_int, C.c_int, C.c_void_p]),
+    "vrd_position_rows": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, C.c_int64, C.c_int64, c_i32p, c_u8p,
+                                    C.POINTER(RowSegs), C.c_int, C.c_int, C.c_void_p]),
     "vrd_dwconv_ln": (C.c_int, [C.POINTER(DwconvLnArgs), C.c_void_p]),
     "vrd_dwconv_ln_multi": (C.c_int, [C.POINTER(DwconvLnMultiArgs), C.c_void_p]),
     "vrd_local_attn": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_u8p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -356,7 +361,7 @@ def check(rc, what):
 # tags of the f16 operand-range flag word (vrd_f16_range_flag; enum RangeTag of csrc/vrd_common.h): the entry points that OR each
 # bit.  A value x reports from |x| >= 4095 on (|x * 2^4| >= 65520 rounds to hi = inf); |x| < 4094 is the documented safe bound.
 RANGE_TAGS = {1: "boundary tensors (vrd_bct_to_btc / vrd_pack_pairs / vrd_gather_pairs / vrd_gather_train)",
-              2: "vrd_layernorm / vrd_conv_ln / vrd_dwconv_ln_multi outputs",
+              2: "vrd_layernorm / vrd_layernorm_pos / vrd_position_rows / vrd_conv_ln / vrd_dwconv_ln_multi outputs",
               4: "vrd_dwconv_ln outputs",
               8: "pair-row outputs of vrd_gemm / vrd_gemm_batch",
               16: "f32 rows split while staged (vrd_gemm / vrd_gemm_batch, vrd_attention_rows, vrd_attention_bwd)",

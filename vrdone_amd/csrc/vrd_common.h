@@ -217,7 +217,7 @@ __device__ __forceinline__ mfma_acc16_t mfma16(f16x8_t a, f16x8_t b, mfma_acc16_
 // host mirror reads the word with a call's results and repeats the call in the f32 mode.
 enum RangeTag : unsigned {
     RANGE_INPUT = 1u,        // boundary tensors: vrd_bct_to_btc, vrd_pack_pairs, vrd_gather_pairs, vrd_gather_train (vrd_assemble_pairs writes f32 rows only)
-    RANGE_LAYERNORM = 2u,    // vrd_layernorm, vrd_conv_ln, vrd_dwconv_ln_multi
+    RANGE_LAYERNORM = 2u,    // vrd_layernorm (+ _pos, vrd_position_rows), vrd_conv_ln, vrd_dwconv_ln_multi
     RANGE_DWCONV_LN = 4u,    // vrd_dwconv_ln
     RANGE_GEMM_OUT = 8u,     // pair-row outputs of vrd_gemm (c_pair)
     RANGE_GEMM_IN = 16u,     // f32 rows split inside a GEMM / attention kernel while they are staged (vrd_gemm, vrd_attention_rows / _bwd)

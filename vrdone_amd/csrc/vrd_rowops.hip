@@ -245,12 +245,53 @@ __device__ __forceinline__ void ln_rows(float4 (&v)[NV], const float* gamma, con
     }
 }
 
-template <int NV>
+// Absolute position rows whose table belongs to the SEQUENCE (vrd_layernorm_pos, vrd_position_rows): the launch's rows are `count`
+// groups of sequences (group g: T[g] frames each from row row[g] on, its first sequence the seq0[g]-th of the launch; a batch of B
+// x T rows is one group); the waves walk slots 0 .. slot0[count] -- the groups' rows back to back -- so rows between and behind
+// the groups are never touched.  Sequence s, frame t receives table[first[s] + t] where mask[row] is set, nothing elsewhere.
+// Passed by value as a kernel argument (scalar loads).
+struct PosRows {
+    const float* table;
+    int64_t ld, table_rows;
+    const int32_t* first;
+    const uint8_t* mask;
+    int count;
+    int T[VRD_MAX_SEGS], seq0[VRD_MAX_SEGS];
+    int64_t row[VRD_MAX_SEGS], slot0[VRD_MAX_SEGS + 1];
+};
+
+// slot -> (row of the matrices, sequence of the launch, frame); wave-uniform arithmetic (a group holds fewer than 2^31 rows)
+__device__ __forceinline__ void pos_locate(const PosRows& p, int64_t slot, int64_t& row, int& s, int& t) {
+    int g = 0;
+    while (g + 1 < p.count && slot >= p.slot0[g + 1]) ++g;
+    const unsigned r = (unsigned)(slot - p.slot0[g]), T = (unsigned)p.T[g];
+    const unsigned b = r / T;
+    row = p.row[g] + r;
+    s = p.seq0[g] + (int)b;
+    t = (int)(r - b * T);
+}
+
+// the lane's four channels from c on of the position row of (row, sequence s, frame t): zeros on a padded frame.  (A table row
+// outside the table -- pos_first is device data the host cannot check -- reads as zeros, never out of bounds.)
+__device__ __forceinline__ float4 pos_row4(const PosRows& p, int64_t row, int s, int t, int c) {
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (vrd::uniform_load(p.mask + row)) {
+        const int64_t pr = (int64_t)vrd::uniform_load(p.first + s) + t;
+        if (pr >= 0 && pr < p.table_rows) a = vrd::gload4(p.table + pr * p.ld + c);
+    }
+    return a;
+}
+
+// POS = PosRows, the one trailing argument of the kernel then (none without: that instantiation's arguments are what they were):
+// `rows` counts the slots of `pos` and the position row takes the place of post_add; the sum is formed the same way, so the result
+// has the bits of the post_add form fed the materialised rows.
+__device__ __forceinline__ const PosRows& pos_of(const PosRows& p) { return p; }
+template <int NV, typename... POS>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                         int64_t ldy, int64_t rows, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int relu,
                                                         const float* __restrict__ post_add, int64_t ld_add, int period,
-                                                        int pair, unsigned* rflag) {
+                                                        int pair, unsigned* rflag, POS... pos_arg) {
     vrd::RangeTrack rt;
     const int lane = threadIdx.x & 63;
     // Waves walk the rows with the stride of the grid (row = wave, wave + waves of the grid, ...) and request their next row before
@@ -261,29 +302,80 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const int64_t stride = (int64_t)gridDim.x * 4;
     if (row >= rows) return;
     float4 v[NV], vn[NV];
+    if constexpr (sizeof...(POS) > 0) {
+        const PosRows& pos = pos_of(pos_arg...);
+        // (`row` walks the slots; at / s / t: the slot's row of x and y, its sequence and frame)
+        int64_t at, at_n = 0;
+        int s, t, s_n = 0, t_n = 0;
+        pos_locate(pos, row, at, s, t);
 #pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = ld4(x + row * ldx + i * 256 + lane * 4);
-    for (;;) {
-        const int64_t nxt = row + stride;
-        if (nxt < rows) {
+        for (int i = 0; i < NV; ++i) v[i] = ld4(x + at * ldx + i * 256 + lane * 4);
+        for (;;) {
+            const int64_t nxt = row + stride;
+            if (nxt < rows) {
+                pos_locate(pos, nxt, at_n, s_n, t_n);
 #pragma unroll
-            for (int i = 0; i < NV; ++i) vn[i] = ld4(x + nxt * ldx + i * 256 + lane * 4);
+                for (int i = 0; i < NV; ++i) vn[i] = ld4(x + at_n * ldx + i * 256 + lane * 4);
+            }
+            ln_rows<NV>(v, gamma, beta, lane, relu != 0);
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[i] = f4add(v[i], pos_row4(pos, at, s, t, i * 256 + lane * 4));
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                if (pair) vrd::store_pair4(y + at * ldy, i * 256 + lane * 4, 256 * NV, v[i], pair, &rt);
+                else st4(y + at * ldy + i * 256 + lane * 4, v[i]);
+            }
+            if (nxt >= rows) break;
+            row = nxt, at = at_n, s = s_n, t = t_n;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[i] = vn[i];
         }
-        ln_rows<NV>(v, gamma, beta, lane, relu != 0);
-        if (post_add) {
-            const float* a = post_add + (row % period) * ld_add;
+    } else {
 #pragma unroll
-            for (int i = 0; i < NV; ++i) v[i] = f4add(v[i], ld4(a + i * 256 + lane * 4));
+        for (int i = 0; i < NV; ++i) v[i] = ld4(x + row * ldx + i * 256 + lane * 4);
+        for (;;) {
+            const int64_t nxt = row + stride;
+            if (nxt < rows) {
+#pragma unroll
+                for (int i = 0; i < NV; ++i) vn[i] = ld4(x + nxt * ldx + i * 256 + lane * 4);
+            }
+            ln_rows<NV>(v, gamma, beta, lane, relu != 0);
+            if (post_add) {
+                const float* a = post_add + (row % period) * ld_add;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) v[i] = f4add(v[i], ld4(a + i * 256 + lane * 4));
+            }
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                if (pair) vrd::store_pair4(y + row * ldy, i * 256 + lane * 4, 256 * NV, v[i], pair, &rt);
+                else st4(y + row * ldy + i * 256 + lane * 4, v[i]);
+            }
+            if (nxt >= rows) break;
+            row = nxt;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[i] = vn[i];
         }
+    }
+    rt.report(rflag, vrd::RANGE_LAYERNORM);
+}
+
+// the masked position rows themselves (vrd_position_rows): a wave per slot of `pos`, slots walked with the grid's stride
+template <int NV>
+__global__ __launch_bounds__(256) void position_rows_kernel(float* __restrict__ y, int64_t ldy, int64_t rows, int pair, unsigned* rflag,
+                                                            PosRows pos) {
+    vrd::RangeTrack rt;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * 4;
+    for (int64_t slot = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); slot < rows; slot += stride) {
+        int64_t at;
+        int s, t;
+        pos_locate(pos, slot, at, s, t);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            if (pair) vrd::store_pair4(y + row * ldy, i * 256 + lane * 4, 256 * NV, v[i], pair, &rt);
-            else st4(y + row * ldy + i * 256 + lane * 4, v[i]);
+            const float4 v = pos_row4(pos, at, s, t, i * 256 + lane * 4);
+            if (pair) vrd::store_pair4(y + at * ldy, i * 256 + lane * 4, 256 * NV, v, pair, &rt);
+            else st4(y + at * ldy + i * 256 + lane * 4, v);
         }
-        if (nxt >= rows) break;
-        row = nxt;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] = vn[i];
     }
     rt.report(rflag, vrd::RANGE_LAYERNORM);
 }
@@ -1036,6 +1128,85 @@ int vrd_layernorm(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t ro
         hipLaunchKernelGGL(layernorm_kernel<1>, grid, dim3(256), 0, s, x, ldx, y, ldy, rows, gamma, beta, relu, post_add, ld_add, add_period, out_pair, rflag);
     else
         hipLaunchKernelGGL(layernorm_kernel<2>, grid, dim3(256), 0, s, x, ldx, y, ldy, rows, gamma, beta, relu, post_add, ld_add, add_period, out_pair, rflag);
+    VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+// PosRows of a launch over `rows` rows: the groups of `segs`, or (NULL) rows / T sequences of T rows; the slots it walks, or -1
+static int64_t pos_rows_table(PosRows& p, const float* table, int64_t ld_pos, int64_t pos_rows, const int32_t* first, const uint8_t* mask,
+                              const vrd_row_segs* segs, int T, int64_t rows) {
+    p.table = table, p.ld = ld_pos, p.table_rows = pos_rows, p.first = first, p.mask = mask;
+    constexpr int64_t group_max = (int64_t)1 << 31;
+    if (!segs) {
+        if (T <= 0 || rows % T || rows >= group_max) return -1;
+        p.count = 1, p.T[0] = T, p.seq0[0] = 0, p.row[0] = 0, p.slot0[0] = 0, p.slot0[1] = rows;
+        return rows;
+    }
+    if (segs->count < 1 || segs->count > VRD_MAX_SEGS) return -1;
+    int64_t slots = 0, seqs = 0;
+    for (int g = 0; g < segs->count; ++g) {
+        const int64_t n = segs->n[g], Tg = segs->T[g], r0 = segs->row[g];
+        if (n <= 0 || Tg <= 0 || r0 < 0 || n * Tg >= group_max || r0 + n * Tg > rows || seqs + n >= group_max) return -1;
+        p.T[g] = (int)Tg, p.seq0[g] = (int)seqs, p.row[g] = r0, p.slot0[g] = slots;
+        slots += n * Tg, seqs += n;
+    }
+    p.count = segs->count;
+    p.slot0[segs->count] = slots;
+    return slots;
+}
+
+static dim3 row_wave_grid(int64_t slots) {
+    static const int64_t max_blocks = [] { const char* e = getenv("VRD_LN_BLOCKS"); return e ? atoll(e) : 8192; }();
+    const int64_t want = (slots + 3) / 4;
+    return dim3((unsigned)(max_blocks > 0 && want > max_blocks ? max_blocks : want));
+}
+
+int vrd_layernorm_pos(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int C, const float* gamma, const float* beta,
+                      int relu, const float* pos_table, int64_t ld_pos, int64_t pos_rows, const int32_t* pos_first, const uint8_t* mask,
+                      const vrd_row_segs* segs, int T, int out_pair, void* stream) {
+    VRD_CHECK_ARG(x && y && gamma && beta && pos_table && pos_first && mask, "vrd_layernorm_pos: null pointer");
+    VRD_CHECK_ARG(C == 256 || C == 512, "vrd_layernorm_pos: C must be 256 or 512 (got %d)", C);
+    VRD_CHECK_ARG(ldx >= C && ldy >= C && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta),
+                  "vrd_layernorm_pos: rows must be 16-byte aligned");
+    VRD_CHECK_ARG(ld_pos >= C && ld_pos % 4 == 0 && aligned16(pos_table) && pos_rows > 0, "vrd_layernorm_pos: bad position table");
+    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == VRD_PAIR_BF16 || out_pair == VRD_PAIR_F16, "vrd_layernorm_pos: bad out_pair %d", out_pair);
+    if (rows <= 0) return 0;
+    PosRows p;
+    const int64_t slots = pos_rows_table(p, pos_table, ld_pos, pos_rows, pos_first, mask, segs, T, rows);
+    VRD_CHECK_ARG(slots >= 0, "vrd_layernorm_pos: bad row groups (1..%d groups inside the %lld rows, each below 2^31 rows; without groups rows %% T == 0)",
+                  VRD_MAX_SEGS, (long long)rows);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    vrd::ProfScope prof(VRD_K_LAYERNORM, s, 0.0, 8.0 * (double)slots * C);
+    unsigned* const rflag = out_pair == VRD_PAIR_F16 ? vrd::range_flag() : nullptr;
+    const dim3 grid = row_wave_grid(slots);
+    if (C == 256)
+        hipLaunchKernelGGL((layernorm_kernel<1, PosRows>), grid, dim3(256), 0, s, x, ldx, y, ldy, slots, gamma, beta, relu, nullptr, 0, 0, out_pair, rflag, p);
+    else
+        hipLaunchKernelGGL((layernorm_kernel<2, PosRows>), grid, dim3(256), 0, s, x, ldx, y, ldy, slots, gamma, beta, relu, nullptr, 0, 0, out_pair, rflag, p);
+    VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+int vrd_position_rows(float* y, int64_t ldy, int64_t rows, int C, const float* pos_table, int64_t ld_pos, int64_t pos_rows,
+                      const int32_t* pos_first, const uint8_t* mask, const vrd_row_segs* segs, int T, int out_pair, void* stream) {
+    VRD_CHECK_ARG(y && pos_table && pos_first && mask, "vrd_position_rows: null pointer");
+    VRD_CHECK_ARG(C == 256 || C == 512, "vrd_position_rows: C must be 256 or 512 (got %d)", C);
+    VRD_CHECK_ARG(ldy >= C && ldy % 4 == 0 && aligned16(y), "vrd_position_rows: rows must be 16-byte aligned");
+    VRD_CHECK_ARG(ld_pos >= C && ld_pos % 4 == 0 && aligned16(pos_table) && pos_rows > 0, "vrd_position_rows: bad position table");
+    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == VRD_PAIR_BF16 || out_pair == VRD_PAIR_F16, "vrd_position_rows: bad out_pair %d", out_pair);
+    if (rows <= 0) return 0;
+    PosRows p;
+    const int64_t slots = pos_rows_table(p, pos_table, ld_pos, pos_rows, pos_first, mask, segs, T, rows);
+    VRD_CHECK_ARG(slots >= 0, "vrd_position_rows: bad row groups (1..%d groups inside the %lld rows, each below 2^31 rows; without groups rows %% T == 0)",
+                  VRD_MAX_SEGS, (long long)rows);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    vrd::ProfScope prof(VRD_K_LAYERNORM, s, 0.0, 4.0 * (double)slots * C);
+    unsigned* const rflag = out_pair == VRD_PAIR_F16 ? vrd::range_flag() : nullptr;
+    const dim3 grid = row_wave_grid(slots);
+    if (C == 256)
+        hipLaunchKernelGGL(position_rows_kernel<1>, grid, dim3(256), 0, s, y, ldy, slots, out_pair, rflag, p);
+    else
+        hipLaunchKernelGGL(position_rows_kernel<2>, grid, dim3(256), 0, s, y, ldy, slots, out_pair, rflag, p);
     VRD_LAUNCH_CHECK();
     return 0;
 }

@@ -136,29 +136,37 @@ class MaskConvTransformerBackbone(nn.Module):
         return (stacked(0, V, pair), stacked(2 * V, Cc, pair) if Cc else None, so_box, stacked(o0 + S, E, False))
 
     @staticmethod
-    def _embed(h, convs, norms, mask2, out, lay, post_add=None):
+    def _embed(h, convs, norms, mask2, out, lay, post_add=None, pos=None):
         """k=3 conv * mask -> LN -> ReLU stack on the stacked sequences of `lay`; the last LN writes into `out`, a column
-        slab of the consumer GEMM's input buffer (pair rows in bf16x3 mode)."""
+        slab of the consumer GEMM's input buffer (pair rows in bf16x3 mode).  Absolute position rows behind the last LN: post_add
+        (materialised, one per row of a batch: the autograd path) or pos (position_operands: per-sequence tables, inference)."""
         ops = _ops()
         last = len(convs) - 1
-        if last == 0 and post_add is None and ops.conv_ln_ok(h, convs[0].conv.weight, convs[0].conv.bias, norms[0].weight, norms[0].bias):
+        if last == 0 and post_add is None and pos is None and ops.conv_ln_ok(h, convs[0].conv.weight, convs[0].conv.bias, norms[0].weight, norms[0].bias):
             # few input channels (the box features): conv, mask, LayerNorm and ReLU as one row kernel, straight into the consumer's slab
             return ragged.conv3(lay, h, convs[0].conv, mask2, out=out, out_pair=ops.pair_mode(), norm=norms[0])
         for i, (conv, norm) in enumerate(zip(convs, norms)):
             h = ragged.conv3(lay, h, conv.conv, mask2)
+            if i == last and pos is not None:
+                return ragged.layernorm_pos(lay, h, norm, mask2, pos, relu=True, out=out, pair=ops.pair_mode())
             h = norm.cl(h, relu=True, out=out if i == last else None, pair=ops.pair_mode(), post_add=post_add if i == last else None)
         return h
 
-    def cl(self, x, mask):
-        """x: (B, C_in, T) contiguous fp32 (the boundary layout), mask: (B, T) bool.
+    def cl(self, x, mask, t_refs=None):
+        """x: (B, C_in, T) contiguous fp32 (the boundary layout), mask: (B, T) bool; t_refs: see cl_parts.
         Returns channels-last feats [(B, T/2^l, D)] and masks [(B, T/2^l)]."""
         assert x.shape[1] == self.in_channels(), f"expected {self.in_channels()} input channels, got {x.shape[1]}"
-        return self.cl_parts(*self._unpack(x.contiguous()), mask)
+        return self.cl_parts(*self._unpack(x.contiguous()), mask, t_refs)
 
-    def cl_parts(self, vis, clip, so_box, ent, mask):
+    def cl_parts(self, vis, clip, so_box, ent, mask, t_refs=None):
         """vis (2B, T, V), clip (2B, T, Cc) or None, so_box (B, T, S), ent (2B, T, E): channels-last operand
-        buffers (from _unpack or ops.pack_pairs); mask (B, T) bool."""
-        return self.pair_stage(self.entity_stage(vis, clip, ent, torch.cat([mask, mask], dim=0)), so_box, mask)
+        buffers (from _unpack or ops.pack_pairs); mask (B, T) bool.
+        t_refs: the length the reference pads the pairs to (an int, or one per pair) where that is not T -- the pairs of a
+        tight-padding bucket; only absolute position rows depend on it (position_table)."""
+        lay2 = None
+        if t_refs is not None and self.use_abs_pe:
+            lay2 = Layout.batch(*mask.shape).with_refs([t_refs if isinstance(t_refs, int) else tuple(t_refs)]).stacked()
+        return self.pair_stage(self.entity_stage(vis, clip, ent, torch.cat([mask, mask], dim=0), lay2), so_box, mask)
 
     def entity_reach(self):
         """How many frames either side of a frame the entity stage reads (embedding convs, then the first stem block's
@@ -182,6 +190,66 @@ class MaskConvTransformerBackbone(nn.Module):
         rows = pe[0, :, :T].t()                                              # (T, D)
         return (rows[None] * mask2[..., None].to(rows.dtype)).reshape(n * T, -1).contiguous()
 
+    def position_table(self, t_ref):
+        """The (t_ref, D) position rows of a pair the reference pads to t_ref frames (reference backbones.py:187-196): the
+        sinusoid table's first t_ref frames as they are below max_len, the table linearly re-interpolated to t_ref frames from
+        max_len on (at max_len itself that is the table).  They do not depend on the length the pair is computed at: frame t of
+        the pair gets row t.  Kept per t_ref for as long as pos_embd is the tensor it was built from."""
+        pe = self.pos_embd
+        key = (pe.data_ptr(), pe._version, str(pe.device))
+        cache = self.__dict__.setdefault("_pos_tables", {})
+        if cache.get("key") != key:
+            cache.clear()
+            cache["key"] = key
+        t_ref = int(t_ref)
+        if t_ref not in cache:
+            rows = pe if t_ref < self.max_len else torch.nn.functional.interpolate(pe, t_ref, mode='linear', align_corners=False)
+            cache[t_ref] = rows[0, :, :t_ref].t().contiguous()
+        return cache[t_ref]
+
+    _POS_PLANS = 64          # position_plan results kept (a video's bucket plan repeats from call to call)
+
+    def position_plan(self, refs):
+        """(table, pos_first) of a call whose sequences, in row order, have the reference lengths `refs` (subject and object
+        sequences share their pair's entry): the tables of the distinct lengths one behind the other, (sum of lengths, D), and per
+        sequence the first row of its length's table, int32 on pos_embd's device."""
+        refs = tuple(int(r) for r in refs)
+        self.position_table(refs[0])                  # (a replaced pos_embd empties the cache, the plans with it)
+        cache = self._pos_tables
+        plans = cache.setdefault("plans", {})
+        hit = plans.get(refs)
+        if hit is None:
+            if len(plans) >= self._POS_PLANS:
+                plans.clear()
+            distinct = sorted(set(refs))
+            start, at = {}, 0
+            for t in distinct:
+                start[t] = at
+                at += t
+            table = torch.cat([self.position_table(t) for t in distinct]) if len(distinct) > 1 else self.position_table(distinct[0])
+            dev = self.pos_embd.device
+            if len(distinct) == 1:                    # (built on the device: no upload in the middle of a call)
+                first = torch.zeros(len(refs), dtype=torch.int32, device=dev)
+            else:
+                first = torch.tensor([start[t] for t in refs], dtype=torch.int32).to(dev)
+            hit = plans[refs] = (table, first)
+        return hit
+
+    def position_operands(self, lay):
+        """position_plan for the sequences of `lay`: their reference lengths (Layout.with_refs), their own where none are given"""
+        t_refs = lay.t_refs if lay.t_refs is not None else [T for _, _, T in lay.segs]
+        key = tuple((r, n) for r, (_, n, _) in zip(t_refs, lay.segs))           # (hashed in C: a call has thousands of sequences)
+        self.position_table(lay.segs[0][2])
+        plans = self._pos_tables.setdefault("plans", {})
+        hit = plans.get(key)
+        if hit is None:
+            refs = [t for r, n in key for t in ((r,) * n if isinstance(r, int) else r)]
+            frames = [T for _, n, T in lay.segs for _ in range(n)]
+            assert all(r >= T for r, T in zip(refs, frames)), "a sequence is never computed at more frames than the reference pads it to"
+            hit = self.position_plan(refs)
+            plans[key] = hit
+        return hit
+
     def entity_stage(self, vis, clip, ent, mask2, lay=None):
         """Everything that sees ONE entity's frames only -- embeddings, visual/box fusion and the first stem block, all
         with weights shared between subject and object (reference backbones.py:172-214): n sequences in, (n, T, D) out.
@@ -189,7 +257,6 @@ class MaskConvTransformerBackbone(nn.Module):
         instead of once per pair.  lay: the layout of the rows (default: the batch form of n sequences)."""
         ops = _ops()
         lay = Layout.of(lay, mask2)
-        assert not self.use_abs_pe or lay.axis == 0, "absolute position rows are laid out per padded length: such models run bucket by bucket"
         Cc = self.n_clip
         D = self.s_fuse_norm.num_channels
         new = lambda width: lay.new(width, mask2)          # noqa: E731
@@ -201,15 +268,24 @@ class MaskConvTransformerBackbone(nn.Module):
         # [visual (+clip) | entity box] -> visual_bbox_fuse
         # (ops.join: the slab-filled buffer, or -- under autograd, where ops return fresh tensors -- the concatenation)
         fuse_in = new(2 * D)
-        pe = self._position_rows(mask2) if self.use_abs_pe else None        # (n * T, D): pe[t] on valid frames, 0 on padded ones
+        # absolute position rows: pe[t] on valid frames, 0 on padded ones.  Inference: per-sequence tables of the pairs' reference
+        # lengths, looked up by the kernel that adds them (pos); under autograd the materialised (n * T, D) rows of a batch (pe)
+        pe = pos = None
+        if self.use_abs_pe and torch.is_grad_enabled():
+            assert lay.axis == 0 and lay.t_refs is None, "training runs in the batch form, at the batch's own padded length"
+            pe = self._position_rows(mask2)
+        elif self.use_abs_pe:
+            pos = self.position_operands(lay)
         if Cc:
             vc = new(2 * D)
             a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, vc[..., :D], lay)
             b = self._embed(clip, self.clip_embd, self.clip_embd_norm, mask2, vc[..., D:], lay)
             # (CLIP variant: the position rows are added behind the visual / CLIP fusion, backbones.py:362-384)
+            if pos is not None:
+                pe = ragged.position_rows(lay, mask2, pos)
             a = self.visual_clip_fuse.cl(cat(ops.join(vc, (a, b))), row_mask=mask2, out=fuse_in[..., :D], out_pair=pair, res=pe)
         else:
-            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, fuse_in[..., :D], lay, post_add=pe)
+            a = self._embed(vis, self.visual_embd, self.visual_embd_norm, mask2, fuse_in[..., :D], lay, post_add=pe, pos=pos)
         b = self._embed(ent, [self.bbox_entity_embd], [self.bbox_entity_norm], mask2, fuse_in[..., D:], lay)
         so = self.visual_bbox_fuse.cl(cat(ops.join(fuse_in, (a, b))), row_mask=mask2)
         so, _ = self.stem[0].cl(so, mask2, lay=lay)

@@ -102,7 +102,17 @@ def _parts(t):
 
 class Source:
     """Where the operands of a bucket of pair_candidates come from.  `operands(bucket)` is the one method a source has to have
-    (`Padded`, which goes through _mask_vrd, has `outputs` in its place); the rest is what the drivers make of it."""
+    (`Padded`, which goes through _mask_vrd, has `outputs` in its place); the rest is what the drivers make of it.
+    refs: the reference's padded length of the pair at every position of the call's pair list, for a model with absolute position
+    rows (pair_candidates sets it; None otherwise)."""
+    refs = None
+
+    def refs_of(self, b):
+        """the reference lengths of the pairs of bucket b (one int where they agree), or None: no position rows / a filler bucket"""
+        if self.refs is None or b.sel is None:
+            return None
+        r = self.refs[b.sel.start:b.sel.stop]
+        return r[0] if len(set(r)) == 1 else tuple(r)
 
     def prepare(self, wave):
         """before the operands of the buckets of `wave` are asked for one by one"""
@@ -115,7 +125,7 @@ class Source:
         o, bb = self.operands(b), self.model.backbone
         if o.kind == "so":
             return bb.pair_stage(o.so, o.so_box, o.mask)
-        return bb.cl_parts(o.vis, o.clip, o.so_box, o.ent, o.mask)
+        return bb.cl_parts(o.vis, o.clip, o.so_box, o.ent, o.mask, self.refs_of(b))
 
     def outputs(self, b):
         """the output dict of bucket b on its own, in launch waves"""
@@ -138,7 +148,8 @@ class Matrices(Source):
     def replay(self, b, k):
         """vrd_postprocess's outputs of bucket b from a recorded graph, or None"""
         from .. import eval_graph
-        if b.n > eval_graph.MAX_PAIRS:
+        # (a recording is made per padded length; position rows follow the pairs' reference lengths: such a model runs eagerly)
+        if b.n > eval_graph.MAX_PAIRS or self.refs is not None:
             return None
         if self._storage is None:                   # (one walk over the parameters per call instead of one per bucket)
             self._storage = eval_graph.storage_key(self.model)
@@ -270,8 +281,19 @@ class Padded(Source):
         self.model, self.feats = model, feats
 
     def outputs(self, b):
-        x, m = self.model._batch(self.feats, b.sel, b.T)
-        return self.model._mask_vrd(x, m, with_aux=False)
+        refs = self.refs_of(b)
+        if not isinstance(refs, tuple):
+            x, m = self.model._batch(self.feats, b.sel, b.T)
+            return self.model._mask_vrd(x, m, with_aux=False, t_ref=refs)
+        # pairs of one padded length whose reference lengths differ (long pairs of several slices): a batch per reference length
+        groups = {}
+        for pos, r in zip(b.sel, refs):
+            groups.setdefault(r, []).append(pos)
+        outs = [self.model._mask_vrd(*self.model._batch(self.feats, ps, b.T), with_aux=False, t_ref=r) for r, ps in groups.items()]
+        back = torch.empty(b.n, dtype=torch.int64)
+        back[torch.tensor([pos - b.sel.start for ps in groups.values() for pos in ps])] = torch.arange(b.n)
+        back = back.to(outs[0]["pred_logits"].device)
+        return {key: torch.cat([o[key] for o in outs])[back] for key in ("pred_logits", "pred_masks")}
 
 
 def _filler_operands(bb, b, kind, dev):
@@ -341,15 +363,18 @@ def backbone_rows(bb, x, index, lay, mask):
     return bb.pair_stage(so, so_box, mask, lay)
 
 
-def mask_vrd_rows(model, x, masks2d, buckets, with_aux):
+def mask_vrd_rows(model, x, masks2d, buckets, with_aux, t_ref=None):
     """MaskVRD._mask_vrd for `buckets` (sel: pair indices into the batch x (B, C_in, T)), each launch wave of at most ~pair_chunk
-    pairs in one row space -> the batch-shaped output dict, at the batch's own padded length."""
+    pairs in one row space -> the batch-shaped output dict, at the batch's own padded length.
+    t_ref: the reference's padded length of the pairs (default: the batch's T)."""
     (B, T), dev, out = masks2d.shape, x.device, None
     for wave in waves(buckets, model._chunk_size(B)):
         plan = add_filler(wave, T)
         # (a filler bucket recomputes the first frames of some pair under an all-false mask: finite numbers nobody reads)
         index = [b.sel if b.sel is not None else wave[0].sel[:1].repeat(b.n) for b in plan]
         lay = ragged.Layout([(b.n, b.T, b.flat) for b in plan])
+        if model.use_abs_pe:            # (a filler bucket has no valid frame: any table serves it)
+            lay = lay.with_refs([T if t_ref is None else t_ref] * len(plan))
         idx64 = [i.long() for i in index]
         mask = torch.cat([masks2d[i64, :b.T].reshape(-1) if b.sel is not None else torch.zeros(b.n * b.T, dtype=torch.bool, device=dev)
                           for b, i64 in zip(plan, idx64)]).view(1, lay.rows)
@@ -394,14 +419,16 @@ def _gather(run, wave):
     return [src.operands(b) if b.sel is not None else _filler_operands(run.model.backbone, b, kind, run.cand.device) for b in wave]
 
 
-def _raw_entity_stage(bb, wave, got):
+def _raw_entity_stage(bb, wave, got, refs=None):
     """The entity stage of the buckets that bring raw features, in a row space of their own, [subject | object] like the joint
-    one -> (its rows (1, 2 R_e, D), R_e), or (None, 0) without such a bucket."""
+    one -> (its rows (1, 2 R_e, D), R_e), or (None, 0) without such a bucket.  refs: the buckets' reference lengths (Layout.with_refs)."""
     ops = _ops()
     raw = [(b, o) for b, o in zip(wave, got) if o.kind == "parts"]
     if not raw:
         return None, 0
     lay = ragged.Layout([(b.n, b.T, b.flat) for b, _ in raw])
+    if refs is not None:
+        lay = lay.with_refs([r for r, o in zip(refs, got) if o.kind == "parts"])
 
     def stacked(ts):
         if ts[0] is None:
@@ -440,7 +467,9 @@ def candidates_rows(run, lens, ids, t_pad):
         got = _gather(run, wave)
         mask = torch.cat([o.mask.reshape(-1) for o in got]).view(1, lay.rows)
         so_box = torch.cat([o.so_box.reshape(-1, bb.n_bbox_so) for o in got]).view(1, lay.rows, -1)
-        so = _joint_rows(wave, got, *_raw_entity_stage(bb, wave, got), lay)
+        # (absolute position rows: every pair's reference length, a filler bucket's own -- it has no valid frame)
+        refs = None if run.source.refs is None else [b.T if b.sel is None else run.source.refs_of(b) for b in wave]
+        so = _joint_rows(wave, got, *_raw_entity_stage(bb, wave, got, refs), lay)
         del got
         logits, segs = model._heads(*bb.pair_stage(so, so_box, mask, lay), False, lay)[-1]
         p = 0
@@ -452,7 +481,7 @@ def candidates_rows(run, lens, ids, t_pad):
             p += b.n
 
 
-def pair_candidates(model, feats, lens, ids, t_pad, k, source=None):
+def pair_candidates(model, feats, lens, ids, t_pad, k, source=None, t_refs=None):
     """MaskVRD.pair_candidates: the candidate record of the pairs `ids` (already grouped by padded length)."""
     ops = _ops()
     dev = model.device
@@ -469,6 +498,10 @@ def pair_candidates(model, feats, lens, ids, t_pad, k, source=None):
         local = [feats[i] for i in ids]
         tables = ops.pair_table(local)      # None unless the features are the dataloader's frame-major matrices
         src = Padded(model, local) if tables is None else Matrices(model, tables, int(local[0].shape[0]))
+    if model.use_abs_pe:
+        if t_refs is None:
+            t_refs = model._reference_pad(lens)
+        src.refs = [t_refs[i] for i in ids]
     run = Run(model, src, lens_dev, k, cand)
     if model._eval_rows_form(len(lens)) and not isinstance(src, Padded):
         # all padded lengths of the video in one row space, in waves of ~pair_chunk pairs

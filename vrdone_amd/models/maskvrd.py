@@ -123,7 +123,10 @@ class MaskVRD(nn.Module):
     # follow it, only on there being one at every pyramid level (the frame behind the last valid one is what the depthwise
     # convs, the pools and the FPN read across the end: LayerNorm(0) = beta there, zero padding if the sequence simply
     # ends): with `down` = the coarsest level's stride, any padded length T' with T' / down > ceil(L / down) gives the
-    # same outputs on the pair's frames (checked in float64 on the oracle: 1e-14; tests/test_oracle_golden.py).  So a
+    # same outputs on the pair's frames (checked in float64 on the oracle: 1e-14; tests/test_oracle_golden.py).  Absolute
+    # position rows (use_abs_pe) are no exception: frame t of a pair gets row t of the table of the REFERENCE's padded length
+    # (re-interpolated from max_seq_len on), which is known per pair and travels with it (Layout.with_refs,
+    # backbones.position_table) -- the length the pair is computed at does not enter.  So a
     # pair of L frames is computed at the smallest such multiple of TIGHT_UNIT below the batch's padded length, pairs of
     # equal T' as one batch; the outputs are laid out at the batch's padded length like the reference's.
     tight_padding = os.environ.get("VRDONE_TIGHT_PADDING", "1") != "0"
@@ -136,8 +139,8 @@ class MaskVRD(nn.Module):
     def tight_len(self, L, T):
         """The padded length a pair of L valid frames is computed at inside a batch padded to T frames."""
         down = self.scale_factor ** self.backbone_arch[-1]
-        if not self.tight_padding or self.use_abs_pe or L >= T or T % down:
-            return T            # (absolute position rows are interpolated to the padded length: it is part of the input there)
+        if not self.tight_padding or L >= T or T % down:
+            return T
         need = down * (-(-L // down) + 1)
         unit = self.TIGHT_UNIT * down // math.gcd(self.TIGHT_UNIT, down)
         t = -(-need // unit) * unit
@@ -189,7 +192,7 @@ class MaskVRD(nn.Module):
     with_so_trajs = True
 
     def _eval_rows_form(self, n_pairs):
-        return self.row_space and not self.use_abs_pe and n_pairs >= self.ROWS_MIN_PAIRS
+        return self.row_space and n_pairs >= self.ROWS_MIN_PAIRS
 
     def _tight_plan(self, batched_masks, masks2d):
         """{"buckets": [eval_batches.Bucket(T', pair indices (n,) int32 on the device, n, flat)], "rows": the buckets can share one
@@ -210,7 +213,7 @@ class MaskVRD(nn.Module):
             lens_h = host[0].tolist() if bool((host[0] == host[1]).logical_or(host[0] == 0).all()) else None
         plan = None
         if lens_h is not None:
-            rows = self.row_space and not self.use_abs_pe
+            rows = self.row_space
             want = {}
             for i, t2 in enumerate(self.tight_buckets(lens_h, [T] * B, self.ROWS_MIN_ROWS if rows else None)):
                 # the row-space form runs the dense k = 3 convs flat over the buckets whose sequences all end in two padded
@@ -246,11 +249,13 @@ class MaskVRD(nn.Module):
             pool[key] = [torch.cuda.Stream(device=dev) for _ in range(self.TIGHT_STREAMS - 1)]
         return pool[key]
 
-    def _mask_vrd_tight(self, x, masks2d, plan, with_aux):
-        """_mask_vrd bucket by bucket (see `tight padding` above); outputs in the batch's own padded length."""
+    def _mask_vrd_tight(self, x, masks2d, plan, with_aux, t_ref=None):
+        """_mask_vrd bucket by bucket (see `tight padding` above); outputs in the batch's own padded length.
+        t_ref: the reference's padded length of the pairs (default: the batch's)."""
         B, T = masks2d.shape
         dev = x.device
         out = None
+        t_ref = T if t_ref is None else t_ref
         main = torch.cuda.current_stream(dev)
         plan = plan["buckets"]
         side = self._tight_side_streams(dev) if len(plan) > 1 and not torch.cuda.is_current_stream_capturing() else None
@@ -267,7 +272,7 @@ class MaskVRD(nn.Module):
                 for c0 in range(0, n, step):
                     sel, sel64 = idx[c0:c0 + step].contiguous(), idx64[c0:c0 + step]
                     m = m_all[c0:c0 + step]
-                    o = self._heads(*self.backbone.cl_parts(*self.backbone._unpack(x, frames=t2, index=sel), m), with_aux)
+                    o = self._heads(*self.backbone.cl_parts(*self.backbone._unpack(x, frames=t2, index=sel), m, t_ref), with_aux)
                     if out is None:
                         out = eval_batches.new_outputs(B, T, *o["pred_logits"].shape[1:], len(o.get("aux_outputs", ())), dev)
                         if len(lanes) > 1:
@@ -280,9 +285,11 @@ class MaskVRD(nn.Module):
         out["output_mask"] = masks2d[:, None, :]
         return out
 
-    def _mask_vrd(self, batched_inputs, batched_masks, with_aux=None):
+    def _mask_vrd(self, batched_inputs, batched_masks, with_aux=None, t_ref=None):
         """(B, C_in, T) fp32, (B, 1, T) bool -> dict(pred_logits (B,Q,K+1), pred_masks (B,Q,T),
-        [aux_outputs], output_mask (B,1,T)); backbone -> neck -> predictor like the reference."""
+        [aux_outputs], output_mask (B,1,T)); backbone -> neck -> predictor like the reference.
+        t_ref: the length the reference pads these pairs to when that is not T (a batch that a caller padded tighter, eval only);
+        absolute position rows follow it."""
         if not batched_inputs.is_cuda:
             raise RuntimeError("MaskVRD._mask_vrd runs on the HIP device only; move the model and inputs to 'cuda'")
         B = batched_inputs.shape[0]
@@ -291,8 +298,8 @@ class MaskVRD(nn.Module):
             plan = self._tight_plan(batched_masks, masks2d)
             if plan is not None:
                 if plan["rows"]:
-                    return eval_batches.mask_vrd_rows(self, batched_inputs, masks2d, plan["buckets"], with_aux)
-                return self._mask_vrd_tight(batched_inputs, masks2d, plan, with_aux)
+                    return eval_batches.mask_vrd_rows(self, batched_inputs, masks2d, plan["buckets"], with_aux, t_ref)
+                return self._mask_vrd_tight(batched_inputs, masks2d, plan, with_aux, t_ref)
         if self.training and torch.is_grad_enabled():
             self._begin_training_pass(batched_inputs.device)
         outs = []
@@ -300,7 +307,7 @@ class MaskVRD(nn.Module):
         for b0 in range(0, B, step):
             x = batched_inputs[b0:b0 + step]
             m = masks2d[b0:b0 + step]
-            outs.append(self._heads(*self.backbone.cl(x, m), with_aux))
+            outs.append(self._heads(*self.backbone.cl(x, m, t_ref), with_aux))
         return self._merge(outs)
 
     def _begin_training_pass(self, device):
@@ -716,15 +723,16 @@ class MaskVRD(nn.Module):
     def _shared_entity_rows(self, source, sel, shared, at, T, pieces=None):
         return eval_batches.SharedStreams(self, source, None, shared).entity_rows(sel, at, T, pieces)
 
-    def pair_candidates(self, feats, lens, ids, t_pad, k, source=None):
+    def pair_candidates(self, feats, lens, ids, t_pad, k, source=None, t_refs=None):
         """Network + per-(pair, query) post-processing kernel for the pairs `ids` (already grouped by padded length), bucket by
         bucket or, from _eval_rows_form's size on, all padded lengths of a launch wave in one row space (models/eval_batches.py).
         source: a proposals.PairSource -- pair rows are then gathered on the device from the per-tracklet features
         (vrd_gather_pairs) and `feats` is not used; with its tracklet table the entity stage of the backbone runs once
         per tracklet instead of twice per pair (eval_batches.SharedStreams).
+        t_refs: the reference's padded length per pair id (default: _reference_pad(lens), one video's); absolute position rows follow it.
         Returns ONE float32 tensor (len(ids), Q, 2k + 2) = [top-k scores | top-k class ids | first | last frame], the
         three integer fields bit-cast: the compact candidate record that sharded runs exchange (SURVEY 8e option i)."""
-        return eval_batches.pair_candidates(self, feats, lens, ids, t_pad, k, source)
+        return eval_batches.pair_candidates(self, feats, lens, ids, t_pad, k, source, t_refs)
 
     @torch.no_grad()
     def forward_test(self, input_data):
@@ -744,6 +752,7 @@ class MaskVRD(nn.Module):
         lens = list(source.lens) if source is not None else [int(f.shape[1]) for f in feats]
         assert len(lens) == P
         order, t_pad = self.eval_plan(lens)
+        t_refs = self._reference_pad(lens)              # (the lengths eval_plan shortened: absolute position rows follow them)
         shard = getattr(self, "_shard", None)
         rank, world = parallel.rank_world(shard[0]) if shard else (0, 1)
         mine = order[rank::world]                      # round-robin over the length-sorted order
@@ -755,7 +764,7 @@ class MaskVRD(nn.Module):
         if f16:
             flag = ops.f16_range_flag(next(self.parameters()).device)
             flag.zero_()
-        cand = self.pair_candidates(feats, lens, mine, t_pad, k, source=source)
+        cand = self.pair_candidates(feats, lens, mine, t_pad, k, source=source, t_refs=t_refs)
         if f16:
             # an activation beyond the f16 operand range is reported in the device's flag word (a NaN would not reach the
             # scores reliably: the ReLUs and max-pools on the way drop it).  Without leaving the stream the flag poisons this
@@ -885,7 +894,8 @@ class MaskVRD(nn.Module):
         lens = [L for lv in lens_v for L in lv]
         P = len(lens)
         # the reference's padded lengths video by video, then one tight-padding plan over all pairs of the call
-        order, t_pad = eval_batches.pair_order(self, lens, [t for lv in lens_v for t in self._reference_pad(lv)])
+        t_refs = [t for lv in lens_v for t in self._reference_pad(lv)]
+        order, t_pad = eval_batches.pair_order(self, lens, t_refs)
 
         # per-pair tables on the host, in one upload: [s score | o score | so_offset | so_start | so_end | video pair offsets]
         base = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -917,7 +927,7 @@ class MaskVRD(nn.Module):
         if f16:
             flag = ops.f16_range_flag(next(self.parameters()).device)
             flag.zero_()
-        cand = self.pair_candidates(feats, lens, order, t_pad, k, source=source)[unsort_dev]     # each video's own pair order
+        cand = self.pair_candidates(feats, lens, order, t_pad, k, source=source, t_refs=t_refs)[unsort_dev]     # each video's own pair order
         ints = cand.view(torch.int32)
         vp = table_dev[5 * P:]
         count, index, score = ops.select_triplets(cand, f_dev[:P], f_dev[P:], table_dev[2 * P:3 * P], table_dev[3 * P:4 * P],

@@ -67,6 +67,7 @@ class Layout:
         self.rows_flat = sum(n * T for (_, n, T), f in zip(segs, flat) if f)
         self.lead = (1, self.rows) if axis else segs[0][1:]           # a tensor's shape in front of its channels
         self._tails, self._stacked = {}, None
+        self.t_refs = None          # see with_refs
 
     @classmethod
     def _of_segs(cls, segs, flat, axis):
@@ -89,6 +90,21 @@ class Layout:
         """`lay`, or without one the batch form of the (B, T, ...) tensor / mask x"""
         return lay if lay is not None else cls.batch(x.shape[0], x.shape[1])
 
+    def with_refs(self, t_refs):
+        """This layout with the reference padded lengths of its sequences: t_refs[i] for bucket i, one int for all its sequences
+        or one per sequence.  Absolute position rows are the reference's table of that length (backbones.position_operands),
+        whatever length the sequence is computed at here; nothing else reads them."""
+        assert len(t_refs) == len(self.segs) and all(isinstance(r, int) or len(r) == n for r, (_, n, _) in zip(t_refs, self.segs))
+        lay = Layout._of_segs(self.segs, self.flat, self.axis)
+        lay.t_refs = [r if isinstance(r, int) else tuple(r) for r in t_refs]
+        return lay
+
+    def seq_refs(self):
+        """the reference padded length of every sequence, in row order (None: no lengths given, the sequences' own)"""
+        if self.t_refs is None:
+            return None
+        return [t for r, (_, n, _) in zip(self.t_refs, self.segs) for t in ((r,) * n if isinstance(r, int) else r)]
+
     def twice(self):
         """segs of the stacked [subject | object] rows"""
         return self.segs + [(self.rows + off, n, T) for off, n, T in self.segs]
@@ -100,6 +116,8 @@ class Layout:
                 self._stacked = Layout.batch(2 * self.segs[0][1], self.segs[0][2])
             else:
                 self._stacked = Layout._of_segs(self.twice(), self.flat * 2, 1)
+            if self.t_refs is not None:         # (subject and object sequences share their pair's length)
+                self._stacked = self._stacked.with_refs(self.t_refs * 2 if self.axis else [r if isinstance(r, int) else r * 2 for r in self.t_refs])
         return self._stacked
 
     def strided(self, s):
@@ -218,6 +236,45 @@ def dwconv_ln_multi(lay, x, sets, mask_out, *, pre_ln=None):
                             mask_out=None if mask_out is None else mask_out[:, r0:r1], pre_ln=pre_ln,
                             segs=[(off - r0, n, T) for off, n, T in part])
     return [ops.Pair(b, Cout) if ops._fmt(st.get("pair")) else b for st, b in zip(sets, bufs)]
+
+
+def _pos_launches(lay):
+    """the launches of a position-row kernel over the sequences of `lay`: [(segs or None, T or None, first sequence, sequences)]
+    -- one for a single group of sequences, else one per _MAX_SEGS buckets as its row groups"""
+    if len(_merged(lay.segs)) == 1:
+        (_, n, T), = _merged(lay.segs)
+        return [(None, T, 0, n)]
+    out, at = [], 0
+    for g0 in range(0, len(lay.segs), _MAX_SEGS):
+        part = lay.segs[g0:g0 + _MAX_SEGS]
+        seqs = sum(n for _, n, _ in part)
+        out.append((part, None, at, seqs))
+        at += seqs
+    return out
+
+
+def layernorm_pos(lay, x, norm, mask, pos, *, relu=False, out=None, pair=False):
+    """ops.layernorm_pos over the sequences of `lay`: LayerNorm (+ ReLU) of the rows x, then the position row of every valid
+    frame.  pos = (table, first): the tables of the call's reference lengths and the first table row of every sequence of `lay`
+    in row order (backbones.position_operands)."""
+    ops = _ops()
+    table, first = pos
+    if out is None:
+        out = lay.new(x.shape[-1], x)
+    for segs, T, s0, n in _pos_launches(lay):
+        ops.layernorm_pos(x, norm.weight, norm.bias, table, first[s0:s0 + n], mask, T=T, segs=segs, relu=relu, out=out, pair=pair)
+    return ops.Pair(out, x.shape[-1]) if pair else out
+
+
+def position_rows(lay, mask, pos):
+    """the masked position rows of the sequences of `lay` as (rows, C) f32 rows: what layernorm_pos adds (the CLIP variant adds
+    them as a GEMM's residual)"""
+    ops = _ops()
+    table, first = pos
+    out = torch.empty(lay.rows, table.shape[-1], device=table.device, dtype=torch.float32)
+    for segs, T, s0, n in _pos_launches(lay):
+        ops.position_rows(table, first[s0:s0 + n], mask, T=T, segs=segs, out=out)
+    return out
 
 
 def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, rel_pe=None, pair=False, drop=None):

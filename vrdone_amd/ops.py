@@ -951,6 +951,52 @@ def layernorm(x, gamma, beta, *, relu=False, post_add=None, out=None, pair=False
     return _as_pair(out, cols, _fmt(pair))
 
 
+def _pos_args(table, first, mask, rows, cols, segs, T):
+    """the (pos_table, ld_pos, pos_rows, pos_first, mask, segs, T) arguments of vrd_layernorm_pos / vrd_position_rows for a launch
+    over `rows` rows: segs = [(first row, sequences, frames)] or None for rows / T sequences of T rows"""
+    pt, n_pos, c_pos, ld_pos = _rows(table)
+    assert c_pos == cols, f"position table of {c_pos} channels for rows of {cols}"
+    if segs is None:
+        seqs, seg_table = rows // T, None
+    else:
+        seqs, seg_table, T = sum(n for _, n, _ in segs), C.pointer(_hip.RowSegs.of(segs)), 0
+    if not first.is_cuda or first.dtype != torch.int32 or not first.is_contiguous() or first.numel() != seqs:
+        raise ValueError(f"pos_first must be a contiguous int32 HIP tensor with one entry per sequence ({first.numel()} vs {seqs})")
+    return pt, ld_pos, n_pos, first.data_ptr(), _mask_ptr(mask, rows), seg_table, T
+
+
+def layernorm_pos(x, gamma, beta, table, first, mask, *, T=None, segs=None, relu=False, out=None, pair=False):
+    """layernorm() with absolute position rows from per-sequence tables in place of post_add (vrd_layernorm_pos; inference only):
+    sequence s, frame t gets table[first[s] + t] where mask is set.  table: (rows of all tables, C) f32; first: int32 per sequence,
+    on the device; mask: one byte per row of x.  The rows of x are sequences of T frames, or the groups `segs` = [(first row,
+    sequences, frames)] (rows outside the groups are left alone).  Same bits as layernorm() with the materialised rows as post_add."""
+    assert not recording(x, gamma, beta), "per-sequence position tables are an inference form: training adds the periodic post_add rows"
+    px, rows, cols, ldx = _rows(x)
+    if out is None:
+        out = torch.empty(*x.shape, device=x.device, dtype=torch.float32)
+    py, rows_y, cols_y, ldy = _rows(out)
+    assert rows_y == rows and cols_y == cols and gamma.numel() == cols and beta.numel() == cols
+    _hip.check(lib.vrd_layernorm_pos(px, ldx, py, ldy, rows, cols, _param_ptr(gamma, x, "LayerNorm weight"),
+                                     _param_ptr(beta, x, "LayerNorm bias"), 1 if relu else 0,
+                                     *_pos_args(table, first, mask, rows, cols, segs, T if T is not None else x.shape[-2]),
+                                     _fmt(pair), _stream()), "vrd_layernorm_pos")
+    return _as_pair(out, cols, _fmt(pair))
+
+
+def position_rows(table, first, mask, *, T=None, segs=None, out=None, pair=False):
+    """The masked position rows layernorm_pos() adds, on their own (vrd_position_rows): (rows of mask, C) f32 or pair rows.
+    out: the buffer (required with `segs` that leave rows out: those rows keep what they hold)."""
+    cols = table.shape[-1]
+    if out is None:
+        out = torch.empty(*mask.shape, cols, device=table.device, dtype=torch.float32)
+    py, rows, cols_y, ldy = _rows(out)
+    assert cols_y == cols
+    _hip.check(lib.vrd_position_rows(py, ldy, rows, cols, *_pos_args(table, first, mask, rows, cols, segs,
+                                                                     T if T is not None else mask.shape[-1]),
+                                     _fmt(pair), _stream()), "vrd_position_rows")
+    return _as_pair(out, cols, _fmt(pair))
+
+
 CONV_LN_MAXK = 32
 _conv_ln_on = os.environ.get("VRDONE_CONV_LN", "1") != "0"
 
