@@ -695,7 +695,7 @@ def _per_row_child():
 def test_local_attention_per_row_kernel():
     """The per-row banded kernel runs only under VRD_LOCAL_STRIP=0, which the library reads once per process: a child process.
     Both banded kernels record under the same profiler family (local_attn), so launch counts cannot tell them apart: that the
-    child ran the per-row kernel rests on vrd_local_attn honouring the switch (csrc/vrd_attn.hip, local_attn_launch), which the
+    child ran the per-row kernel rests on vrd_local_attn honouring the switch (csrc/vrd_local_attn.hip, local_attn_launch), which the
     child checks is set in its own environment before the library is loaded."""
     env = dict(os.environ, VRD_LOCAL_STRIP="0")
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "per-row"], env=env, capture_output=True, text=True, timeout=300)

@@ -3,7 +3,7 @@ against goldens of the real reference at windows 5, 11 and 19 (scripts/make_gold
 tests/local_window_cases.py) and against the float64 oracle at every window, 3 included (the reference's own code fails
 at window 3, see local_window_cases.REF_WINDOWS).
 
-Windows 3 .. 9 run the whole-row strip kernel, 11 .. 19 the half-row one (csrc/vrd_attn.hip); the cases cover both with
+Windows 3 .. 9 run the whole-row strip kernel, 11 .. 19 the half-row one (csrc/vrd_local_attn.hip); the cases cover both with
 4 and 8 heads, with and without rel_pe: two full strips of 16 rows and a partial one, a sequence of half a window, a
 fully masked sequence.  Tolerances are those of the existing tests of the same op and mode (tests/test_gpu_ops.py,
 test_gpu_backward.py, test_gpu_train.py, test_gpu_model.py): the banded kernels compute in f32 on the vector units in

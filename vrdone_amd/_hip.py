@@ -267,7 +267,7 @@ _SIGNATURES = {
     "vrd_dwconv_bwd": (C.c_int, [C.POINTER(DwconvBwdArgs), C.c_void_p]),
     "vrd_local_attn_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, c_f32p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
-    # ---- training dropout (csrc/vrd_dropout.hip, vrd_backward.hip; host mirror vrdone_amd/dropout.py): seed = a 64-bit word on the device
+    # ---- training dropout (csrc/vrd_dropout.hip, vrd_local_attn_bwd.hip; host mirror vrdone_amd/dropout.py): seed = a 64-bit word on the device
     "vrd_dropout_mask": (C.c_int, [C.c_void_p, C.c_uint, C.c_int64, C.c_int64, C.c_float, c_u8p, C.c_void_p]),
     "vrd_dropout_rows": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_uint, C.c_int64, C.c_float, c_f32p, C.c_int64,
                                    C.c_void_p]),

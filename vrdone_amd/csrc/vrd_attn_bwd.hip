@@ -589,7 +589,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_kernel(const float* _
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+using vrd::aligned16;
 
 template <int HD, bool F16>
 int launch_bwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* out, const float* dO, int64_t ldo,

@@ -1396,7 +1396,7 @@ int launch(const float* q, int64_t ldq, const float* k, const float* v, int64_t 
     return 0;
 }
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+using vrd::aligned16;
 
 }  // namespace
 
@@ -1443,27 +1443,49 @@ FlashChoice choose_flash(int head_dim, int Tq, int Tk, int64_t ldq, int64_t ldkv
 }
 
 // one launch of the chosen instantiation; SEGS: over the row groups of *sg (B is unused; Tq, Tk: the largest group's)
+// head_dim 32 has one form, launch<32, 4, F16, 3>; products == 1 only the f16 operands at head_dim 64 / 128; NW is 3 or 4
 template <bool SEGS>
 int launch_flash(FlashChoice c, int head_dim, bool f16, int products, const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                  const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, float scale, float* out, int64_t ldo,
                  int out_pair, hipStream_t s, const AttnSegs* sg) {
-    const bool w64 = c.w64;
-    const int nw = c.nw;
-    int rc;
-#define VRD_ATTN_ARGS q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s, sg
-    if (head_dim == 32) rc = f16 ? launch<32, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<32, 4, false, 3, SEGS>(VRD_ATTN_ARGS);
-    else if (products == 1) {
-        if (w64) rc = head_dim == 128 ? launch_w64<128, true, 1, SEGS>(VRD_ATTN_ARGS) : launch_w64<64, true, 1, SEGS>(VRD_ATTN_ARGS);
-        else if (head_dim == 128) rc = nw == 3 ? launch<128, 3, true, 1, SEGS>(VRD_ATTN_ARGS) : launch<128, 4, true, 1, SEGS>(VRD_ATTN_ARGS);
-        else rc = nw == 3 ? launch<64, 3, true, 1, SEGS>(VRD_ATTN_ARGS) : launch<64, 4, true, 1, SEGS>(VRD_ATTN_ARGS);
-    } else if (w64) rc = head_dim == 128 ? (f16 ? launch_w64<128, true, 3, SEGS>(VRD_ATTN_ARGS) : launch_w64<128, false, 3, SEGS>(VRD_ATTN_ARGS))
-                                  : (f16 ? launch_w64<64, true, 3, SEGS>(VRD_ATTN_ARGS) : launch_w64<64, false, 3, SEGS>(VRD_ATTN_ARGS));
-    else if (head_dim == 128) rc = nw == 3 ? (f16 ? launch<128, 3, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<128, 3, false, 3, SEGS>(VRD_ATTN_ARGS))
-                                           : (f16 ? launch<128, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<128, 4, false, 3, SEGS>(VRD_ATTN_ARGS));
-    else rc = nw == 3 ? (f16 ? launch<64, 3, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<64, 3, false, 3, SEGS>(VRD_ATTN_ARGS))
-                      : (f16 ? launch<64, 4, true, 3, SEGS>(VRD_ATTN_ARGS) : launch<64, 4, false, 3, SEGS>(VRD_ATTN_ARGS));
-#undef VRD_ATTN_ARGS
+    using vrd::IntList;
+    int rc = 0;
+    auto run = [&](auto* fn) { rc = fn(q, ldq, k, v, ldkv, kv_mask, q_mask, B, Tq, Tk, n_head, scale, out, ldo, out_pair, s, sg); };
+    // HD and the operand format F16 at NPROD products, on the kernel and wave count of the choice
+    auto form = [&](auto HD, auto F16, auto NPROD) {
+        constexpr int hd = decltype(HD)::value, np = decltype(NPROD)::value;
+        constexpr bool f = decltype(F16)::value;
+        if (c.w64) run(launch_w64<hd, f, np, SEGS>);
+        else if (c.nw == 3) run(launch<hd, 3, f, np, SEGS>);
+        else run(launch<hd, 4, f, np, SEGS>);
+    };
+    if (head_dim == 32)
+        vrd::pick_bool(f16, [&](auto F16) { run(launch<32, 4, decltype(F16)::value, 3, SEGS>); });
+    else
+        vrd::pick_of(IntList<64, 128>{}, head_dim, [&](auto HD) {
+            if (products == 1) form(HD, std::true_type{}, std::integral_constant<int, 1>{});
+            else vrd::pick_bool(f16, [&](auto F16) { form(HD, F16, std::integral_constant<int, 3>{}); });
+        });
     return rc;
+}
+
+// The checks vrd_attention_pair and vrd_attention_pair_segs share, under the caller's name `who`; the caller passes what its own
+// pointers and sizes come to.  0, or -1 with the error set.
+int check_pair_args(const char* who, bool ptrs_ok, bool sizes_ok, const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
+                    int n_head, int head_dim, const float* out, int64_t ldo, int out_pair, int pair_fmt, int products) {
+    VRD_CHECK_ARG(ptrs_ok, "%s: null pointer", who);
+    VRD_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128, "%s: head_dim must be 32, 64 or 128 (got %d)", who, head_dim);
+    VRD_CHECK_ARG(sizes_ok, "%s: bad sizes", who);
+    const int width = n_head * head_dim;
+    VRD_CHECK_ARG(ldq >= width && ldkv >= width && ldo >= width && ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 &&
+                      aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out),
+                  "%s: rows must be 16-byte aligned pair rows of width n_head*head_dim", who);
+    VRD_CHECK_ARG(pair_fmt == VRD_PAIR_BF16 || pair_fmt == VRD_PAIR_F16, "%s: pair_fmt must be VRD_PAIR_BF16 or VRD_PAIR_F16", who);
+    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == pair_fmt, "%s: pair output comes in the operands' format", who);
+    VRD_CHECK_ARG(products == 0 || products == 3 || (products == 1 && pair_fmt == VRD_PAIR_F16),
+                  "%s: products must be 0 or 3, or 1 with VRD_PAIR_F16 operands (got %d, pair_fmt %d)", who, products, pair_fmt);
+    VRD_CHECK_ARG(products != 1 || head_dim != 32, "%s: head_dim 32 has no one-product form (products = 1 needs head_dim 64 or 128)", who);
+    return 0;
 }
 
 }  // namespace
@@ -1471,18 +1493,10 @@ int launch_flash(FlashChoice c, int head_dim, bool f16, int products, const floa
 extern "C" int vrd_attention_pair(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                                   const uint8_t* kv_mask, const uint8_t* q_mask, int B, int Tq, int Tk, int n_head, int head_dim,
                                   float* out, int64_t ldo, int out_pair, int pair_fmt, void* stream, int products) {
-    VRD_CHECK_ARG(q && k && v && out, "vrd_attention_pair: null pointer");
-    VRD_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128, "vrd_attention_pair: head_dim must be 32, 64 or 128 (got %d)", head_dim);
-    VRD_CHECK_ARG(B > 0 && B <= 65535 && Tq > 0 && Tk > 0 && n_head > 0 && n_head <= 65535, "vrd_attention_pair: bad sizes");
+    if (int rc = check_pair_args("vrd_attention_pair", q && k && v && out, B > 0 && B <= 65535 && Tq > 0 && Tk > 0 && n_head > 0 && n_head <= 65535,
+                                 q, ldq, k, v, ldkv, n_head, head_dim, out, ldo, out_pair, pair_fmt, products))
+        return rc;
     const int width = n_head * head_dim;
-    VRD_CHECK_ARG(ldq >= width && ldkv >= width && ldo >= width && ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 &&
-                      aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out),
-                  "vrd_attention_pair: rows must be 16-byte aligned pair rows of width n_head*head_dim");
-    VRD_CHECK_ARG(pair_fmt == VRD_PAIR_BF16 || pair_fmt == VRD_PAIR_F16, "vrd_attention_pair: pair_fmt must be VRD_PAIR_BF16 or VRD_PAIR_F16");
-    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == pair_fmt, "vrd_attention_pair: pair output comes in the operands' format");
-    VRD_CHECK_ARG(products == 0 || products == 3 || (products == 1 && pair_fmt == VRD_PAIR_F16),
-                  "vrd_attention_pair: products must be 0 or 3, or 1 with VRD_PAIR_F16 operands (got %d, pair_fmt %d)", products, pair_fmt);
-    VRD_CHECK_ARG(products != 1 || head_dim != 32, "vrd_attention_pair: head_dim 32 has no one-product form (products = 1 needs head_dim 64 or 128)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool f16 = pair_fmt == VRD_PAIR_F16;
     // f16 operands hold q and k times 2^VRD_F16_ACT_EXP each: the raw scores are 2^(2 e) too large, undone in the softmax scale
@@ -1505,23 +1519,14 @@ extern "C" int vrd_attention_pair_segs(const float* q, int64_t ldq, const float*
                                        const uint8_t* kv_mask, const uint8_t* q_mask, const vrd_row_segs* qsegs,
                                        const vrd_row_segs* ksegs, int n_head, int head_dim, float* out, int64_t ldo, int out_pair,
                                        int pair_fmt, void* stream, int products) {
-    VRD_CHECK_ARG(q && k && v && out && qsegs && ksegs, "vrd_attention_pair_segs: null pointer");
-    VRD_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 128, "vrd_attention_pair_segs: head_dim must be 32, 64 or 128 (got %d)", head_dim);
-    VRD_CHECK_ARG(n_head > 0 && n_head <= 65535, "vrd_attention_pair_segs: bad sizes");
+    if (int rc = check_pair_args("vrd_attention_pair_segs", q && k && v && out && qsegs && ksegs, n_head > 0 && n_head <= 65535, q, ldq, k, v, ldkv,
+                                 n_head, head_dim, out, ldo, out_pair, pair_fmt, products))
+        return rc;
     VRD_CHECK_ARG(qsegs->count >= 1 && qsegs->count <= VRD_MAX_SEGS, "vrd_attention_pair_segs: bad row groups (%d groups, 1..%d)", qsegs->count,
                   VRD_MAX_SEGS);
     VRD_CHECK_ARG(ksegs->count == qsegs->count, "vrd_attention_pair_segs: the query and key tables disagree (%d and %d groups)", qsegs->count,
                   ksegs->count);
     const int width = n_head * head_dim;
-    VRD_CHECK_ARG(ldq >= width && ldkv >= width && ldo >= width && ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 &&
-                      aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out),
-                  "vrd_attention_pair_segs: rows must be 16-byte aligned pair rows of width n_head*head_dim");
-    VRD_CHECK_ARG(pair_fmt == VRD_PAIR_BF16 || pair_fmt == VRD_PAIR_F16, "vrd_attention_pair_segs: pair_fmt must be VRD_PAIR_BF16 or VRD_PAIR_F16");
-    VRD_CHECK_ARG(out_pair == VRD_PAIR_NONE || out_pair == pair_fmt, "vrd_attention_pair_segs: pair output comes in the operands' format");
-    VRD_CHECK_ARG(products == 0 || products == 3 || (products == 1 && pair_fmt == VRD_PAIR_F16),
-                  "vrd_attention_pair_segs: products must be 0 or 3, or 1 with VRD_PAIR_F16 operands (got %d, pair_fmt %d)", products, pair_fmt);
-    VRD_CHECK_ARG(products != 1 || head_dim != 32,
-                  "vrd_attention_pair_segs: head_dim 32 has no one-product form (products = 1 needs head_dim 64 or 128)");
     const int count = qsegs->count;
     int64_t units_w64 = 0, units_x3 = 0;
     FlashChoice choice[VRD_MAX_SEGS];

@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <type_traits>
+#include <utility>
 #include "../../include/vrdone_hip.h"
 
 namespace vrd {
@@ -76,6 +78,27 @@ __device__ __forceinline__ float4 gload4(const float* ptr) {          // 16-byte
 __device__ __forceinline__ void gstore4(void* ptr, float4 v) {        // 16-byte global store
     const f32x4_native t = {v.x, v.y, v.z, v.w};
     *as_global(reinterpret_cast<f32x4_native*>(ptr)) = t;
+}
+
+// 16 bytes of f32 through a generic pointer (global or LDS), and the host check that goes with them
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+
+// Host dispatch from a run-time value to a compile-time one.  The callable is a generic lambda; it receives a
+// std::integral_constant and names the template it wants with `decltype(x)::value`, so what gets instantiated is what the
+// lambda's body names for the listed values and nothing else.
+template <int... Vs>
+using IntList = std::integer_sequence<int, Vs...>;
+// f(integral_constant<int, V>) for the V of the list that equals v; false (f not called) if none does
+template <int... Vs, class F>
+bool pick_of(IntList<Vs...>, int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F>
+void pick_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // Device address of the current device's f16 operand-range flag word (vrd_f16_range_flag of the ABI), or nullptr

@@ -1,6 +1,6 @@
 // Training dropout on f32 rows (reference models/blocks.py:988,1057,1059: proj_drop and the two MLP dropouts of a
 // TransformerBlock).  No mask is stored: forward and backward compute the keep decisions from (seed, site, element id)
-// (vrd_philox.h; host mirror vrdone_amd/dropout.py).  The banded attention's attn_drop lives with its kernels (vrd_backward.hip).
+// (vrd_philox.h; host mirror vrdone_amd/dropout.py).  The banded attention's attn_drop lives with its kernels (vrd_local_attn_bwd.hip).
 //
 //  vrd_dropout_mask   the keep decisions of n consecutive ids as bytes: what the tests pin against the host mirror
 //  vrd_dropout_rows   out[r, c] = x[r, c] * keep(id) / (1 - p), id = (row0 + r) * C + c: the forward, and on dy the backward.
@@ -9,7 +9,7 @@
 
 namespace {
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+using vrd::aligned16;
 
 __global__ __launch_bounds__(256) void dropout_mask_kernel(vrd::DropSite d, uint64_t first_id, int64_t n, uint8_t* __restrict__ keep) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

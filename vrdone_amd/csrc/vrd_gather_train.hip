@@ -17,7 +17,7 @@ namespace {
 constexpr int GT_FRAMES = 8;
 enum RowMode { ROWS_SCALAR = 0, ROWS_UNALIGNED = 1, ROWS_ALIGNED = 2 };
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+using vrd::aligned16;
 
 template <bool A16>
 __device__ __forceinline__ float4 ldv4(const float* p) {

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, VRD_F32_WAVES) void gemm_f32_mfma_kernel(vrd_g
     vrd::gemm_epilogue<STAGED>(p, acc, smem, wm ? brow[2] : brow[0], n0 + wn * 64, wave, lane, rflag, wm ? brow[3] : brow[1]);
 }
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+using vrd::aligned16;
 
 template <bool VEC, int TAPS, int BK, bool STAGED>
 int launch_variant(const vrd_gemm_args& a, int tiles_m, int tiles_n, hipStream_t s) {

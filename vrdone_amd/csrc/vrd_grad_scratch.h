@@ -11,8 +11,6 @@
 
 namespace vrd {
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
-
 // default mode: partial sums go through the scratch only when it holds them
 inline bool scratch_holds(const float* scratch, int64_t scratch_floats, int64_t need) {
     return scratch && aligned16(scratch) && scratch_floats >= need;

@@ -13,8 +13,8 @@ namespace {
 
 constexpr float LN_EPS = 1e-5f;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+using vrd::ld4;
+using vrd::st4;
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // ------------------------------------------------------------------------------------------
@@ -965,7 +965,7 @@ __global__ __launch_bounds__(256) void mask_head_groups_kernel(const float* __re
     }
 }
 
-inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+using vrd::aligned16;
 
 // ---- padding map: 32-row blocks dealt into segments of seg_len list entries (the last one may be shorter), inside a
 // segment the blocks with a valid row first (one workgroup; rows/32 is a few ten thousand at most).  Thread t owns a

@@ -15,7 +15,7 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using vrd::aligned16;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using vrd::ld4;
 
 // ------------------------------------------------------------------------------------------------------------------
 // dW[n, j] += sum_{r in chunk} G[r, n] * X[r + tap(j) - taps/2, ci(j)],  j = tap*Cin + ci, rows outside the length-T
