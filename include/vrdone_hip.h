@@ -752,6 +752,13 @@ int vrd_colsum(const float* a, int64_t lda, const float* b, int64_t ldb, int b_c
 int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
                      const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch, int64_t scratch_floats,
                      void* stream, int flags);
+/* The same with the conv's INPUT rows given as the groups of `segs` (host memory, see vrd_row_segs; T[i] and row[i] multiples of
+ * stride): group i's dD / row_mask rows start at row[i] / stride, its n[i] sequences of T[i] / stride output frames one behind the
+ * other, and the taps end at the sequences' own ends.  The sums run over the rows of all groups in one launch; rows between or
+ * behind the groups are not read.  scratch and flags as above, with rows = the groups' output rows. */
+int vrd_dwconv_wgrad_segs(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in,
+                          const vrd_row_segs* segs, const uint8_t* row_mask, int C, float* dw, float* dbias, float* scratch,
+                          int64_t scratch_floats, void* stream, int flags);
 
 /* out[r,c] = v[r,c] * col_scale[c] * row_scale[r] * row_mask[r] + res[r,c] * (res_masked ? row_mask[r] : 1) + res2[r,c]
  * (every factor / term optional).  Training form of the affine drop-path residual: models/blocks.py:1074-1076 with
@@ -788,6 +795,11 @@ typedef struct {
     float* dx_up;  int64_t lddx_up;
 } vrd_dwconv_bwd_args;
 int vrd_dwconv_bwd(const vrd_dwconv_bwd_args* a, void* stream);
+/* The same over a ragged row space in one launch: the INPUT rows (dx) are the groups of `segs` (host memory) under the rules of
+ * vrd_dwconv_ln_args.segs -- T[i] % stride == 0; row[i] and T[i] even when dx_up or stride 2 is used; group i's dD / mask_out rows
+ * start at row[i] / stride, its dx_up rows at row[i] / 2.  a->B and a->Tin are ignored.  Every row written has the bits of
+ * vrd_dwconv_bwd called on its group alone; rows between or behind the groups are neither read nor written. */
+int vrd_dwconv_bwd_segs(const vrd_dwconv_bwd_args* a, const vrd_row_segs* segs, void* stream);
 
 /* Banded attention backward (vrd_local_attn; models/blocks.py:950-986): dq, dk, dv (leading dimension ldd) from the
  * forward inputs and dO.  scratch: 2 * B*T * n_head * (2*half_win+1) floats; on return its second half holds dS
@@ -796,6 +808,15 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
                        const uint8_t* mask, const float* rel_pe, int B, int T, int C, int n_head, int half_win,
                        float* dq, float* dk, float* dv,
                        int64_t ldd, float* scratch, void* stream);
+/* The same over a ragged row space (segs: host memory, see vrd_row_segs) in one launch per pass; the shapes served and the
+ * refusals are vrd_local_attn_bwd's.  Every dq / dk / dv row of a group has the bits of vrd_local_attn_bwd called on that group
+ * alone; rows between or behind the groups are neither read nor written.  scratch: 2 * R * n_head * (2*half_win+1) floats, R =
+ * the rows the groups span (first row of the first group to the end of the last: a caller sizes it without walking the table).
+ * Its second half starts with dS of the groups' frames, counted through the groups in order without gaps: [F][n_head][2*half_win+1],
+ * F = sum n[i] * T[i] <= R -- d rel_pe is still one sum over rows. */
+int vrd_local_attn_bwd_segs(const float* q, const float* k, const float* v, int64_t ld, const float* dO, int64_t lddo,
+                            const uint8_t* mask, const float* rel_pe, const vrd_row_segs* segs, int C, int n_head, int half_win,
+                            float* dq, float* dk, float* dv, int64_t ldd, float* scratch, void* stream);
 
 /* ---- training dropout (models/blocks.py:975-979,988,1057,1059: attn_drop, proj_drop and the two MLP dropouts of a
  * TransformerBlock).  No mask is stored between forward and backward: a keep decision is a pure function of
@@ -877,6 +898,11 @@ int vrd_bmm(const vrd_bmm_args* a, void* stream);
  * the first maximum of each window (ATen's rule). */
 int vrd_maxpool_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, int B, int Tin, int C, const uint8_t* mask_in, float* dx,
                     int64_t lddx, void* stream);
+/* The same over a ragged row space in one launch: x / mask_in / dx are the rows of the groups of `segs` (host memory; T[i] and
+ * row[i] even), group i's dy rows start at row[i] / 2.  Bit for bit vrd_maxpool_bwd group by group; rows between or behind the
+ * groups are neither read nor written. */
+int vrd_maxpool_bwd_segs(const float* x, int64_t ldx, const float* dy, int64_t lddy, const vrd_row_segs* segs, int C,
+                         const uint8_t* mask_in, float* dx, int64_t lddx, void* stream);
 
 /* ---- training tail on the device ----------------------------------------------------------------------
  * Hungarian assignment of the matcher (models/maskvrd.py:484-492: `.cpu()` + scipy linear_sum_assignment per pair).

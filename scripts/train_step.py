@@ -99,8 +99,10 @@ def synthetic_entries(cfg, n_pairs, seed=0, keys_per_video=4):
 
 def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, ema_decay=0.999, verbose=True, drop_path=True,
         graphs=False, config="vidvrd", n_pairs=24, profile=False, deterministic=False, fused_tail=False, torch_fused=False,
-        feed=None, heads=None, dropattn=0.0, dropout=0.0):
-    """dropattn / dropout: the config's attention / projection dropout rates (the backbone's TransformerBlocks).
+        feed=None, heads=None, dropattn=0.0, dropout=0.0, rows=False, rows_min_rows=None):
+    """rows: MaskVRD.train_rows -- steps that qualify run in the row space (log["train_form"], ["buckets"] = [[pairs, frames, flat]],
+    ["rows_computed"] against ["rows_padded"] of the last step); rows_min_rows: MaskVRD.TRAIN_ROWS_MIN_ROWS.
+    dropattn / dropout: the config's attention / projection dropout rates (the backbone's TransformerBlocks).
     heads: n_head = fuse_head of the config replaced (16 at width 512: head_dim 32 in the SOS layers' global attention).
     feed: None (one fixed synthetic batch), "lists" or "source" (per step from synthetic cache entries, see the module text).
     fused_tail: clip + AdamW as vrdone_amd.optim.FusedAdamW.step(max_grad_norm=clip) (three launches) instead of torch's
@@ -124,6 +126,9 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
                 mod.drop_prob = 0.0
     if graphs:
         model.enable_training_graphs()        # forward + backward of the network as two HIP-graph replays (train_graph.py)
+    model.train_rows = bool(rows)
+    if rows_min_rows is not None:
+        model.TRAIN_ROWS_MIN_ROWS = int(rows_min_rows)
     from vrdone_amd.ema import ModelEma
     ema = ModelEma(model, decay=ema_decay)                                # one-launch EMA (vrd_ema_update), same values
     if fused_tail:
@@ -200,6 +205,17 @@ def run(steps=3, seed=0, device="cuda", lr=1e-4, weight_decay=0.05, clip=1.0, em
         if verbose:
             fed = f"  data {log['data_ms'][-1]:.1f} ms" if feed is not None else ""
             print(f"step {step}: total_loss {log['total_loss'][-1]:.4f}  ({log['step_ms'][-1]:.1f} ms){fed}", flush=True)
+    if rows:
+        lens = [int(f.shape[1]) for f in data["so_features_list"]] if "so_features_list" in data else []
+        plan = model.train_rows_plan(lens) if model.train_form == "rows" else []
+        log["train_form"] = model.train_form
+        log["buckets"] = [[len(ids), t, flat] for t, ids, flat in plan]
+        log["rows_padded"] = len(lens) * cfg["max_seq_len"]
+        log["rows_computed"] = sum(len(ids) * t for t, ids, _ in plan) if plan else log["rows_padded"]
+        if verbose:
+            print(f"train_form {model.train_form}: buckets (pairs x frames) " + ", ".join(f"{n} x {t}" + ("" if flat else " (not flat)")
+                                                                                          for n, t, flat in log["buckets"]) +
+                  f"; rows computed / padded {log['rows_computed']} / {log['rows_padded']}", flush=True)
     if profile:
         prof = _hip.prof_read()
         _hip.prof_enable(False)
@@ -245,9 +261,11 @@ if __name__ == "__main__":
     ap.add_argument("--heads", type=int, help="n_head and fuse_head of the config (16: head_dim 32 at width 512)")
     ap.add_argument("--dropattn", type=float, default=0.0, help="the config's `dropattn`: dropout on the banded attention's probabilities")
     ap.add_argument("--dropout", type=float, default=0.0, help="the config's `dropout`: projection and MLP dropout of the TransformerBlocks")
+    ap.add_argument("--rows", action="store_true", help="MaskVRD.train_rows: ragged batches in one row space; prints train_form and the bucket table")
+    ap.add_argument("--rows-min-rows", type=int, help="MaskVRD.TRAIN_ROWS_MIN_ROWS, the bucket-merging threshold of the training plan")
     args = ap.parse_args()
     assert not (args.device_source and args.entry_lists)
     print(json.dumps(run(steps=args.steps, seed=args.seed, graphs=args.graphs, config=args.config, n_pairs=args.pairs, profile=args.profile,
                          deterministic=args.deterministic, fused_tail=args.fused_tail, torch_fused=args.torch_fused,
                          feed="source" if args.device_source else "lists" if args.entry_lists else None, heads=args.heads,
-                         dropattn=args.dropattn, dropout=args.dropout)))
+                         dropattn=args.dropattn, dropout=args.dropout, rows=args.rows, rows_min_rows=args.rows_min_rows)))

@@ -299,6 +299,14 @@ _SIGNATURES = {
     "vrd_criterion_backward": (C.c_int, [C.c_void_p, c_i32p, c_f32p, C.c_float, c_f32p, c_f32p, C.c_void_p, C.c_void_p]),
     "vrd_maxpool_bwd": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, c_u8p, c_f32p, C.c_int64,
                                   C.c_void_p]),
+    # ---- the sequence-walking backward kernels over a ragged row space (vrd_row_segs): a training step in the row space
+    "vrd_local_attn_bwd_segs": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, c_u8p, c_f32p, C.POINTER(RowSegs),
+                                          C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
+    "vrd_dwconv_bwd_segs": (C.c_int, [C.POINTER(DwconvBwdArgs), C.POINTER(RowSegs), C.c_void_p]),
+    "vrd_dwconv_wgrad_segs": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(RowSegs), c_u8p,
+                                        C.c_int, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int]),
+    "vrd_maxpool_bwd_segs": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.POINTER(RowSegs), C.c_int, c_u8p, c_f32p, C.c_int64,
+                                       C.c_void_p]),
 }
 
 ABI_VERSION = 37

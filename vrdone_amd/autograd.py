@@ -374,17 +374,32 @@ class LayerNormFn(_Differentiable):
         return dx, dg.view_as(gamma), db.view_as(beta), None, dpost
 
 
+def _row_segs(segs):
+    """the vrd_row_segs of the row groups [(first row, sequences, frames)] of a Function in the row space (one launch takes them all)"""
+    assert 1 <= len(segs) <= _hip.MAX_SEGS, f"a differentiable op takes up to {_hip.MAX_SEGS} row groups (got {len(segs)})"
+    return C.byref(_hip.RowSegs.of(segs))
+
+
+def _group(t, off, n, T):
+    """rows [off, off + n T) of the (1, R, ...) tensor t as (n, T, ...): a view for a launch on pointer offsets (never recorded)"""
+    return None if t is None else t[0, off:off + n * T].unflatten(0, (n, T))
+
+
 class DepthwiseConv(_Differentiable):
     """D_o = mask_out * (bias_o + depthwise_conv(x (+ up2(x_up)); w_o)) for 1..3 weight sets (vrd_dwconv_ln without
-    LayerNorm).  args after the fixed ones: w_0, b_0, w_1, b_1, ... (b_i may be None)."""
+    LayerNorm).  args after the fixed ones: w_0, b_0, w_1, b_1, ... (b_i may be None).
+    segs: None, or the row groups [(first row, sequences, frames)] of x (1, R, C) in a row space (models/ragged.py); outputs,
+    mask_out and x_up follow them at their own frame counts, and every gradient is one (1, rows, C) tensor."""
 
     @staticmethod
-    def forward(ctx, x, x_up, mask_out, stride, *wb):
+    def forward(ctx, x, x_up, mask_out, stride, segs, *wb):
         ws, bs = wb[0::2], wb[1::2]
-        outs = ops.dwconv_ln(x, [dict(weight=w, bias=b) for w, b in zip(ws, bs)], mask_out=mask_out, stride=stride, x_up=x_up)
+        outs = ops.dwconv_ln(x, [dict(weight=w, bias=b) for w, b in zip(ws, bs)], mask_out=mask_out, stride=stride, x_up=x_up,
+                             segs=segs)
         ctx.save_for_backward(x, *( [x_up] if x_up is not None else [] ), *ws)
         ctx.has_up, ctx.mask_out, ctx.stride, ctx.has_bias = x_up is not None, mask_out, stride, [b is not None for b in bs]
         ctx.det = ops.get_deterministic()
+        ctx.segs = None if segs is None else list(segs)
         return tuple(outs)
 
     @staticmethod
@@ -412,7 +427,10 @@ class DepthwiseConv(_Differentiable):
         if ctx.has_up:
             dx_up = torch.empty(B, Tin // 2, Cx, device=dev, dtype=torch.float32)
             a.dx_up, a.lddx_up = dx_up.data_ptr(), Cx
-        check(lib.vrd_dwconv_bwd(C.byref(a), _stream()), "vrd_dwconv_bwd")
+        if ctx.segs is not None:
+            check(lib.vrd_dwconv_bwd_segs(C.byref(a), _row_segs(ctx.segs), _stream()), "vrd_dwconv_bwd_segs")
+        else:
+            check(lib.vrd_dwconv_bwd(C.byref(a), _stream()), "vrd_dwconv_bwd")
         # the conv's input, for the weight gradients: x + nearest-x2-upsampled x_up (the copy is torch's, the add a kernel)
         xin = x if x_up is None else rowcol_scale(x, res2=x_up.repeat_interleave(2, dim=1))
         grads = []
@@ -423,22 +441,30 @@ class DepthwiseConv(_Differentiable):
             gb = _zeros(Cout, device=dev) if ctx.has_bias[i] else None
             pd, rows_out, _, ldd = _rows(dDs[i])
             pgb = gb.data_ptr() if gb is not None else None
-            _grad_call(dev, ctx.det, lambda part: lib.vrd_dwconv_wgrad(
-                pd, ldd, pxin, ldxin, k, s, gin, Tout, _mask_ptr(ctx.mask_out, rows_out), rows_out, Cout, gw.data_ptr(), pgb,
-                part.data_ptr(), part.numel(), _stream(), _flags(ctx.det)), "vrd_dwconv_wgrad")
+            if ctx.segs is not None:
+                _grad_call(dev, ctx.det, lambda part: lib.vrd_dwconv_wgrad_segs(
+                    pd, ldd, pxin, ldxin, k, s, gin, _row_segs(ctx.segs), _mask_ptr(ctx.mask_out, rows_out), Cout, gw.data_ptr(), pgb,
+                    part.data_ptr(), part.numel(), _stream(), _flags(ctx.det)), "vrd_dwconv_wgrad_segs")
+            else:
+                _grad_call(dev, ctx.det, lambda part: lib.vrd_dwconv_wgrad(
+                    pd, ldd, pxin, ldxin, k, s, gin, Tout, _mask_ptr(ctx.mask_out, rows_out), rows_out, Cout, gw.data_ptr(), pgb,
+                    part.data_ptr(), part.numel(), _stream(), _flags(ctx.det)), "vrd_dwconv_wgrad")
             grads.append(gw)
             grads.append(gb)
-        return (dx, dx_up, None, None, *grads)
+        return (dx, dx_up, None, None, None, *grads)
 
 
 class LocalAttention(_Differentiable):
     @staticmethod
-    def forward(ctx, q, k, v, mask, n_head, half_win, rel_pe=None, drop=None):
+    def forward(ctx, q, k, v, mask, n_head, half_win, rel_pe=None, drop=None, segs=None):
         """drop: None, or the attn_drop call (models.blocks.Drop) -- dropout on the window probabilities, forward and backward on
-        the kernels that compute the keep decisions from (seed, site, row, head, slot)."""
+        the kernels that compute the keep decisions from (seed, site, row, head, slot).
+        segs: None, or the row groups of q / k / v / mask (1, R, ...) in a row space (p = 0 only)."""
         rel = None if rel_pe is None else rel_pe.detach()
+        assert segs is None or drop is None, "attention dropout counts batch rows: the row space runs at p = 0"
+        ctx.segs = None if segs is None else list(segs)
         if drop is None:
-            out = ops.local_attention(q, k, v, mask, n_head, half_win, rel_pe=rel)
+            out = ops.local_attention(q, k, v, mask, n_head, half_win, rel_pe=rel, segs=segs)
         else:
             B, T, Cc = q.shape
             pq, rows, _, ld = _rows(q)
@@ -463,7 +489,13 @@ class LocalAttention(_Differentiable):
         dq, dk, dv = (torch.empty(B, T, Cc, device=q.device, dtype=torch.float32) for _ in range(3))
         scratch = torch.empty(2 * B * T * ctx.n_head * W, device=q.device, dtype=torch.float32)
         d = ctx.drop
-        if d is None:
+        if ctx.segs is not None:
+            # (the layout's groups cover all B * T = R rows: the scratch's dS rows are the rows)
+            check(lib.vrd_local_attn_bwd_segs(q.data_ptr(), k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc, _mask_ptr(ctx.mask, B * T),
+                                              ops._rel_pe_ptr(rel, q, ctx.n_head, ctx.half_win), _row_segs(ctx.segs), Cc, ctx.n_head,
+                                              ctx.half_win, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Cc, scratch.data_ptr(), _stream()),
+                  "vrd_local_attn_bwd_segs")
+        elif d is None:
             check(lib.vrd_local_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc, _mask_ptr(ctx.mask, B * T),
                                          ops._rel_pe_ptr(rel, q, ctx.n_head, ctx.half_win), B, T, Cc, ctx.n_head, ctx.half_win,
                                          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), Cc, scratch.data_ptr(), _stream()),
@@ -476,7 +508,7 @@ class LocalAttention(_Differentiable):
         d_rel = None
         if rel is not None and ctx.needs_input_grad[6]:      # the bias is added to every row's scores: d rel_pe = sum of dS
             d_rel = scratch[B * T * ctx.n_head * W:].view(B * T, ctx.n_head, W).sum(0).view(rel.shape)
-        return dq, dk, dv, None, None, None, d_rel, None
+        return dq, dk, dv, None, None, None, d_rel, None, None
 
 
 def _flash_attention_route(split, head_dim, Tq, Tk):
@@ -490,84 +522,125 @@ def _flash_attention_route(split, head_dim, Tq, Tk):
     return bool(FUSED_ATTN_BWD and split and head_dim in (32, 64) and Tq >= 32 and Tk >= 32)
 
 
+def _attention_fwd(q, k, v, kv_mask, n_head, split, out=None):
+    """Global attention of q (B, Tq, C) over k / v (B, Tk, C), contiguous f32 rows -> (out, lse): on the route
+    _flash_attention_route picks for the shape; lse (B, n_head, Tq): the flash route's log-sum-exp per query, else None.
+    out: the contiguous rows to write (a group's slice of a row space's output), fresh when None."""
+    B, Tq, Cc = q.shape
+    Tk = k.shape[1]
+    if (_flash_attention_route(split, Cc // n_head, Tq, Tk) and
+            q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        # the split-precision flash forward on f32 rows (operands split while they are staged), which keeps every query's
+        # log-sum-exp for the backward
+        if out is None:
+            out = torch.empty_like(q)
+        lse = torch.empty(B, n_head, Tq, device=q.device, dtype=torch.float32)
+        check(lib.vrd_attention_rows(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, _mask_ptr(kv_mask, B * Tk), B, Tq, Tk, n_head,
+                                     Cc // n_head, ops.pair_fmt(), out.data_ptr(), Cc, lse.data_ptr(), _stream()), "vrd_attention_rows")
+        return out, lse
+    return ops.attention(q, k, v, kv_mask, n_head, out=out), None
+
+
+def _attention_bwd(q, k, v, out, dO, kv_mask, H, lse, split_bwd, bfmt, dq, dk, dv):
+    """dq, dk, dv (contiguous rows to write) of _attention_fwd from its operands, its result and dO, all contiguous (B, T, C)"""
+    B, Tq, Cc = q.shape
+    Tk = k.shape[1]
+    hd = Cc // H
+    dev = q.device
+    if _flash_attention_route(split_bwd, hd, Tq, Tk):
+        # flash style (vrd_attention_bwd): the scores are recomputed tile by tile in the split of the other backward GEMMs
+        # (bf16 planes; f16x3 mode: f16 planes, dO and dS at power-of-two factors from the absolute maxima of dO and v);
+        # no (B, H, Tq, Tk) matrix exists
+        scratch = torch.empty(2, B, H, Tq, device=dev, dtype=torch.float32)
+        so = sv = None
+        if bfmt == PAIR_F16:
+            so = ops.grad_scale(dO, slot=0)
+            sv = ops.grad_scale(v, slot=1) if so is not None else None
+            if sv is None:
+                so = None
+        check(lib.vrd_attention_bwd(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, out.data_ptr(), dO.data_ptr(), Cc,
+                                    _mask_ptr(kv_mask, B * Tk), B, Tq, Tk, H, hd, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                                    _ptr(lse), scratch.data_ptr(), _ptr(so), _ptr(sv), _stream()), "vrd_attention_bwd")
+        return
+    P = torch.empty(B, H, Tq, Tk, device=dev, dtype=torch.float32)
+    dS = torch.empty(B, H, Tq, Tk, device=dev, dtype=torch.float32)
+    scale = hd ** -0.5
+    sc = (H * Tq * Tk, Tq * Tk)                   # z strides of P / dS
+    row_q, row_k = (Tq * Cc, hd), (Tk * Cc, hd)   # z strides of (B, T, H*hd) operands
+    if Tq >= 32 and Tk >= 32:
+        # long sequences: scores and dP as matrix products on the matrix cores (vrd_bmm), then softmax / dS row by row
+        bmm(q, (*row_q, Cc, 1), k, (*row_k, 1, Cc), P, (*sc, Tk, 1), B, H, Tq, Tk, hd, alpha=scale)       # S = scale Q K^T
+        bmm(dO, (*row_q, Cc, 1), v, (*row_k, 1, Cc), dS, (*sc, Tk, 1), B, H, Tq, Tk, hd)                  # dP = dO V^T
+        check(lib.vrd_attn_bwd_softmax(P.data_ptr(), dS.data_ptr(), _mask_ptr(kv_mask, B * Tk), B, Tq, Tk, H, _stream()),
+              "vrd_attn_bwd_softmax")
+    else:
+        check(lib.vrd_attn_bwd_probs(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc,
+                                     _mask_ptr(kv_mask, B * Tk), B, Tq, Tk, H, hd, P.data_ptr(), dS.data_ptr(), _stream()),
+              "vrd_attn_bwd_probs")
+    # dq[b, i, h, :] = scale * sum_j dS[b,h,i,j] k[b,j,h,:]
+    bmm(dS, (*sc, Tk, 1), k, (*row_k, Cc, 1), dq, (*row_q, Cc, 1), B, H, Tq, hd, Tk, alpha=scale)
+    # dk[b, j, h, :] = scale * sum_i dS[b,h,i,j] q[b,i,h,:]
+    bmm(dS, (*sc, 1, Tk), q, (*row_q, Cc, 1), dk, (*row_k, Cc, 1), B, H, Tk, hd, Tq, alpha=scale)
+    # dv[b, j, h, :] = sum_i P[b,h,i,j] dO[b,i,h,:]
+    bmm(P, (*sc, 1, Tk), dO, (*row_q, Cc, 1), dv, (*row_k, Cc, 1), B, H, Tk, hd, Tq)
+
+
 class Attention(_Differentiable):
-    """Global masked attention (f32 kernels of vrd_attention)."""
+    """Global masked attention (f32 kernels of vrd_attention).
+    segs: None, or (qsegs, ksegs): q (1, Rq, C) and k / v / kv_mask (1, Rk, ...) are row spaces of the groups qsegs / ksegs =
+    [(first row, sequences, frames)] (models/ragged.py; the same sequences per group on both sides).  Forward and backward then
+    launch the batch form's entry points group by group on pointer offsets -- every group on the route its own shape takes --,
+    each writing its slice of ONE out / dq / dk / dv."""
 
     @staticmethod
-    def forward(ctx, q, k, v, kv_mask, n_head):
-        B, Tq, Cc = q.shape
-        Tk = k.shape[1]
-        lse = None
-        if (_flash_attention_route(ops.split_backward(), Cc // n_head, Tq, Tk) and
-                q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
-            # the split-precision flash forward on f32 rows (operands split while they are staged), which keeps every query's
-            # log-sum-exp for the backward
-            out = torch.empty_like(q)
-            lse = torch.empty(B, n_head, Tq, device=q.device, dtype=torch.float32)
-            check(lib.vrd_attention_rows(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, _mask_ptr(kv_mask, B * Tk), B, Tq, Tk, n_head,
-                                         Cc // n_head, ops.pair_fmt(), out.data_ptr(), Cc, lse.data_ptr(), _stream()), "vrd_attention_rows")
+    def forward(ctx, q, k, v, kv_mask, n_head, segs=None):
+        split = ops.split_backward()
+        if segs is None:
+            out, lse = _attention_fwd(q, k, v, kv_mask, n_head, split)
         else:
-            out = ops.attention(q, k, v, kv_mask, n_head)
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            out, lse = torch.empty_like(q), []
+            for qs, ks in zip(*segs):
+                assert qs[1] == ks[1]
+                lse.append(_attention_fwd(_group(q, *qs), _group(k, *ks), _group(v, *ks), _group(kv_mask, *ks), n_head, split,
+                                          _group(out, *qs))[1])
         ctx.save_for_backward(q, k, v, out)
         ctx.kv_mask, ctx.n_head, ctx.lse = kv_mask, n_head, lse
-        ctx.split_bwd, ctx.bfmt = ops.split_backward(), ops.backward_fmt()          # (as in Linear: the backward follows its forward's mode)
+        ctx.split_bwd, ctx.bfmt = split, ops.backward_fmt()          # (as in Linear: the backward follows its forward's mode)
+        ctx.segs = None if segs is None else (list(segs[0]), list(segs[1]))
         return out
 
     @staticmethod
     def backward(ctx, dO):
         q, k, v, out = (t.contiguous() for t in ctx.saved_tensors)
         dO = dO.contiguous()
-        B, Tq, Cc = q.shape
-        Tk, H = k.shape[1], ctx.n_head
-        hd = Cc // H
-        dev = q.device
-        if _flash_attention_route(ctx.split_bwd, hd, Tq, Tk):
-            # flash style (vrd_attention_bwd): the scores are recomputed tile by tile in the split of the other backward GEMMs
-            # (bf16 planes; f16x3 mode: f16 planes, dO and dS at power-of-two factors from the absolute maxima of dO and v);
-            # no (B, H, Tq, Tk) matrix exists
-            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-            scratch = torch.empty(2, B, H, Tq, device=dev, dtype=torch.float32)
-            so = sv = None
-            if ctx.bfmt == PAIR_F16:
-                so = ops.grad_scale(dO, slot=0)
-                sv = ops.grad_scale(v, slot=1) if so is not None else None
-                if sv is None:
-                    so = None
-            check(lib.vrd_attention_bwd(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, out.data_ptr(), dO.data_ptr(), Cc,
-                                        _mask_ptr(ctx.kv_mask, B * Tk), B, Tq, Tk, H, hd, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                                        _ptr(ctx.lse), scratch.data_ptr(), _ptr(so), _ptr(sv), _stream()), "vrd_attention_bwd")
-            return dq, dk, dv, None, None
-        P = torch.empty(B, H, Tq, Tk, device=dev, dtype=torch.float32)
-        dS = torch.empty(B, H, Tq, Tk, device=dev, dtype=torch.float32)
-        scale = hd ** -0.5
-        sc = (H * Tq * Tk, Tq * Tk)                   # z strides of P / dS
-        row_q, row_k = (Tq * Cc, hd), (Tk * Cc, hd)   # z strides of (B, T, H*hd) operands
-        if Tq >= 32 and Tk >= 32:
-            # long sequences: scores and dP as matrix products on the matrix cores (vrd_bmm), then softmax / dS row by row
-            bmm(q, (*row_q, Cc, 1), k, (*row_k, 1, Cc), P, (*sc, Tk, 1), B, H, Tq, Tk, hd, alpha=scale)       # S = scale Q K^T
-            bmm(dO, (*row_q, Cc, 1), v, (*row_k, 1, Cc), dS, (*sc, Tk, 1), B, H, Tq, Tk, hd)                  # dP = dO V^T
-            check(lib.vrd_attn_bwd_softmax(P.data_ptr(), dS.data_ptr(), _mask_ptr(ctx.kv_mask, B * Tk), B, Tq, Tk, H, _stream()),
-                  "vrd_attn_bwd_softmax")
-        else:
-            check(lib.vrd_attn_bwd_probs(q.data_ptr(), Cc, k.data_ptr(), v.data_ptr(), Cc, dO.data_ptr(), Cc,
-                                         _mask_ptr(ctx.kv_mask, B * Tk), B, Tq, Tk, H, hd, P.data_ptr(), dS.data_ptr(), _stream()),
-                  "vrd_attn_bwd_probs")
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        # dq[b, i, h, :] = scale * sum_j dS[b,h,i,j] k[b,j,h,:]
-        bmm(dS, (*sc, Tk, 1), k, (*row_k, Cc, 1), dq, (*row_q, Cc, 1), B, H, Tq, hd, Tk, alpha=scale)
-        # dk[b, j, h, :] = scale * sum_i dS[b,h,i,j] q[b,i,h,:]
-        bmm(dS, (*sc, 1, Tk), q, (*row_q, Cc, 1), dk, (*row_k, Cc, 1), B, H, Tk, hd, Tq, alpha=scale)
-        # dv[b, j, h, :] = sum_i P[b,h,i,j] dO[b,i,h,:]
-        bmm(P, (*sc, 1, Tk), dO, (*row_q, Cc, 1), dv, (*row_k, Cc, 1), B, H, Tk, hd, Tq)
-        return dq, dk, dv, None, None
+        if ctx.segs is None:
+            _attention_bwd(q, k, v, out, dO, ctx.kv_mask, ctx.n_head, ctx.lse, ctx.split_bwd, ctx.bfmt, dq, dk, dv)
+        else:
+            for qs, ks, lse in zip(*ctx.segs, ctx.lse):
+                _attention_bwd(_group(q, *qs), _group(k, *ks), _group(v, *ks), _group(out, *qs), _group(dO, *qs),
+                               _group(ctx.kv_mask, *ks), ctx.n_head, lse, ctx.split_bwd, ctx.bfmt,
+                               _group(dq, *qs), _group(dk, *ks), _group(dv, *ks))
+        return dq, dk, dv, None, None, None
 
 
 class MaxPoolMask(_Differentiable):
     @staticmethod
-    def forward(ctx, x, mask_in):
-        y, m_out = ops.maxpool_mask(x, mask_in)
+    def forward(ctx, x, mask_in, segs=None):
+        """segs: None, or the row groups of x (1, R, C) / mask_in (1, R) in a row space; the results' rows follow them at half
+        the frames."""
+        if segs is None:
+            y, m_out = ops.maxpool_mask(x, mask_in)
+        else:
+            y = torch.empty(1, x.shape[1] // 2, x.shape[2], device=x.device, dtype=torch.float32)
+            m_out = torch.empty(1, x.shape[1] // 2, device=x.device, dtype=torch.bool)
+            for off, n, T in segs:
+                ops.maxpool_mask(_group(x, off, n, T), _group(mask_in, off, n, T),
+                                 out=(_group(y, off // 2, n, T // 2), _group(m_out, off // 2, n, T // 2)))
         ctx.save_for_backward(x)
         ctx.mask_in = mask_in
+        ctx.segs = None if segs is None else list(segs)
         ctx.mark_non_differentiable(m_out)
         return y, m_out
 
@@ -579,30 +652,57 @@ class MaxPoolMask(_Differentiable):
         px, _, _, ldx = _rows(x)
         pd, _, _, ldd = _rows(dy)
         dx = torch.empty(B, T, Cc, device=x.device, dtype=torch.float32)
-        check(lib.vrd_maxpool_bwd(px, ldx, pd, ldd, B, T, Cc, _mask_ptr(ctx.mask_in, B * T), dx.data_ptr(), Cc, _stream()),
-              "vrd_maxpool_bwd")
-        return dx, None
+        if ctx.segs is not None:
+            check(lib.vrd_maxpool_bwd_segs(px, ldx, pd, ldd, _row_segs(ctx.segs), Cc, _mask_ptr(ctx.mask_in, B * T), dx.data_ptr(), Cc,
+                                           _stream()), "vrd_maxpool_bwd_segs")
+        else:
+            check(lib.vrd_maxpool_bwd(px, ldx, pd, ldd, B, T, Cc, _mask_ptr(ctx.mask_in, B * T), dx.data_ptr(), Cc, _stream()),
+                  "vrd_maxpool_bwd")
+        return dx, None, None
+
+
+def _mask_head_bwd(emb, feat, out_mask, dseg, demb, dfeat):
+    """demb (B, Q, Dp), dfeat (B, T, Dp) (contiguous rows to write) of seg = ops.mask_head(emb, feat, out_mask) from dseg (B, Q, T)"""
+    B, Q, Dp = emb.shape
+    T = feat.shape[1]
+    g = dseg.masked_fill(~out_mask[:, None, :].bool(), 0.0).contiguous()    # filled frames carry no gradient
+    # demb[b, q, :] = sum_t g[b,q,t] feat[b,t,:];  dfeat[b, t, :] = sum_q g[b,q,t] emb[b,q,:]
+    bmm(g, (Q * T, 0, T, 1), feat, (T * Dp, 0, Dp, 1), demb, (Q * Dp, 0, Dp, 1), B, 1, Q, Dp, T)
+    bmm(g, (Q * T, 0, 1, T), emb, (Q * Dp, 0, Dp, 1), dfeat, (T * Dp, 0, Dp, 1), B, 1, T, Dp, Q)
 
 
 class MaskHead(_Differentiable):
-    @staticmethod
-    def forward(ctx, emb, feat, out_mask, fill):
-        seg = ops.mask_head(emb, feat, out_mask, fill)
-        ctx.save_for_backward(emb, feat)
-        ctx.out_mask = out_mask
-        return seg
+    """segs: None, or the row groups of feat (1, R, Dp) / out_mask (1, R) in a row space, emb (B, Q, Dp) the groups' sequences in
+    order: the result is then one (n_i, Q, T_i) tensor per group, and backward writes every group's slice of ONE demb / dfeat."""
 
     @staticmethod
-    def backward(ctx, dseg):
+    def forward(ctx, emb, feat, out_mask, fill, segs=None):
+        ctx.save_for_backward(emb, feat)
+        ctx.out_mask = out_mask
+        ctx.segs = None if segs is None else list(segs)
+        if segs is None:
+            return ops.mask_head(emb, feat, out_mask, fill)
+        out, p = [], 0
+        for off, n, T in segs:
+            out.append(ops.mask_head(emb[p:p + n], _group(feat, off, n, T), _group(out_mask, off, n, T), fill))
+            p += n
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *dsegs):
         emb, feat = (t.contiguous() for t in ctx.saved_tensors)
-        B, Q, Dp = emb.shape
-        T = feat.shape[1]
-        g = dseg.masked_fill(~ctx.out_mask[:, None, :].bool(), 0.0).contiguous()    # filled frames carry no gradient
         demb, dfeat = torch.empty_like(emb), torch.empty_like(feat)
-        # demb[b, q, :] = sum_t g[b,q,t] feat[b,t,:];  dfeat[b, t, :] = sum_q g[b,q,t] emb[b,q,:]
-        bmm(g, (Q * T, 0, T, 1), feat, (T * Dp, 0, Dp, 1), demb, (Q * Dp, 0, Dp, 1), B, 1, Q, Dp, T)
-        bmm(g, (Q * T, 0, 1, T), emb, (Q * Dp, 0, Dp, 1), dfeat, (T * Dp, 0, Dp, 1), B, 1, T, Dp, Q)
-        return demb, dfeat, None, None
+        if ctx.segs is None:
+            _mask_head_bwd(emb, feat, ctx.out_mask, dsegs[0], demb, dfeat)
+        else:
+            p = 0
+            for (off, n, T), dseg in zip(ctx.segs, dsegs):
+                if dseg is None:
+                    dseg = torch.zeros(n, emb.shape[1], T, device=emb.device)
+                _mask_head_bwd(emb[p:p + n], _group(feat, off, n, T), _group(ctx.out_mask, off, n, T), dseg,
+                               demb[p:p + n], _group(dfeat, off, n, T))
+                p += n
+        return demb, dfeat, None, None, None
 
 
 class ToChannelsLast(_Differentiable):
@@ -644,13 +744,13 @@ def layernorm(x, gamma, beta, *, relu=False, post_add=None):
     return LayerNormFn.apply(x, gamma, beta, relu, post_add)
 
 
-def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None):
+def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=None):
     if pre_ln is not None:
         x = LayerNormFn.apply(x, pre_ln[0], pre_ln[1], False, None)
     wb = []
     for s in sets:
         wb += [s["weight"], s.get("bias")]
-    outs = DepthwiseConv.apply(x, x_up, mask_out, stride, *wb)
+    outs = DepthwiseConv.apply(x, x_up, mask_out, stride, segs, *wb)
     res = []
     for s, d in zip(sets, outs):
         if s.get("gamma") is not None:

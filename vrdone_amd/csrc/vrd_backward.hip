@@ -19,6 +19,7 @@
 //  vrd_attn_bwd_probs  global attention: probabilities P and score gradients dS, row by row
 //  vrd_bmm             strided batched matmul (dq = dS K, dk = dS^T Q, dv = P^T dO; mask head)
 //  vrd_maxpool_bwd     MaxPool1d(3,2,1) * mask
+//  vrd_dwconv_bwd_segs / vrd_maxpool_bwd_segs   the two over a ragged row space (vrd_row_segs), one launch for all groups
 // (the banded attention's backward and its training forward with attn_drop: vrd_local_attn_bwd.hip)
 #include "vrd_grad_scratch.h"
 #include <cstdlib>
@@ -227,16 +228,17 @@ struct DwBwdArgs {
     float* dx_up;
     int64_t lddx_up;
 };
-__device__ __forceinline__ float dw_bwd_elem(const DwBwdArgs& p, int b, int ti, int cin) {
+// out0: the first output row of the element's sequence, Tin: its input frames
+__device__ __forceinline__ float dw_bwd_elem(const DwBwdArgs& p, int64_t out0, int Tin, int ti, int cin) {
     const int c = cin / p.gin, g = cin - c * p.gin;
-    const int Tout = p.Tin / p.stride;
+    const int Tout = Tin / p.stride;
     float s = 0.f;
     for (int k = 0; k < p.ksize; ++k) {
         const int tn = ti - k + p.ksize / 2;
         if (tn < 0 || tn % p.stride) continue;
         const int to = tn / p.stride;
         if (to >= Tout) continue;
-        const int64_t row = (int64_t)b * Tout + to;
+        const int64_t row = out0 + to;
         if (p.mask_out && !p.mask_out[row]) continue;
         for (int o = 0; o < p.n_out; ++o) s = fmaf(p.dD[o][row * p.lddd[o] + c], p.w[o][(c * p.gin + g) * p.ksize + k], s);
     }
@@ -246,14 +248,26 @@ __device__ __forceinline__ float dw_bwd_elem(const DwBwdArgs& p, int b, int ti, 
 // dx[b, ti, c] = sum_o sum_k m[b, ti + 1 - k] dD_o[b, ti + 1 - k, c] w_o[c, k]: three rows x n_out float4 of dD and 3 n_out float4
 // of weights (a channel's taps are contiguous: 12 floats for 4 channels) per 4 outputs.  The element-per-thread form below spends
 // ~100 instructions per element on index arithmetic and scalar loads and ran at 3.2 TB/s of its traffic.
-template <int NOUT>
-__global__ __launch_bounds__(256) void dwconv_bwd_vec_kernel(DwBwdArgs p) {
+// SEGS (vrd_dwconv_bwd_segs, both kernels): the threads count the input frames (with dx_up: the frame pairs) of the groups of `sg`
+// in order; a frame's rows are those of its group (input rows from row[g] on, output rows from row[g] / stride, x_up rows from
+// row[g] / 2), and nothing else is read or written.  B and Tin of `p` are unused.
+template <int NOUT, bool SEGS = false>
+__global__ __launch_bounds__(256) void dwconv_bwd_vec_kernel(DwBwdArgs p, const vrd::RowSegArg<SEGS> sg) {
     const int C4 = p.C / 4;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)p.B * p.Tin * C4) return;
-    const int64_t r = idx / C4;
+    int64_t r = idx / C4;
     const int c = (int)(idx - r * C4) * 4;
-    const int ti = (int)(r % p.Tin);
+    int ti;
+    if constexpr (SEGS) {
+        int g, b;
+        if (C4 % 64 == 0) r = vrd::wave_uniform(r);          // (a wave's 64 threads then lie in one row)
+        if (!vrd::seg_find(sg, r, g, b, ti)) return;
+        p.Tin = sg.T[g];
+        r = sg.row[g] + (int64_t)b * p.Tin + ti;
+    } else {
+        if (idx >= (int64_t)p.B * p.Tin * C4) return;
+        ti = (int)(r % p.Tin);
+    }
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 w[NOUT][3];
 #pragma unroll
@@ -279,27 +293,51 @@ __global__ __launch_bounds__(256) void dwconv_bwd_vec_kernel(DwBwdArgs p) {
     st4(p.dx + r * p.lddx + c, acc);
 }
 
-__global__ __launch_bounds__(256) void dwconv_bwd_kernel(DwBwdArgs p) {
+template <bool SEGS = false>
+__global__ __launch_bounds__(256) void dwconv_bwd_kernel(DwBwdArgs p, const vrd::RowSegArg<SEGS> sg) {
     const int Cin = p.C * p.gin;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int cin = (int)(idx % Cin);
     if (p.dx_up) {
-        const int64_t total = (int64_t)p.B * (p.Tin / 2) * Cin;
-        if (idx >= total) return;
-        const int cin = (int)(idx % Cin);
-        const int64_t ru = idx / Cin;
-        const int b = (int)(ru / (p.Tin / 2)), tu = (int)(ru - (int64_t)b * (p.Tin / 2));
-        const float g0 = dw_bwd_elem(p, b, 2 * tu, cin), g1 = dw_bwd_elem(p, b, 2 * tu + 1, cin);
-        p.dx[((int64_t)b * p.Tin + 2 * tu) * p.lddx + cin] = g0;
-        p.dx[((int64_t)b * p.Tin + 2 * tu + 1) * p.lddx + cin] = g1;
+        int64_t ru = idx / Cin;                   // the frame pair: its x_up row
+        int64_t in0, out0;                        // first input / output row of its sequence
+        int tu;
+        if constexpr (SEGS) {
+            int g, b;
+            if (Cin % 64 == 0) ru = vrd::wave_uniform(ru);
+            if (!vrd::seg_find(sg, ru, g, b, tu)) return;            // (the table counts T / 2 frame pairs per sequence)
+            p.Tin = sg.T[g];
+            in0 = sg.row[g] + (int64_t)b * p.Tin;
+            out0 = sg.row[g] / p.stride + (int64_t)b * (p.Tin / p.stride);
+            ru = sg.row[g] / 2 + (int64_t)b * (p.Tin / 2) + tu;
+        } else {
+            if (idx >= (int64_t)p.B * (p.Tin / 2) * Cin) return;
+            const int b = (int)(ru / (p.Tin / 2));
+            tu = (int)(ru - (int64_t)b * (p.Tin / 2));
+            in0 = (int64_t)b * p.Tin, out0 = (int64_t)b * (p.Tin / p.stride);
+        }
+        const float g0 = dw_bwd_elem(p, out0, p.Tin, 2 * tu, cin), g1 = dw_bwd_elem(p, out0, p.Tin, 2 * tu + 1, cin);
+        p.dx[(in0 + 2 * tu) * p.lddx + cin] = g0;
+        p.dx[(in0 + 2 * tu + 1) * p.lddx + cin] = g1;
         p.dx_up[ru * p.lddx_up + cin] = g0 + g1;
         return;
     }
-    const int64_t total = (int64_t)p.B * p.Tin * Cin;
-    if (idx >= total) return;
-    const int cin = (int)(idx % Cin);
-    const int64_t r = idx / Cin;
-    const int b = (int)(r / p.Tin), ti = (int)(r - (int64_t)b * p.Tin);
-    p.dx[r * p.lddx + cin] = dw_bwd_elem(p, b, ti, cin);
+    int64_t r = idx / Cin, out0;
+    int ti;
+    if constexpr (SEGS) {
+        int g, b;
+        if (Cin % 64 == 0) r = vrd::wave_uniform(r);
+        if (!vrd::seg_find(sg, r, g, b, ti)) return;
+        p.Tin = sg.T[g];
+        r = sg.row[g] + (int64_t)b * p.Tin + ti;
+        out0 = sg.row[g] / p.stride + (int64_t)b * (p.Tin / p.stride);
+    } else {
+        if (idx >= (int64_t)p.B * p.Tin * Cin) return;
+        const int b = (int)(r / p.Tin);
+        ti = (int)(r - (int64_t)b * p.Tin);
+        out0 = (int64_t)b * (p.Tin / p.stride);
+    }
+    p.dx[r * p.lddx + cin] = dw_bwd_elem(p, out0, p.Tin, ti, cin);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -569,28 +607,44 @@ __global__ __launch_bounds__(256) void attn_bwd_softmax_kernel(float* __restrict
 
 // MaxPool1d(3, 2, 1)(x) * mask[::2] backward: dx[b, ti, c] = sum over the (1 or 2) windows holding ti in which ti is the
 // FIRST maximum (ATen's tie rule) of mask[2 to] * dy[b, to, c]
+// SEGS (vrd_maxpool_bwd_segs): the threads count the input frames of the groups of `sg` in order; group g's x / mask / dx rows start
+// at row[g], its dy rows at row[g] / 2.  B and Tin are unused.
+template <bool SEGS = false>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ dy,
                                                           int64_t lddy, int B, int Tin, int C, const uint8_t* __restrict__ mask_in,
-                                                          float* __restrict__ dx, int64_t lddx) {
+                                                          float* __restrict__ dx, int64_t lddx, const vrd::RowSegArg<SEGS> sg) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)B * Tin * C) return;
     const int c = (int)(idx % C);
-    const int64_t r = idx / C;
-    const int b = (int)(r / Tin), ti = (int)(r - (int64_t)b * Tin);
+    int64_t r = idx / C, in0, out0;               // the frame's row; first input / output row of its sequence
+    int ti;
+    if constexpr (SEGS) {
+        int g, b;
+        if (C % 64 == 0) r = vrd::wave_uniform(r);
+        if (!vrd::seg_find(sg, r, g, b, ti)) return;
+        Tin = sg.T[g];
+        in0 = sg.row[g] + (int64_t)b * Tin;
+        out0 = sg.row[g] / 2 + (int64_t)b * (Tin / 2);
+        r = in0 + ti;
+    } else {
+        if (idx >= (int64_t)B * Tin * C) return;
+        const int b = (int)(r / Tin);
+        ti = (int)(r - (int64_t)b * Tin);
+        in0 = (int64_t)b * Tin, out0 = (int64_t)b * (Tin / 2);
+    }
     const int Tout = Tin / 2;
     const float xv = x[r * ldx + c];
     float g = 0.f;
     // windows: to with 2 to - 1 <= ti <= 2 to + 1
     for (int to = (ti + 1) / 2 - ((ti & 1) ? 1 : 0); to <= (ti + 1) / 2; ++to) {
         if (to < 0 || to >= Tout) continue;
-        if (!mask_in[(int64_t)b * Tin + 2 * to]) continue;
+        if (!mask_in[in0 + 2 * to]) continue;
         bool first_max = true;
         for (int tt = 2 * to - 1; tt <= 2 * to + 1; ++tt) {
             if (tt < 0 || tt >= Tin || tt == ti) continue;
-            const float o = x[((int64_t)b * Tin + tt) * ldx + c];
+            const float o = x[(in0 + tt) * ldx + c];
             if (o > xv || (o == xv && tt < ti)) first_max = false;
         }
-        if (first_max) g += dy[((int64_t)b * Tout + to) * lddy + c];
+        if (first_max) g += dy[(out0 + to) * lddy + c];
     }
     dx[r * lddx + c] = g;
 }
@@ -660,14 +714,26 @@ int vrd_layernorm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy
     return partials ? vrd::reduce_partial_rows(scratch, pr, dgamma, dbeta, C, det, s) : 0;
 }
 
-int vrd_dwconv_bwd(const vrd_dwconv_bwd_args* a, void* stream) {
+// segs: NULL, or the row groups of vrd_dwconv_bwd_segs (a->B and a->Tin are then unused)
+static int dwconv_bwd_launch(const vrd_dwconv_bwd_args* a, const vrd_row_segs* segs, void* stream) {
     VRD_CHECK_ARG(a && a->dx, "vrd_dwconv_bwd: null args");
-    VRD_CHECK_ARG(a->n_out >= 1 && a->n_out <= 3 && a->B > 0 && a->Tin > 0 && a->C > 0, "vrd_dwconv_bwd: bad sizes");
+    VRD_CHECK_ARG(a->n_out >= 1 && a->n_out <= 3 && a->C > 0 && (segs || (a->B > 0 && a->Tin > 0)), "vrd_dwconv_bwd: bad sizes");
     VRD_CHECK_ARG((a->ksize == 1 || a->ksize == 3) && (a->stride == 1 || a->stride == 2) && (a->group_in == 1 || a->group_in == 2) &&
-                      a->Tin % a->stride == 0,
+                      (segs || a->Tin % a->stride == 0),
                   "vrd_dwconv_bwd: ksize 1/3, stride 1/2, group_in 1/2, Tin %% stride == 0");
-    VRD_CHECK_ARG(!a->dx_up || (a->Tin % 2 == 0 && a->lddx_up >= (int64_t)a->C * a->group_in), "vrd_dwconv_bwd: bad dx_up");
+    VRD_CHECK_ARG(!a->dx_up || ((segs || a->Tin % 2 == 0) && a->lddx_up >= (int64_t)a->C * a->group_in), "vrd_dwconv_bwd: bad dx_up");
     VRD_CHECK_ARG(a->lddx >= (int64_t)a->C * a->group_in, "vrd_dwconv_bwd: lddx too small");
+    // the rules of vrd_dwconv_ln_args.segs: T[i] % stride == 0, row[i] even when x_up or stride 2 is used.  The table counts what a
+    // thread owns: input frames, or with dx_up pairs of them
+    vrd::SegTable sg;
+    int64_t units = 0;
+    if (segs) {
+        const int even = (a->dx_up || a->stride == 2) ? 2 : 1;
+        units = vrd::seg_table(sg, segs, a->dx_up ? 2 : 1, 1);
+        VRD_CHECK_ARG(units > 0, "vrd_dwconv_bwd_segs: bad row groups (1..%d groups, T %% %d == 0)", VRD_MAX_SEGS, even);
+        for (int g = 0; g < segs->count; ++g)
+            VRD_CHECK_ARG(segs->T[g] % even == 0 && segs->row[g] % even == 0, "vrd_dwconv_bwd_segs: group %d: T and row must be even", g);
+    }
     DwBwdArgs p{};
     for (int o = 0; o < a->n_out; ++o) {
         VRD_CHECK_ARG(a->dD[o] && a->w[o] && a->lddd[o] >= a->C, "vrd_dwconv_bwd: bad set %d", o);
@@ -676,20 +742,31 @@ int vrd_dwconv_bwd(const vrd_dwconv_bwd_args* a, void* stream) {
     p.n_out = a->n_out, p.B = a->B, p.Tin = a->Tin, p.C = a->C, p.ksize = a->ksize, p.stride = a->stride, p.gin = a->group_in;
     p.mask_out = a->mask_out, p.dx = a->dx, p.lddx = a->lddx, p.dx_up = a->dx_up, p.lddx_up = a->lddx_up;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t n = (int64_t)a->B * (a->dx_up ? a->Tin / 2 : a->Tin) * a->C * a->group_in;
-    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)a->B * a->Tin * a->C * (a->group_in + a->n_out));
+    const int64_t n = (segs ? units : (int64_t)a->B * (a->dx_up ? a->Tin / 2 : a->Tin)) * a->C * a->group_in;
+    const double in_rows = segs ? (double)units * (a->dx_up ? 2 : 1) : (double)a->B * a->Tin;
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * in_rows * a->C * (a->group_in + a->n_out));
     bool vec = a->ksize == 3 && a->stride == 1 && a->group_in == 1 && !a->dx_up && a->C % 4 == 0 && a->lddx % 4 == 0 && aligned16(a->dx);
     for (int o = 0; o < a->n_out; ++o) vec = vec && a->lddd[o] % 4 == 0 && aligned16(a->dD[o]) && aligned16(a->w[o]);
     if (vec) {
         const dim3 grid((unsigned)((n / 4 + 255) / 256));
-        if (a->n_out == 3) hipLaunchKernelGGL(dwconv_bwd_vec_kernel<3>, grid, dim3(256), 0, s, p);
-        else if (a->n_out == 2) hipLaunchKernelGGL(dwconv_bwd_vec_kernel<2>, grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(dwconv_bwd_vec_kernel<1>, grid, dim3(256), 0, s, p);
+        vrd::pick_of(vrd::IntList<1, 2, 3>{}, a->n_out, [&](auto NOUT) {
+            if (segs) hipLaunchKernelGGL((dwconv_bwd_vec_kernel<decltype(NOUT)::value, true>), grid, dim3(256), 0, s, p, sg);
+            else hipLaunchKernelGGL((dwconv_bwd_vec_kernel<decltype(NOUT)::value>), grid, dim3(256), 0, s, p, vrd::NoRowSegs{});
+        });
+    } else if (segs) {
+        hipLaunchKernelGGL(dwconv_bwd_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, sg);
     } else {
-        hipLaunchKernelGGL(dwconv_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(dwconv_bwd_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, vrd::NoRowSegs{});
     }
     VRD_LAUNCH_CHECK();
     return 0;
+}
+
+int vrd_dwconv_bwd(const vrd_dwconv_bwd_args* a, void* stream) { return dwconv_bwd_launch(a, nullptr, stream); }
+
+int vrd_dwconv_bwd_segs(const vrd_dwconv_bwd_args* a, const vrd_row_segs* segs, void* stream) {
+    VRD_CHECK_ARG(segs, "vrd_dwconv_bwd_segs: null row groups");
+    return dwconv_bwd_launch(a, segs, stream);
 }
 
 int vrd_attn_bwd_probs(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, const float* dO, int64_t lddo,
@@ -758,7 +835,26 @@ int vrd_maxpool_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n = (int64_t)B * Tin * C;
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)n * 2.5);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, B, Tin, C, mask_in, dx, lddx);
+    hipLaunchKernelGGL(maxpool_bwd_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, B, Tin, C, mask_in, dx,
+                       lddx, vrd::NoRowSegs{});
+    VRD_LAUNCH_CHECK();
+    return 0;
+}
+
+int vrd_maxpool_bwd_segs(const float* x, int64_t ldx, const float* dy, int64_t lddy, const vrd_row_segs* segs, int C, const uint8_t* mask_in,
+                         float* dx, int64_t lddx, void* stream) {
+    VRD_CHECK_ARG(x && dy && mask_in && dx && segs && C > 0, "vrd_maxpool_bwd_segs: bad arguments");
+    VRD_CHECK_ARG(ldx >= C && lddy >= C && lddx >= C, "vrd_maxpool_bwd_segs: leading dimension too small");
+    vrd::SegTable sg;
+    const int64_t rows = vrd::seg_table(sg, segs, 1, 1);
+    VRD_CHECK_ARG(rows > 0, "vrd_maxpool_bwd_segs: bad row groups (1..%d groups)", VRD_MAX_SEGS);
+    for (int g = 0; g < segs->count; ++g)
+        VRD_CHECK_ARG(segs->T[g] % 2 == 0 && segs->row[g] % 2 == 0, "vrd_maxpool_bwd_segs: group %d: T and row must be even", g);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t n = rows * C;
+    vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)n * 2.5);
+    hipLaunchKernelGGL(maxpool_bwd_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, 0, 0, C, mask_in, dx, lddx,
+                       sg);
     VRD_LAUNCH_CHECK();
     return 0;
 }

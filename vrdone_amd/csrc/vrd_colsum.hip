@@ -7,6 +7,7 @@
 //
 //  vrd_colsum            out[c] += sum_r a[r,c] * b[s*r+shift, c*bc+bo] * mask[r] * rscale[r]
 //  vrd_dwconv_wgrad      weight and bias gradient of a depthwise conv in one pass over dD
+//  vrd_dwconv_wgrad_segs the same with the rows as groups of sequences (vrd_row_segs): the sums run over all groups
 //  vrd_scratch_required  floats of scratch the last refused deterministic call of this thread asked for
 #include "vrd_grad_scratch.h"
 
@@ -112,11 +113,22 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
 // block = rpb rows x 64 columns, a quarter of the rows per wave (as vrd_colsum); one atomic per column, output and block.
 // DET: row blockIdx.x of `partial` (gridDim.x x (C * GIN * KS [+ C])) instead: dw's layout, then the bias.
 // ------------------------------------------------------------------------------------------------------------------
-template <int KS, int GIN, bool DET>
+// SEGS (vrd_dwconv_wgrad_segs, both kernels): `rows` counts the OUTPUT frames of the groups of `sg` in order (the table is built
+// over T[g] / bs frames per sequence); a frame's dD / mask row and its input rows are those of its group (output rows from
+// row[g] / bs on, input rows from row[g]), and the sequence ends that bound the taps are the group's.  T is unused.
+// seg_rows: the dD / mask row and the sequence's first input row and input frames at the cursor c.
+__device__ __forceinline__ void seg_rows(const vrd::SegTable& sg, const vrd::SegCursor& c, int bs, int64_t& out_row, int64_t& in0, int& Tin) {
+    const int g = c.g < sg.count ? c.g : sg.count - 1;        // (behind the last frame: a row nobody reads)
+    Tin = sg.T[g];
+    in0 = sg.row[g] + (int64_t)c.b * Tin;
+    out_row = sg.row[g] / bs + (int64_t)c.b * sg.sps[g] + c.t;
+}
+template <int KS, int GIN, bool DET, bool SEGS = false>
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x,
                                                            int64_t ldx, int bs, int T, const uint8_t* __restrict__ mask,
                                                            int64_t rows, int C, int rpb, float* __restrict__ dw,
-                                                           float* __restrict__ dbias, float* __restrict__ partial) {
+                                                           float* __restrict__ dbias, float* __restrict__ partial,
+                                                           const vrd::RowSegArg<SEGS> sg) {
     __shared__ float red[3][GIN * KS + 1][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
@@ -124,8 +136,15 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
     const int wrows = rpb / 4;
     const int64_t r0 = (int64_t)blockIdx.x * rpb + (int64_t)wave * wrows;
     const int64_t r1 = r0 + wrows < rows ? r0 + wrows : rows;
-    int64_t seq = r0 / T;
-    int tpos = (int)(r0 - seq * T);
+    int64_t seq = 0;
+    int tpos = 0;
+    vrd::SegCursor cur{0, 0, 0};
+    if constexpr (SEGS) {
+        if (r0 < r1) vrd::seg_find(sg, vrd::wave_uniform(r0), cur.g, cur.b, cur.t);          // (r0 is the wave's)
+    } else {
+        seq = r0 / T;
+        tpos = (int)(r0 - seq * T);
+    }
     float sw[GIN][KS], sb = 0.f;
 #pragma unroll
     for (int g = 0; g < GIN; ++g)
@@ -135,18 +154,30 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
         float av[4], xv[4][GIN][KS];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int64_t r = rb + u;
-            const bool live = col_ok && r < r1 && (!mask || mask[r]);
-            int tq = tpos + u;
-            int64_t sq = seq;
-            while (tq >= T) tq -= T, ++sq;
+            int64_t r = rb + u, in0;
+            int tq, Tin;
+            if constexpr (SEGS) {
+                vrd::SegCursor cu = cur;
+                vrd::seg_step(sg, cu, u);
+                const bool in_range = r < r1;
+                seg_rows(sg, cu, bs, r, in0, Tin);
+                tq = cu.t;
+                if (!in_range) r = -1;
+            } else {
+                tq = tpos + u;
+                int64_t sq = seq;
+                while (tq >= T) tq -= T, ++sq;
+                in0 = sq * (int64_t)bs * T, Tin = bs * T;
+                if (r >= r1) r = -1;
+            }
+            const bool live = col_ok && r >= 0 && (!mask || mask[r]);
             av[u] = live ? a[r * lda + c] : 0.f;
 #pragma unroll
             for (int kk = 0; kk < KS; ++kk) {
                 const int tb = bs * tq + kk - KS / 2;
-                const bool ok = live && tb >= 0 && tb < bs * T;
+                const bool ok = live && tb >= 0 && tb < Tin;
 #pragma unroll
-                for (int g = 0; g < GIN; ++g) xv[u][g][kk] = ok ? x[(sq * (int64_t)bs * T + tb) * ldx + (int64_t)c * GIN + g] : 0.f;
+                for (int g = 0; g < GIN; ++g) xv[u][g][kk] = ok ? x[(in0 + tb) * ldx + (int64_t)c * GIN + g] : 0.f;
             }
         }
 #pragma unroll
@@ -157,8 +188,12 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
 #pragma unroll
                 for (int kk = 0; kk < KS; ++kk) sw[g][kk] = fmaf(av[u], xv[u][g][kk], sw[g][kk]);
         }
-        tpos += 4;
-        while (tpos >= T) tpos -= T, ++seq;
+        if constexpr (SEGS) {
+            vrd::seg_step(sg, cur, 4);
+        } else {
+            tpos += 4;
+            while (tpos >= T) tpos -= T, ++seq;
+        }
     }
     if (wave > 0) {
 #pragma unroll
@@ -246,11 +281,12 @@ __global__ __launch_bounds__(256) void colsum_vec_kernel(const float* __restrict
     }
 }
 
-template <bool A16>
+template <bool A16, bool SEGS = false>
 __global__ __launch_bounds__(256) void dwconv_wgrad_vec_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ x,
                                                                int64_t ldx, int bs, int T, const uint8_t* __restrict__ mask,
                                                                int64_t rows, int C, int rpb, float* __restrict__ dw,
-                                                               float* __restrict__ dbias, float* __restrict__ partial) {
+                                                               float* __restrict__ dbias, float* __restrict__ partial,
+                                                               const vrd::RowSegArg<SEGS> sg) {
     __shared__ float4 red[3][4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.y * 256 + lane * 4;
@@ -258,25 +294,44 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_vec_kernel(const float* __re
     const int wrows = rpb / 4;
     const int64_t r0 = (int64_t)blockIdx.x * rpb + (int64_t)wave * wrows;
     const int64_t r1 = r0 + wrows < rows ? r0 + wrows : rows;
-    int64_t seq = r0 / T;
-    int tpos = (int)(r0 - seq * T);
+    int64_t seq = 0;
+    int tpos = 0;
+    vrd::SegCursor cur{0, 0, 0};
+    if constexpr (SEGS) {
+        if (r0 < r1) vrd::seg_find(sg, vrd::wave_uniform(r0), cur.g, cur.b, cur.t);          // (r0 is the wave's)
+    } else {
+        seq = r0 / T;
+        tpos = (int)(r0 - seq * T);
+    }
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 sw[3] = {zero, zero, zero}, sb = zero;         // sw[kk] = the four channels' sums of tap kk
     for (int64_t rb = r0; rb < r1; rb += 4) {
         float4 av[4], xv[4][3];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int64_t r = rb + u;
-            const bool live = col_ok && r < r1 && (!mask || mask[r]);
-            int tq = tpos + u;
-            int64_t sq = seq;
-            while (tq >= T) tq -= T, ++sq;
+            int64_t r = rb + u, in0;
+            int tq, Tin;
+            if constexpr (SEGS) {
+                vrd::SegCursor cu = cur;
+                vrd::seg_step(sg, cu, u);
+                const bool in_range = r < r1;
+                seg_rows(sg, cu, bs, r, in0, Tin);
+                tq = cu.t;
+                if (!in_range) r = -1;
+            } else {
+                tq = tpos + u;
+                int64_t sq = seq;
+                while (tq >= T) tq -= T, ++sq;
+                in0 = sq * (int64_t)bs * T, Tin = bs * T;
+                if (r >= r1) r = -1;
+            }
+            const bool live = col_ok && r >= 0 && (!mask || mask[r]);
             av[u] = live ? ldv4<A16>(a + r * lda + c) : zero;
 #pragma unroll
             for (int kk = 0; kk < 3; ++kk) {
                 const int tb = bs * tq + kk - 1;
-                const bool ok = live && tb >= 0 && tb < bs * T;
-                xv[u][kk] = ok ? ldv4<A16>(x + (sq * (int64_t)bs * T + tb) * ldx + c) : zero;
+                const bool ok = live && tb >= 0 && tb < Tin;
+                xv[u][kk] = ok ? ldv4<A16>(x + (in0 + tb) * ldx + c) : zero;
             }
         }
 #pragma unroll
@@ -285,8 +340,12 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_vec_kernel(const float* __re
 #pragma unroll
             for (int kk = 0; kk < 3; ++kk) fma4(sw[kk], av[u], xv[u][kk]);
         }
-        tpos += 4;
-        while (tpos >= T) tpos -= T, ++seq;
+        if constexpr (SEGS) {
+            vrd::seg_step(sg, cur, 4);
+        } else {
+            tpos += 4;
+            while (tpos >= T) tpos -= T, ++seq;
+        }
     }
     if (wave > 0) {
 #pragma unroll
@@ -370,10 +429,10 @@ static int launch_colsum(const vrd::ColsumPlan& p, const float* a, int64_t lda, 
     return p.partials ? vrd::reduce_partial_rows(scratch, p.pr, out, nullptr, C, det, s) : 0;
 }
 
-template <bool DET>
-static auto dwconv_wgrad_for(int ksize, int group_in) -> decltype(&dwconv_wgrad_kernel<3, 1, DET>) {
-    if (ksize == 3) return group_in == 1 ? dwconv_wgrad_kernel<3, 1, DET> : dwconv_wgrad_kernel<3, 2, DET>;
-    return group_in == 1 ? dwconv_wgrad_kernel<1, 1, DET> : dwconv_wgrad_kernel<1, 2, DET>;
+template <bool DET, bool SEGS = false>
+static auto dwconv_wgrad_for(int ksize, int group_in) -> decltype(&dwconv_wgrad_kernel<3, 1, DET, SEGS>) {
+    if (ksize == 3) return group_in == 1 ? dwconv_wgrad_kernel<3, 1, DET, SEGS> : dwconv_wgrad_kernel<3, 2, DET, SEGS>;
+    return group_in == 1 ? dwconv_wgrad_kernel<1, 1, DET, SEGS> : dwconv_wgrad_kernel<1, 2, DET, SEGS>;
 }
 
 static thread_local int64_t g_scratch_need = 0;
@@ -421,9 +480,19 @@ int vrd_scratch_required(int64_t* floats) {
     return 0;
 }
 
-int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
-                     const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch, int64_t scratch_floats,
-                     void* stream, int flags) {
+// segs: NULL, or the INPUT rows' groups of vrd_dwconv_wgrad_segs (T and rows are then taken from the table)
+static int dwconv_wgrad_launch(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
+                               const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch,
+                               int64_t scratch_floats, void* stream, int flags, const vrd_row_segs* segs) {
+    vrd::SegTable sg;
+    if (segs) {
+        VRD_CHECK_ARG(stride >= 1, "vrd_dwconv_wgrad_segs: bad stride %d", stride);
+        rows = vrd::seg_table(sg, segs, stride, 1);          // (output frames: T[g] / stride per sequence)
+        VRD_CHECK_ARG(rows > 0, "vrd_dwconv_wgrad_segs: bad row groups (1..%d groups, T %% %d == 0)", VRD_MAX_SEGS, stride);
+        for (int g = 0; g < segs->count; ++g)
+            VRD_CHECK_ARG(segs->row[g] % stride == 0, "vrd_dwconv_wgrad_segs: group %d: row %% stride != 0", g);
+        T = 1;
+    }
     VRD_CHECK_ARG(dD && x && dw && rows > 0 && C > 0 && lddd >= C, "vrd_dwconv_wgrad: bad arguments");
     VRD_CHECK_ARG((ksize == 1 || ksize == 3) && (group_in == 1 || group_in == 2) && stride >= 1 && T > 0 && rows % T == 0,
                   "vrd_dwconv_wgrad: unsupported k=%d group_in=%d stride=%d T=%d rows=%lld", ksize, group_in, stride, T, (long long)rows);
@@ -440,11 +509,33 @@ int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx,
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * (1 + group_in * stride));
     const dim3 grid(plan.row_blocks, plan.col_blocks);
     float* partial = plan.partials ? scratch + plan.pr.rows_off : nullptr;
-    auto kern = plan.vec ? (a16 ? dwconv_wgrad_vec_kernel<true> : dwconv_wgrad_vec_kernel<false>)
-                         : (det ? dwconv_wgrad_for<true>(ksize, group_in) : dwconv_wgrad_for<false>(ksize, group_in));
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, plan.rpb, dw, dbias, partial);
+    if (segs) {
+        auto kern = plan.vec ? (a16 ? dwconv_wgrad_vec_kernel<true, true> : dwconv_wgrad_vec_kernel<false, true>)
+                             : (det ? dwconv_wgrad_for<true, true>(ksize, group_in) : dwconv_wgrad_for<false, true>(ksize, group_in));
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, plan.rpb, dw, dbias, partial, sg);
+    } else {
+        auto kern = plan.vec ? (a16 ? dwconv_wgrad_vec_kernel<true> : dwconv_wgrad_vec_kernel<false>)
+                             : (det ? dwconv_wgrad_for<true>(ksize, group_in) : dwconv_wgrad_for<false>(ksize, group_in));
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, dD, lddd, x, ldx, stride, T, row_mask, rows, C, plan.rpb, dw, dbias, partial,
+                           vrd::NoRowSegs{});
+    }
     VRD_LAUNCH_CHECK();
     return plan.partials ? vrd::reduce_partial_rows(scratch, plan.pr, dw, dbias, (int)wcols, det, s) : 0;
+}
+
+int vrd_dwconv_wgrad(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in, int T,
+                     const uint8_t* row_mask, int64_t rows, int C, float* dw, float* dbias, float* scratch, int64_t scratch_floats,
+                     void* stream, int flags) {
+    return dwconv_wgrad_launch(dD, lddd, x, ldx, ksize, stride, group_in, T, row_mask, rows, C, dw, dbias, scratch, scratch_floats, stream,
+                               flags, nullptr);
+}
+
+int vrd_dwconv_wgrad_segs(const float* dD, int64_t lddd, const float* x, int64_t ldx, int ksize, int stride, int group_in,
+                          const vrd_row_segs* segs, const uint8_t* row_mask, int C, float* dw, float* dbias, float* scratch,
+                          int64_t scratch_floats, void* stream, int flags) {
+    VRD_CHECK_ARG(segs, "vrd_dwconv_wgrad_segs: null row groups");
+    return dwconv_wgrad_launch(dD, lddd, x, ldx, ksize, stride, group_in, 0, row_mask, 0, C, dw, dbias, scratch, scratch_floats, stream, flags,
+                               segs);
 }
 
 int vrd_colsum(const float* a, int64_t lda, const float* b, int64_t ldb, int b_cstride, int b_coffset, int b_rstride, int shift,

@@ -54,6 +54,31 @@ __device__ __forceinline__ bool seg_find(const SegTable& t, int64_t ws, int& g, 
     return true;
 }
 
+// The row-group argument of a kernel that exists in both forms: the table (SEGS) or nothing (the uniform (B, T) form, whose
+// arguments and code stay what they were).  seg_rows: the table for a kernel that resolves single frames (strips of one row).
+struct NoRowSegs {};
+template <bool SEGS>
+using RowSegArg = std::conditional_t<SEGS, SegTable, NoRowSegs>;
+// A walk over consecutive frames of a table with strips of one row: group g, sequence b of the group, frame t (in units of
+// T[g] / t_div, the table's sps[g]).  seg_step moves it on by `by` frames, through sequence and group ends.
+// v, which the caller knows to be the same in every lane of the wave, as a value the compiler knows that of: what is computed from
+// it (seg_find's walk over the table in the kernel arguments, its divisions) then runs on the scalar unit, once per wave
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff));
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return ((int64_t)hi << 32) | lo;
+}
+struct SegCursor {
+    int g, b, t;
+};
+__device__ __forceinline__ void seg_step(const SegTable& sg, SegCursor& c, int by) {
+    c.t += by;
+    while (c.g < sg.count && c.t >= sg.sps[c.g]) {
+        c.t -= sg.sps[c.g];
+        if (++c.b >= sg.n[c.g]) c.b = 0, ++c.g;
+    }
+}
+
 // A wave-uniform read of kernel INPUT data (written before the launch, never by it) through the scalar cache: s_load instead
 // of a flat_load, which hipcc would follow with `s_waitcnt vmcnt(0)` -- a wait for every vector memory operation the wave has
 // in flight (its LDS-DMA requests, its stores), not just for this value.

@@ -2,6 +2,7 @@
 // also the training forward at p = 0: vrd_local_attn.hip; the envelope of shapes and the dispatch helpers: vrd_local_attn.h.)
 //
 //  vrd_local_attn_bwd                banded attention: dq, dk, dv
+//  vrd_local_attn_bwd_segs           the same over a ragged row space (vrd_row_segs), one launch per pass
 //  vrd_local_attn_drop / _drop_bwd   the same with attn_drop on the window probabilities (training forward and backward)
 #include "vrd_local_attn.h"
 #include "vrd_philox.h"
@@ -50,24 +51,37 @@ __device__ __forceinline__ float la_dot(const LaRow& x, const LaRow& y) {
 // WT: the window as a compile-time constant (11 .. 19: the loops unroll and s[] / dp[] stay in registers), or 0 for the
 // run-time windows up to LA_WRT, whose nine-entry arrays the compiler already keeps in registers
 using vrd::LA_WRT;
-template <int GROUP, int WT, int CPL = 8, bool DROP = false>
+// SEGS (vrd_local_attn_bwd_segs): wave w works on frame w of the groups' frames counted through `sg` in order; its q / k / v / dO /
+// mask / dq row is the frame's row in the row space, its scratch row is w -- the scratch has no gaps, so that the sum of dS over
+// all its rows (d rel_pe) stays one reduction.  B is unused, T is the group's.
+template <int GROUP, int WT, int CPL = 8, bool DROP = false, bool SEGS = false>
 __global__ __launch_bounds__(256) void local_attn_bwd_q_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                const float* __restrict__ v, int64_t ld,
                                                                const float* __restrict__ dO, int64_t lddo,
                                                                const uint8_t* __restrict__ mask, const float* __restrict__ rel,
                                                                int B, int T, int W_rt, float scale,
                                                                float* __restrict__ dq, int64_t lddq, float* __restrict__ P,
-                                                               float* __restrict__ dS, vrd::DropSite drop, uint64_t row0) {
+                                                               float* __restrict__ dS, vrd::DropSite drop, uint64_t row0,
+                                                               const vrd::RowSegArg<SEGS> sg) {
     const int W = WT ? WT : W_rt;
     const int HW = W / 2;
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (int64_t)B * T) return;
-    const int t = (int)(row % T);
+    const int64_t srow = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // the wave's scratch row
+    int64_t row = srow;
+    int t;
+    if constexpr (SEGS) {
+        int g, b;
+        if (!vrd::seg_find(sg, vrd::wave_uniform(srow), g, b, t)) return;
+        T = sg.T[g];
+        row = sg.row[g] + (int64_t)b * T + t;
+    } else {
+        if (row >= (int64_t)B * T) return;
+        t = (int)(row % T);
+    }
     constexpr int H = 64 / GROUP;
     const int head = lane / GROUP;
-    float* const Pr = P + (row * H + head) * W;
-    float* const dSr = dS + (row * H + head) * W;
+    float* const Pr = P + (srow * H + head) * W;
+    float* const dSr = dS + (srow * H + head) * W;
     float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
     if (!mask[row]) {
         if (lane % GROUP == 0)
@@ -169,25 +183,35 @@ __global__ __launch_bounds__(256) void local_attn_drop_fwd_kernel(const float* _
     st4(out + row * ldo + lane * CPL, a0);
     if (CPL == 8) st4(out + row * ldo + lane * CPL + 4, a1);
 }
-template <int GROUP, int CPL = 8>
+template <int GROUP, int CPL = 8, bool SEGS = false>
 __global__ __launch_bounds__(256) void local_attn_bwd_kv_kernel(const float* __restrict__ q, int64_t ld,
                                                                 const float* __restrict__ dO, int64_t lddo, int B, int T, int W,
                                                                 float scale, const float* __restrict__ P,
                                                                 const float* __restrict__ dS, float* __restrict__ dk,
-                                                                float* __restrict__ dv, int64_t lddkv) {
+                                                                float* __restrict__ dv, int64_t lddkv,
+                                                                const vrd::RowSegArg<SEGS> sg) {
     const int HW = W / 2;
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // key row j
-    if (row >= (int64_t)B * T) return;
-    const int tj = (int)(row % T);
+    const int64_t srow = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // key row j in the scratch's count (SEGS: see pass 1)
+    int64_t row = srow;                                                      // ... and in the operands
+    int tj;
+    if constexpr (SEGS) {
+        int g, b;
+        if (!vrd::seg_find(sg, vrd::wave_uniform(srow), g, b, tj)) return;
+        T = sg.T[g];
+        row = sg.row[g] + (int64_t)b * T + tj;
+    } else {
+        if (row >= (int64_t)B * T) return;
+        tj = (int)(row % T);
+    }
     constexpr int H = 64 / GROUP;
     const int head = lane / GROUP;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, c0 = a0, c1 = a0;
     for (int i = 0; i < W; ++i) {           // query t = tj + HW - i sees key tj at window position i
         const int t = tj + HW - i;
         if (t < 0 || t >= T) continue;
-        const int64_t qr = row + HW - i;
-        const float p = P[(qr * H + head) * W + i], ds = dS[(qr * H + head) * W + i] * scale;
+        const int64_t qr = row + HW - i, sr = srow + HW - i;       // (a sequence's rows are consecutive in both counts)
+        const float p = P[(sr * H + head) * W + i], ds = dS[(sr * H + head) * W + i] * scale;
         const float4 q0 = ld4(q + qr * ld + lane * CPL), o0 = ld4(dO + qr * lddo + lane * CPL);
         a0.x = fmaf(ds, q0.x, a0.x); a0.y = fmaf(ds, q0.y, a0.y); a0.z = fmaf(ds, q0.z, a0.z); a0.w = fmaf(ds, q0.w, a0.w);
         c0.x = fmaf(p, o0.x, c0.x); c0.y = fmaf(p, o0.y, c0.y); c0.z = fmaf(p, o0.z, c0.z); c0.w = fmaf(p, o0.w, c0.w);
@@ -204,21 +228,52 @@ __global__ __launch_bounds__(256) void local_attn_bwd_kv_kernel(const float* __r
 }
 
 // drop: NULL (vrd_local_attn_bwd, and vrd_local_attn_drop_bwd at p = 0: the same kernels, the same bits), or the attn_drop site
+// segs: NULL, or the row groups of vrd_local_attn_bwd_segs (B, T unused; no drop)
 int local_attn_bwd_launch(const float* q, const float* k, const float* v, int64_t ld, const float* dO, int64_t lddo,
                           const uint8_t* mask, const float* rel_pe, int B, int T, int C, int n_head, int half_win,
                           const vrd::DropSite* drop, int64_t row0, float* dq, float* dk, float* dv, int64_t ldd, float* scratch,
-                          void* stream) {
+                          void* stream, const vrd_row_segs* segs = nullptr) {
     VRD_CHECK_ARG(q && k && v && dO && mask && dq && dk && dv && scratch, "vrd_local_attn_bwd: null pointer");
     vrd::LaShape sh;
-    if (int rc = vrd::la_shape("vrd_local_attn_bwd", C, n_head, half_win, &sh)) return rc;
+    if (int rc = vrd::la_shape(segs ? "vrd_local_attn_bwd_segs" : "vrd_local_attn_bwd", C, n_head, half_win, &sh)) return rc;
     VRD_CHECK_ARG(ld >= C && lddo >= C && ldd >= C, "vrd_local_attn_bwd: leading dimension too small");
     VRD_CHECK_ARG(ld % 4 == 0 && lddo % 4 == 0 && ldd % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(dO) &&
                       aligned16(dq) && aligned16(dk) && aligned16(dv),
                   "vrd_local_attn_bwd: rows must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)B * T;
     const int W = sh.W;
     const float scale = 1.0f / sqrtf((float)sh.hd);
+    if (segs) {
+        // the frames of all groups, counted through the groups: the scratch rows.  P lies at the scratch's start, dS behind the
+        // P rows of a scratch sized for every row the groups span (the caller sizes it without walking the table)
+        vrd::SegTable sg;
+        const int64_t rows = vrd::seg_table(sg, segs, 1, 1);
+        VRD_CHECK_ARG(rows > 0 && !drop, "vrd_local_attn_bwd_segs: bad row groups (1..%d groups)", VRD_MAX_SEGS);
+        int64_t lo = segs->row[0], hi = 0;
+        for (int g = 0; g < segs->count; ++g) {
+            const int64_t end = segs->row[g] + (int64_t)segs->n[g] * segs->T[g];
+            lo = segs->row[g] < lo ? segs->row[g] : lo;
+            hi = end > hi ? end : hi;
+        }
+        float* P = scratch;
+        float* dS = scratch + (hi - lo) * n_head * W;
+        vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * 8);
+        const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+        const vrd::DropSite site{nullptr, 0u, 0u, 1.0f};
+        vrd::pick_of(vrd::LaWinsTrain{}, W <= LA_WRT ? 0 : W, [&](auto WT) {
+            vrd::la_pick_lanes(sh, [&](auto G, auto CPL) {
+                hipLaunchKernelGGL((local_attn_bwd_q_kernel<decltype(G)::value, decltype(WT)::value, decltype(CPL)::value, false, true>), grid, block,
+                                   0, s, q, k, v, ld, dO, lddo, mask, rel_pe, 0, 0, W, scale, dq, ldd, P, dS, site, (uint64_t)0, sg);
+            });
+        });
+        vrd::la_pick_lanes(sh, [&](auto G, auto CPL) {
+            hipLaunchKernelGGL((local_attn_bwd_kv_kernel<decltype(G)::value, decltype(CPL)::value, true>), grid, block, 0, s, q, ld, dO, lddo, 0, 0,
+                               W, scale, P, dS, dk, dv, ldd, sg);
+        });
+        VRD_LAUNCH_CHECK();
+        return 0;
+    }
+    const int64_t rows = (int64_t)B * T;
     float* P = scratch;
     float* dS = scratch + rows * n_head * W;
     vrd::ProfScope prof(VRD_K_BACKWARD, s, 0.0, 4.0 * (double)rows * C * 8);
@@ -228,13 +283,14 @@ int local_attn_bwd_launch(const float* q, const float* k, const float* v, int64_
         vrd::la_pick_lanes(sh, [&](auto G, auto CPL) {
             vrd::pick_bool(drop != nullptr, [&](auto DROP) {
                 hipLaunchKernelGGL((local_attn_bwd_q_kernel<decltype(G)::value, decltype(WT)::value, decltype(CPL)::value, decltype(DROP)::value>),
-                                   grid, block, 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, scale, dq, ldd, P, dS, site, (uint64_t)row0);
+                                   grid, block, 0, s, q, k, v, ld, dO, lddo, mask, rel_pe, B, T, W, scale, dq, ldd, P, dS, site, (uint64_t)row0,
+                                   vrd::NoRowSegs{});
             });
         });
     });
     vrd::la_pick_lanes(sh, [&](auto G, auto CPL) {
         hipLaunchKernelGGL((local_attn_bwd_kv_kernel<decltype(G)::value, decltype(CPL)::value>), grid, block, 0, s, q, ld, dO, lddo, B, T, W,
-                           scale, P, dS, dk, dv, ldd);
+                           scale, P, dS, dk, dv, ldd, vrd::NoRowSegs{});
     });
     VRD_LAUNCH_CHECK();
     return 0;
@@ -248,6 +304,13 @@ int vrd_local_attn_bwd(const float* q, const float* k, const float* v, int64_t l
                        const uint8_t* mask, const float* rel_pe, int B, int T, int C, int n_head, int half_win,
                        float* dq, float* dk, float* dv, int64_t ldd, float* scratch, void* stream) {
     return local_attn_bwd_launch(q, k, v, ld, dO, lddo, mask, rel_pe, B, T, C, n_head, half_win, nullptr, 0, dq, dk, dv, ldd, scratch, stream);
+}
+
+int vrd_local_attn_bwd_segs(const float* q, const float* k, const float* v, int64_t ld, const float* dO, int64_t lddo,
+                            const uint8_t* mask, const float* rel_pe, const vrd_row_segs* segs, int C, int n_head, int half_win,
+                            float* dq, float* dk, float* dv, int64_t ldd, float* scratch, void* stream) {
+    VRD_CHECK_ARG(segs, "vrd_local_attn_bwd_segs: null row groups");
+    return local_attn_bwd_launch(q, k, v, ld, dO, lddo, mask, rel_pe, 0, 0, C, n_head, half_win, nullptr, 0, dq, dk, dv, ldd, scratch, stream, segs);
 }
 
 int vrd_local_attn_drop_bwd(const float* q, const float* k, const float* v, int64_t ld, const float* dO, int64_t lddo,

@@ -177,18 +177,26 @@ class AffineDropPath(nn.Module):
         self.drop_prob = drop_prob
         self.keep = None            # tests may pin the per-sample keep decisions: a 0/1 vector (>= B entries) used instead of sampling
 
-    def row_factors(self, n_samples, rows_per_sample, device):
+    def row_factors(self, n_samples, rows_per_sample, device, lay=None):
         """Stochastic depth per sample (reference drop_path, blocks.py:1107-1120): factor_b = floor(keep_prob + U[0,1))
         / keep_prob, one per sample, expanded to one per row of the (n_samples * rows_per_sample, C) branch; None when
-        nothing is dropped (eval, drop_prob 0, or autograd not recording)."""
+        nothing is dropped (eval, drop_prob 0, or autograd not recording).
+        lay: the layout of the branch's rows when that is a row space (models/ragged.py).  The factors are still drawn, or read
+        from `keep`, one per sample in BATCH order; the layout knows the batch position of every row's sequence
+        (Layout.sample_rows), so sample i gets the factor the batch form gives it, over its own frame count."""
         if not self.training or self.drop_prob == 0.0 or not torch.is_grad_enabled():
             return None
         keep_prob = 1.0 - self.drop_prob
+        rows = None
+        if lay is not None and lay.axis == 1:
+            n_samples, rows = lay.sample_rows(device)
         if self.keep is not None:
             assert self.keep.numel() >= n_samples
             factors = self.keep[:n_samples].to(device=device, dtype=torch.float32) / keep_prob
         else:
             factors = _factor_pool.take(n_samples, keep_prob, torch.device(device))
+        if rows is not None:
+            return factors[rows]
         return factors[:, None].expand(n_samples, rows_per_sample).contiguous().view(-1)
 
     def forward(self, x):
@@ -520,9 +528,9 @@ class TransformerBlock(nn.Module, _StepDropout):
         return dp.scale if isinstance(dp, AffineDropPath) else None
 
     @staticmethod
-    def _drop(dp, mask):
-        """Per-row stochastic-depth factors of a branch whose rows follow `mask` (B, T'), or None."""
-        return dp.row_factors(mask.shape[0], mask.shape[1], mask.device) if isinstance(dp, AffineDropPath) else None
+    def _drop(dp, mask, lay=None):
+        """Per-row stochastic-depth factors of a branch whose rows follow `mask` (B, T') in the layout `lay`, or None."""
+        return dp.row_factors(mask.shape[0], mask.shape[1], mask.device, lay) if isinstance(dp, AffineDropPath) else None
 
     def cl(self, x, mask, out=None, lay=None):
         """lay: the layout of x's rows (default: the batch form); the result's is lay.strided(self.attn.n_kv_stride)"""
@@ -533,8 +541,9 @@ class TransformerBlock(nn.Module, _StepDropout):
         else:
             skip, m_out = x, mask
         # ln1 is applied to the rows inside the depthwise-conv kernel (its only consumer)
+        lay_out = lay.strided(self.attn.n_kv_stride)
         y, _ = self.attn.cl(x, mask, m_out, pre_ln=(self.ln1.weight, self.ln1.bias), lay=lay,
-                            scale=self._scale(self.drop_path_attn), row_scale=self._drop(self.drop_path_attn, m_out),
+                            scale=self._scale(self.drop_path_attn), row_scale=self._drop(self.drop_path_attn, m_out, lay_out),
                             res=skip, res_masked=True)
         h = self.ln2.cl(y, pair=ops.pair_mode())
         drops = self._drops(m_out.shape[0], m_out.shape[1], m_out.device)
@@ -542,7 +551,7 @@ class TransformerBlock(nn.Module, _StepDropout):
         kw1 = {"drop": drops["mlp.4"]} if drops else {}
         h = ops.conv_gemm(h, self.mlp[0].weight, self.mlp[0].bias, act=ops.ACT_GELU, out_pair=ops.pair_mode(), skip_rows=m_out, **kw0)
         y = ops.conv_gemm(h, self.mlp[3].weight, self.mlp[3].bias, row_mask=m_out, scale=self._scale(self.drop_path_mlp),
-                          row_scale=self._drop(self.drop_path_mlp, m_out), res=y, out=out, **kw1)
+                          row_scale=self._drop(self.drop_path_mlp, m_out, lay_out), res=y, out=out, **kw1)
         return y, m_out
 
     def forward(self, x, mask, pos_embd=None):

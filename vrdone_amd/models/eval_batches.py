@@ -333,6 +333,29 @@ def scatter_heads(dst, idx64, t2, logits, masks):
     dst["pred_masks"][idx64, :, :t2] = masks
 
 
+class _ScatterHeads(torch.autograd.Function):
+    """One layer's heads of all buckets of a row space -> the batch-shaped (pred_logits (B, Q, K+1), pred_masks (B, Q, T) with the
+    predictor's fill on padded frames): what scatter_heads writes bucket by bucket, as one differentiable step of a training pass.
+    Backward gathers: a bucket's rows of the two gradients, its own frames of the masks'."""
+
+    @staticmethod
+    def forward(ctx, T, idx64, frames, logits, *segs):
+        B, (Q, K1) = logits.shape[0], logits.shape[1:]
+        out = new_outputs(B, T, Q, K1, 0, logits.device)
+        p = 0
+        for i64, t2, seg in zip(idx64, frames, segs):
+            scatter_heads(out, i64, t2, logits[p:p + i64.numel()], seg)
+            p += i64.numel()
+        assert p == B
+        ctx.idx64, ctx.frames = idx64, frames
+        return out["pred_logits"], out["pred_masks"]
+
+    @staticmethod
+    def backward(ctx, d_logits, d_masks):
+        every = torch.cat(ctx.idx64) if len(ctx.idx64) > 1 else ctx.idx64[0]
+        return (None, None, None, d_logits[every], *(d_masks[i64, :, :t2] for i64, t2 in zip(ctx.idx64, ctx.frames)))
+
+
 # ---- drivers ----------------------------------------------------------------------------------------------------------------
 def unpack_rows(bb, x, index, lay):
     """backbones.py _unpack for the buckets of `lay`, bucket i the pairs index[i] (int32, device) of the caller's batch
@@ -363,11 +386,16 @@ def backbone_rows(bb, x, index, lay, mask):
     return bb.pair_stage(so, so_box, mask, lay)
 
 
-def mask_vrd_rows(model, x, masks2d, buckets, with_aux, t_ref=None):
+def mask_vrd_rows(model, x, masks2d, buckets, with_aux, t_ref=None, order=None):
     """MaskVRD._mask_vrd for `buckets` (sel: pair indices into the batch x (B, C_in, T)), each launch wave of at most ~pair_chunk
     pairs in one row space -> the batch-shaped output dict, at the batch's own padded length.
-    t_ref: the reference's padded length of the pairs (default: the batch's T)."""
+    t_ref: the reference's padded length of the pairs (default: the batch's T).
+    order: a training step (autograd recording; MaskVRD._train_rows_step) -- the buckets' pair indices on the host, bucket by
+    bucket: all B pairs in one wave without filler buckets, the layout knows every sequence's batch position (stochastic depth),
+    and the heads reach the output dict through a differentiable scatter."""
     (B, T), dev, out = masks2d.shape, x.device, None
+    if order is not None:
+        return _train_rows(model, x, masks2d, buckets, with_aux, order)
     for wave in waves(buckets, model._chunk_size(B)):
         plan = add_filler(wave, T)
         # (a filler bucket recomputes the first frames of some pair under an all-false mask: finite numbers nobody reads)
@@ -387,6 +415,24 @@ def mask_vrd_rows(model, x, masks2d, buckets, with_aux, t_ref=None):
                 if b.sel is not None:
                     scatter_heads(dst, i64, b.T, logits[p:p + b.n], seg)
                 p += b.n
+    out["output_mask"] = masks2d[:, None, :]
+    return out
+
+
+def _train_rows(model, x, masks2d, plan, with_aux, order):
+    """mask_vrd_rows under autograd: see there"""
+    B, T = masks2d.shape
+    assert sum(b.n for b in plan) == B == len(order)
+    index = [b.sel for b in plan]
+    lay = ragged.Layout([(b.n, b.T, b.flat) for b in plan]).with_order(order)
+    idx64 = [i.long() for i in index]
+    mask = torch.cat([masks2d[i64, :b.T].reshape(-1) for b, i64 in zip(plan, idx64)]).view(1, lay.rows)
+    heads = model._heads(*backbone_rows(model.backbone, x, index, lay, mask), with_aux, lay)
+    frames = [b.T for b in plan]
+    layers = [dict(zip(("pred_logits", "pred_masks"), _ScatterHeads.apply(T, idx64, frames, logits, *segs))) for logits, segs in heads]
+    out = layers[-1]
+    if len(layers) > 1:
+        out["aux_outputs"] = layers[:-1]
     out["output_mask"] = masks2d[:, None, :]
     return out
 

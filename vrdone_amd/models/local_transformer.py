@@ -121,9 +121,9 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         return dp.scale if isinstance(dp, AffineDropPath) else None
 
     @staticmethod
-    def _drop(dp, tgt):
-        """Per-row stochastic-depth factors for a branch shaped like tgt (B, Tq, C), or None."""
-        return dp.row_factors(tgt.shape[0], tgt.shape[1], tgt.device) if isinstance(dp, AffineDropPath) else None
+    def _drop(dp, tgt, lay=None):
+        """Per-row stochastic-depth factors for a branch shaped like tgt (B, Tq, C) in the layout `lay`, or None."""
+        return dp.row_factors(tgt.shape[0], tgt.shape[1], tgt.device, lay) if isinstance(dp, AffineDropPath) else None
 
     def cl(self, tgt, memory, tgt_mask, memory_mask, query_pos=None, stream_add=None, out=None, qlay=None, klay=None,
            self_ready=None, cross_ready=None):
@@ -145,12 +145,12 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
         if fuse1:
             tgt, _ = self.self_attn.cl_qkv(tgt, tgt, tgt, tgt_mask, tgt_mask, pre_ln=(self.ln1.weight, self.ln1.bias),
                                            pre_ln_on="qk", scale=self._scale(self.drop_path_attn1), ready=self_ready,
-                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True, **self_lays)
+                                           row_scale=self._drop(self.drop_path_attn1, tgt, qlay), res=tgt, res_masked=True, **self_lays)
         else:
             t2 = self.ln1.cl(tgt, post_add=query_pos)
             tgt, _ = self.self_attn.cl_qkv(t2, t2, tgt, tgt_mask, tgt_mask, scale=self._scale(self.drop_path_attn1),
-                                           row_scale=self._drop(self.drop_path_attn1, tgt), res=tgt, res_masked=True, **self_lays)
-        kw = dict(scale=self._scale(self.drop_path_attn2), row_scale=self._drop(self.drop_path_attn2, tgt), res=tgt,
+                                           row_scale=self._drop(self.drop_path_attn1, tgt, qlay), res=tgt, res_masked=True, **self_lays)
+        kw = dict(scale=self._scale(self.drop_path_attn2), row_scale=self._drop(self.drop_path_attn2, tgt, qlay), res=tgt,
                   res_masked=True, res2=stream_add if last else None, out=out if last else None, **cross_lays)
         if fuse2:
             tgt, _ = self.multihead_attn.cl_qkv(tgt, memory, memory, tgt_mask, memory_mask,
@@ -163,7 +163,7 @@ class MaskedConvTransformerDecoderLayer(nn.Module):
             t2 = self.ln3.cl(tgt)
             h = ops.conv_gemm(t2, self.mlp[0].weight, self.mlp[0].bias, act=ops.ACT_GELU)
             tgt = ops.conv_gemm(h, self.mlp[3].weight, self.mlp[3].bias, row_mask=tgt_mask, scale=self._scale(self.drop_path_mlp),
-                                row_scale=self._drop(self.drop_path_mlp, tgt), res=tgt, out=out)
+                                row_scale=self._drop(self.drop_path_mlp, tgt, qlay), res=tgt, out=out)
         return tgt, tgt_mask
 
     def forward(self, tgt, memory, tgt_mask: Optional[Tensor] = None, memory_mask: Optional[Tensor] = None,

@@ -186,6 +186,44 @@ class MaskVRD(nn.Module):
     # 226 pairs 12.2 / 11.9, 540 pairs 18.9 / 23.1 (profiles/r06_forward_test_small.json)
     ROWS_MIN_PAIRS = int(os.environ.get("VRDONE_ROWS_MIN_PAIRS", "256"))
 
+    # Training in the row space (opt-in; VRDONE_TRAIN_ROWS=1): a step whose batch is ragged -- proposals.train_getitem keeps a
+    # pair's own length -- computes every pair at its tight padded length, all lengths in one row space, forward and backward
+    # (models/ragged.py under autograd), instead of padding every pair to max_seq_len.  _train_rows_step says which steps qualify;
+    # the others take the batch form exactly as with the switch off.  `train_form` is the form the last training step took.
+    train_rows = os.environ.get("VRDONE_TRAIN_ROWS", "0") == "1"
+    # the bucket-merging threshold of the training plan (tight_buckets' min_rows; rows counted as 2 * pairs * T'): the value at which
+    # the vidor step (48 pairs x 512 frames, lengths U[8, 512]) is fastest in the row space (scripts/train_rows_bench.py --sweep,
+    # profiles/train_rows_bench.json: 0 -> 15 buckets, 4096 -> 7, 16384 -> 3; every further bucket costs the global attention and the
+    # mask head a launch pair of its own)
+    TRAIN_ROWS_MIN_ROWS = int(os.environ.get("VRDONE_TRAIN_ROWS_MIN_ROWS", "4096"))
+    train_form = "batch"
+
+    def train_rows_plan(self, lens, T=None):
+        """The bucket plan of a training batch of pairs of `lens` valid frames padded to T (default max_seq_len) frames:
+        [(T', [batch positions], flat)] -- tight_buckets under TRAIN_ROWS_MIN_ROWS, the buckets whose pairs all end in two padded
+        frames (flat: the dense k = 3 convs run flat over them, models/ragged.py) first, each kind by length.  Host only."""
+        T = self.max_seq_len if T is None else T
+        want = {}
+        for i, t2 in enumerate(self.tight_buckets(lens, [T] * len(lens), self.TRAIN_ROWS_MIN_ROWS)):
+            want.setdefault((lens[i] <= t2 - 2, t2), []).append(i)
+        return [(t2, want[(flat, t2)], flat) for flat, t2 in sorted(want, key=lambda k: (not k[0], k[1]))]
+
+    def _train_rows_step(self, batched_masks):
+        """The plan of a training step that takes the row space, or None (the batch form): the switch is set, both dropout rates
+        are 0 (element ids count batch rows), no absolute position rows (training keeps the materialised ones), the batch is one
+        launch wave, and the plan has at least two buckets or shrinks the one it has.  (The caller has made sure of the rest: a
+        list-form batch, training graphs off.)"""
+        known = getattr(batched_masks, "_vrd_lens", None)
+        B, T = batched_masks.shape[0], batched_masks.shape[-1]
+        if (not self.train_rows or any(self.dropout_rates) or self.use_abs_pe or known is None or known[0] != batched_masks._version
+                or len(known[1]) != B or B > self._chunk_size(B)):
+            return None
+        plan = self.train_rows_plan(known[1], T)
+        # (subject and object halves of a bucket are a row group each: one launch takes ragged._MAX_SEGS groups)
+        if (len(plan) == 1 and plan[0][0] == T) or 2 * len(plan) > eval_batches.ragged._MAX_SEGS:
+            return None
+        return plan
+
     # forward_test / forward_test_videos build the winners' box tracks (`so_trajs`, ~100 k Python lists per video) only while
     # this is True.  A caller that scores on the device (evaluate.DeviceRelationScorer reads the tracklet boxes where they
     # are) sets it to False on its model: the key is then absent and every other key unchanged
@@ -285,11 +323,12 @@ class MaskVRD(nn.Module):
         out["output_mask"] = masks2d[:, None, :]
         return out
 
-    def _mask_vrd(self, batched_inputs, batched_masks, with_aux=None, t_ref=None):
+    def _mask_vrd(self, batched_inputs, batched_masks, with_aux=None, t_ref=None, train_plan=None):
         """(B, C_in, T) fp32, (B, 1, T) bool -> dict(pred_logits (B,Q,K+1), pred_masks (B,Q,T),
         [aux_outputs], output_mask (B,1,T)); backbone -> neck -> predictor like the reference.
         t_ref: the length the reference pads these pairs to when that is not T (a batch that a caller padded tighter, eval only);
-        absolute position rows follow it."""
+        absolute position rows follow it.
+        train_plan: the plan of a training step in the row space (_train_rows_step; autograd recording)."""
         if not batched_inputs.is_cuda:
             raise RuntimeError("MaskVRD._mask_vrd runs on the HIP device only; move the model and inputs to 'cuda'")
         B = batched_inputs.shape[0]
@@ -302,6 +341,15 @@ class MaskVRD(nn.Module):
                 return self._mask_vrd_tight(batched_inputs, masks2d, plan, with_aux, t_ref)
         if self.training and torch.is_grad_enabled():
             self._begin_training_pass(batched_inputs.device)
+        if train_plan is not None:
+            assert self.training and torch.is_grad_enabled() and batched_inputs.is_contiguous()
+            order = [i for _, ids, _ in train_plan for i in ids]
+            every = torch.tensor(order, dtype=torch.int32).to(masks2d.device)          # (one upload for all buckets' pair indices)
+            buckets, at = [], 0
+            for t2, ids, flat in train_plan:
+                buckets.append(eval_batches.Bucket(t2, every[at:at + len(ids)], len(ids), flat))
+                at += len(ids)
+            return eval_batches.mask_vrd_rows(self, batched_inputs, masks2d, buckets, with_aux, order=order)
         outs = []
         step = self._chunk_size(B)
         for b0 in range(0, B, step):
@@ -399,6 +447,8 @@ class MaskVRD(nn.Module):
             flag = ops.f16_range_flag(pdev)
             flag.zero_()
         graphs = torch.is_grad_enabled() and self.training and train_graph.enabled(self)
+        if torch.is_grad_enabled() and self.training:
+            self.train_form = "batch"            # (until the step turns out to take the row space)
         if 'train_source' in input_data:
             # a batch built on the device (proposals.TrainSource / train_tables): one gather launch writes the operand buffers of
             # the backbone's first stage and the target masks -- no (B, C_in, T) tensor, no vrd_bct_to_btc
@@ -417,7 +467,10 @@ class MaskVRD(nn.Module):
             if graphs:
                 predictions = train_graph.mask_vrd(self, x, m)        # two HIP-graph replays instead of ~2,000 launches
             else:
-                predictions = self._mask_vrd(x, m, with_aux=self.deep_supervision)
+                plan = self._train_rows_step(m) if self.training and torch.is_grad_enabled() else None
+                if plan is not None:
+                    self.train_form = "rows"
+                predictions = self._mask_vrd(x, m, with_aux=self.deep_supervision, train_plan=plan)
         losses = self.criterion(predictions, ground_truth)
         if guard:
             # (one 4-byte read behind the step's launches: a host synchronisation, like the loss.item() of the reference's loop,

@@ -11,8 +11,8 @@ models/eval_batches.py (it builds the layouts; `filler_buckets` here tells it ho
 
   * the batch form (`Layout.batch`, what a `cl` method reads from its tensors' shape when no layout is given): B sequences of
     T frames as a (B, T, C) tensor.  Every operation here is then the one `ops.*` call on that tensor, and under autograd its
-    result is the tensor the op recorded.  Training runs in this form only.
-  * the row space (inference only): `MaskVRD._mask_vrd` computes the pairs of a batch at the shortest padded lengths that give
+    result is the tensor the op recorded.  Training runs in this form unless `MaskVRD.train_rows` is set.
+  * the row space: `MaskVRD._mask_vrd` computes the pairs of a batch at the shortest padded lengths that give
     the reference's outputs (`tight padding`, models/maskvrd.py), pairs of equal padded length as one bucket.  Run bucket by
     bucket, every launch of the network shrinks with its bucket, and below ~260 k rows a bucket's GEMMs fall off the 256 x 256
     kernel.  So all buckets lie back to back in one (1, R, C) buffer per activation -- bucket i = rows [off_i, off_i + n_i * T_i)
@@ -26,6 +26,12 @@ the next sequence's first frame: the first two are padded frames here (tight pad
 frames behind every pair it shortens; pairs within one frame of their padded length are bucketed apart, behind the others, and
 their buckets' k = 3 convs run one by one) whose outputs the row mask zeroes, which makes the flat conv equal to the per-sequence
 one on every valid row.
+
+Under autograd (a training step with `MaskVRD.train_rows`) every operation here hands its layout's groups to ONE differentiable
+op (vrdone_amd/autograd.py: `segs`), whose backward is one launch over all groups (depthwise conv, banded attention, max-pool)
+or the batch form's entry point group by group on pointer offsets into one gradient tensor (global attention, mask head): no
+operation slices the row space under autograd -- torch's slice backward would allocate and add a full-size zero tensor per group.
+What stays inference-only: dwconv_ln_multi, absolute position rows (layernorm_pos, position_rows; a layout with t_refs) and `drop`.
 
 Subject and object rows of the shared-weight stages are stacked as [all subject buckets | all object buckets] (`stacked`), so
 that either half is a contiguous range with the same bucket layout; in the batch form that is one bucket of 2B sequences.
@@ -68,6 +74,8 @@ class Layout:
         self.lead = (1, self.rows) if axis else segs[0][1:]           # a tensor's shape in front of its channels
         self._tails, self._stacked = {}, None
         self.t_refs = None          # see with_refs
+        self.order = None           # see with_order
+        self._order_rows = {}
 
     @classmethod
     def _of_segs(cls, segs, flat, axis):
@@ -99,6 +107,37 @@ class Layout:
         lay.t_refs = [r if isinstance(r, int) else tuple(r) for r in t_refs]
         return lay
 
+    def with_order(self, order):
+        """This layout with the batch position of every one of its sequences, in row order: `order` is a permutation of
+        range(sequences) -- a training step in the row space lays the pairs out bucket by bucket, and per-sample state drawn in
+        batch order (stochastic depth: blocks.AffineDropPath.row_factors) has to reach sample i's rows wherever they lie."""
+        order = [int(i) for i in order]
+        assert sorted(order) == list(range(sum(n for _, n, _ in self.segs)))
+        lay = Layout._of_segs(self.segs, self.flat, self.axis)
+        lay.t_refs, lay.order = self.t_refs, order
+        return lay
+
+    def _derived(self, lay, order=None):
+        """`lay`, a layout of this one's sequences at other frame counts, with this one's batch positions (or `order`)"""
+        if self.order is not None and lay.order is None:
+            lay.order = self.order if order is None else order
+            lay._order_rows = self._order_rows if order is None else {}
+        return lay
+
+    def sample_rows(self, device):
+        """(samples, None) in the batch form, whose sequences are the samples in order; in a row space (samples, the batch
+        position of every row's sequence as an int64 tensor on `device`), built once per layout and frame count."""
+        n_seq = sum(n for _, n, _ in self.segs)
+        if self.axis == 0:
+            return n_seq, None
+        assert self.order is not None, "a row space that takes per-sample factors needs its sequences' batch positions (with_order)"
+        key = (tuple(self.segs), str(device))
+        rows = self._order_rows.get(key)
+        if rows is None:
+            frames = torch.tensor([T for _, n, T in self.segs for _ in range(n)])
+            rows = self._order_rows[key] = torch.repeat_interleave(torch.tensor(self.order), frames).to(device)
+        return n_seq, rows
+
     def seq_refs(self):
         """the reference padded length of every sequence, in row order (None: no lengths given, the sequences' own)"""
         if self.t_refs is None:
@@ -118,6 +157,8 @@ class Layout:
                 self._stacked = Layout._of_segs(self.twice(), self.flat * 2, 1)
             if self.t_refs is not None:         # (subject and object sequences share their pair's length)
                 self._stacked = self._stacked.with_refs(self.t_refs * 2 if self.axis else [r if isinstance(r, int) else r * 2 for r in self.t_refs])
+            if self.order is not None:          # (the batch form stacks [all subjects | all objects]: object i is sample B + i)
+                self._stacked = self._derived(self._stacked, self.order + [len(self.order) + i for i in self.order])
         return self._stacked
 
     def strided(self, s):
@@ -126,13 +167,13 @@ class Layout:
             return self
         if self.axis == 0:
             return Layout.batch(self.segs[0][1], self.segs[0][2] // s)
-        return Layout._of_segs([(off // s, n, T // s) for off, n, T in self.segs], self.flat, 1)
+        return self._derived(Layout._of_segs([(off // s, n, T // s) for off, n, T in self.segs], self.flat, 1))
 
     def queries(self, Q):
         """Q rows per sequence (the predictor's queries), the sequences in the same order"""
         if self.axis == 0:
             return Layout.batch(self.segs[0][1], Q)
-        return Layout([(n, Q, False) for _, n, _ in self.segs])
+        return self._derived(Layout([(n, Q, False) for _, n, _ in self.segs]))
 
     def min_frames(self):
         return min(T for _, _, T in self.segs)
@@ -149,7 +190,10 @@ class Layout:
 
     def new(self, width, like, zeros=False):
         """a fresh f32 activation of `width` channels in this layout, on the device of `like`"""
-        assert self.axis == 0 or not torch.is_grad_enabled(), "the row space is an inference form: training runs in the batch form"
+        # under autograd a row space is one a training step laid out (with_order), without reference lengths: absolute position
+        # rows keep the batch form in training
+        assert self.axis == 0 or not torch.is_grad_enabled() or (self.order is not None and self.t_refs is None), \
+            "a row space under autograd is a training step's (Layout.with_order), without reference lengths; any other is an inference form"
         return (torch.zeros if zeros else torch.empty)(*self.lead, width, device=_raw(like).device, dtype=torch.float32)
 
     def halves(self, x):
@@ -179,6 +223,9 @@ def _part(x, off, n, T):
     ops = _ops()
     if isinstance(x, ops.Pair):
         return ops.Pair(_part(x.t, off, n, T), x.width, x.fmt)
+    if off == 0 and n * T == x.shape[1]:              # all rows: a view of the tensor itself (under autograd: no slice node)
+        return x.view(n, T, *x.shape[2:])
+    assert not (torch.is_grad_enabled() and x.requires_grad), "no operation slices a row space under autograd (see the module text)"
     return x[0, off:off + n * T].unflatten(0, (n, T))
 
 
@@ -193,6 +240,30 @@ def _raw(x):
     return x.t if isinstance(x, _ops().Pair) else x
 
 
+def _recorded(lay):
+    """a row space under autograd: the operation hands the layout's groups to one differentiable op (see the module text)"""
+    return lay.axis == 1 and torch.is_grad_enabled()
+
+
+class _SplitRows(torch.autograd.Function):
+    """The row runs [(first row, sequences, frames)] of x (1, R, C) as (sequences, frames, C) tensors.  Backward copies the runs'
+    gradients into ONE (1, R, C) tensor (the runs cover all rows); slicing x run by run would have torch allocate and add a
+    full-size zero tensor per run.  Its counterpart towards the result is torch.cat, whose backward takes views."""
+
+    @staticmethod
+    def forward(ctx, x, runs):
+        assert sum(n * T for _, n, T in runs) == x.shape[1]
+        ctx.runs, ctx.shape = runs, x.shape
+        return tuple(x[0, off:off + n * T].unflatten(0, (n, T)).clone() for off, n, T in runs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        dx = torch.empty(ctx.shape, device=grads[0].device, dtype=grads[0].dtype)
+        for (off, n, T), g in zip(ctx.runs, grads):
+            dx[0, off:off + n * T] = g.reshape(n * T, -1)
+        return dx, None
+
+
 def _rows_of(x, sl):
     ops = _ops()
     return ops.Pair(x.t[:, sl], x.width, x.fmt) if isinstance(x, ops.Pair) else x[:, sl]
@@ -202,6 +273,8 @@ def dwconv_ln(lay, x, sets, mask_out, *, stride=1, x_up=None, pre_ln=None):
     """ops.dwconv_ln over the buckets of x's layout `lay`: outputs and mask_out at every stride-th frame, x_up the rows of the
     coarser level.  One launch: a single group of sequences in the kernel's own form, several as its row groups (vrd_row_segs)."""
     ops = _ops()
+    if _recorded(lay):
+        return ops.dwconv_ln(x, sets, mask_out=mask_out, stride=stride, x_up=x_up, pre_ln=pre_ln, segs=list(lay.segs))
     segs = _merged(lay.segs)
     if len(segs) == 1:
         off, n, T = segs[0]
@@ -291,6 +364,12 @@ def attention(q, k, v, kv_mask, q_mask, n_head, qlay, klay, *, half_win=None, re
     # buckets of one frame count on both sides (the predictor's query self-attention: every bucket is n x Q rows) are one launch
     if len(_merged(qsegs)) == 1 and len(_merged(ksegs)) == 1:
         qsegs, ksegs = _merged(qsegs), _merged(ksegs)
+    if _recorded(qlay):
+        assert drop is None and klay.axis == 1
+        if half_win is not None:
+            assert list(qsegs) == list(ksegs)
+            return ops.local_attention(q, k, v, kv_mask, n_head, half_win, rel_pe=rel_pe, segs=list(qsegs))
+        return ops.attention(q, k, v, kv_mask, n_head, segs=(list(qsegs), list(ksegs)))
 
     def one(qs, ks, out=None):
         assert qs[1] == ks[1]
@@ -356,6 +435,8 @@ def _lanes(dev):
 def maxpool_mask(lay, x, mask):
     """ops.maxpool_mask (the pyramid's stride-2 skip path) bucket by bucket -> (pooled rows, mask) in lay.strided(2)"""
     ops = _ops()
+    if _recorded(lay):
+        return ops.maxpool_mask(x, mask, segs=list(lay.segs))
     if len(lay.segs) == 1:
         y, m_out = ops.maxpool_mask(lay.part(x, lay.segs[0]), lay.part(mask, lay.segs[0]))
         return lay.whole(y), lay.whole(m_out)
@@ -383,10 +464,27 @@ def conv3(lay, h, conv, row_mask, *, out=None, out_pair=False, norm=None):
         return ops.conv_gemm(x, conv.weight, conv.bias, row_mask=m, out=o, out_pair=out_pair)
     if lay.axis == 0:
         return one(h, row_mask, out)
+    tails = lay.tail_rows(1, _raw(h).device)
+    if torch.is_grad_enabled():
+        # under autograd: the zeroing of the tail rows is recorded (those rows receive no gradient), and the flat run and the
+        # other buckets are the runs of one split -- a single flat run is the tensor itself
+        if tails is not None:
+            h = h.index_fill(1, tails, 0.0) if h.requires_grad else h.index_fill_(1, tails, 0.0)
+        runs, flat_before = [], False          # (a stacked layout has its flat buckets in front of either half)
+        for (off, n, T), f in zip(lay.segs, lay.flat):
+            if f and flat_before and runs[-1][0] + runs[-1][2] == off:
+                runs[-1] = (runs[-1][0], 1, runs[-1][2] + n * T)
+            else:
+                runs.append((off, 1, n * T) if f else (off, n, T))
+            flat_before = f
+        if len(runs) == 1:
+            return one(h, row_mask, None)
+        parts = _SplitRows.apply(h, runs) if h.requires_grad else [_part(h, *run) for run in runs]
+        outs = [one(x, _part(row_mask, *run), None) for x, run in zip(parts, runs)]
+        return torch.cat([o.reshape(1, -1, o.shape[-1]) for o in outs], dim=1)
     N = conv.weight.shape[0]
     if out is None:
         out = lay.new(N, h)
-    tails = lay.tail_rows(1, _raw(h).device)
     if tails is not None:
         _raw(h)[0].index_fill_(0, tails, 0.0)            # (f32 rows or pair rows: all-zero bits are the value zero in both)
     at = 0
@@ -406,6 +504,8 @@ def conv3(lay, h, conv, row_mask, *, out=None, out_pair=False, norm=None):
 def mask_head(lay, emb, feat, out_mask, fill):
     """ops.mask_head bucket by bucket: emb (B, Q, Dp) of all pairs in bucket order -> [mask logits (n_i, Q, T_i) per bucket]"""
     ops = _ops()
+    if _recorded(lay):
+        return list(ops.mask_head(emb, feat, out_mask, fill, segs=list(lay.segs)))
     if len(lay.segs) == 1:
         return [ops.mask_head(emb, lay.part(feat, lay.segs[0]), lay.part(out_mask, lay.segs[0]), fill)]
     segs_out, p = [], 0

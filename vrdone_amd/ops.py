@@ -1059,13 +1059,13 @@ def dwconv_ln(x, sets, *, mask_out=None, stride=1, x_up=None, pre_ln=None, segs=
     """Fused depthwise conv * mask -> LayerNorm for up to three weight sets sharing x.
     sets: list of dicts(weight=(C, g, k) Conv1d weight, bias=None, gamma=None, beta=None, relu=False, out=None).
     pre_ln = (gamma, beta): the input rows are LayerNorm'ed as they are read (the block's ln1).
-    segs (inference path): x is a ragged row space (1, R, C) -- [(first row, sequences, frames)] groups of sequences back to
+    segs: x is a ragged row space (1, R, C) -- [(first row, sequences, frames)] groups of sequences back to
     back (vrd_row_segs); outputs, mask_out and x_up follow the same grouping at their own frame counts.
     Returns the list of outputs, each (B, T/stride, C)."""
     if recording(x, x_up, *(t for st in sets for t in (st["weight"], st.get("bias"), st.get("gamma"), st.get("beta"))),
                  *(pre_ln or ())):
         from . import autograd
-        return autograd.dwconv_ln(x, sets, mask_out=mask_out, stride=stride, x_up=x_up, pre_ln=pre_ln)
+        return autograd.dwconv_ln(x, sets, mask_out=mask_out, stride=stride, x_up=x_up, pre_ln=pre_ln, segs=segs)
     B, Tin, Cx = x.shape
     w0 = sets[0]["weight"]
     Cout, g, k = w0.shape
@@ -1158,7 +1158,7 @@ def _rel_pe_ptr(rel_pe, like, n_head, half_win):
 def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, out=None, segs=None, drop=None):
     """rel_pe: None or the module's (1, 1, n_head, window) relative position bias (reference blocks.py:739-743).
     out: (B, T, C) contiguous rows to write instead of a fresh tensor (inference path).
-    segs (inference path): q / k / v / mask are a ragged row space (1, R, ...): [(first row, sequences, frames)] (vrd_row_segs).
+    segs: q / k / v / mask are a ragged row space (1, R, ...): [(first row, sequences, frames)] (vrd_row_segs).
     half_win: window // 2 of an odd window from 3 to 19.
     drop (training): the attn_drop call (models.blocks.Drop: seed tensor, site, first row's number, rate) -- dropout on the window
     probabilities; such a call runs as autograd.LocalAttention whether or not an input needs a gradient (it drops regardless)."""
@@ -1172,7 +1172,7 @@ def local_attention(q, k, v, mask, n_head, half_win, pair=False, rel_pe=None, ou
     if recording(q, k, v, rel_pe) or drop is not None:
         from . import autograd
         assert drop is None or (segs is None and not pair)
-        return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe, drop)
+        return autograd.LocalAttention.apply(q, k, v, mask, n_head, half_win, rel_pe, drop, segs)
     B, T, Cc = q.shape
     rel = _rel_pe_ptr(rel_pe, q, n_head, half_win)
     pq, rows, cols, ld = _rows(q)
@@ -1202,11 +1202,12 @@ def attention(q, k, v, kv_mask, n_head, algo=0, pair=False, q_mask=None, out=Non
     segs (inference path, pair-row operands only): (qsegs, ksegs) -- q / q_mask / out are a ragged row space (1, Rq, ...) of the
     groups qsegs = [(first row, sequences, frames)], k / v / kv_mask one of ksegs (vrd_row_segs; the same sequences per group on
     both sides): every group's attention in one call (vrd_attention_pair_segs), bit for bit the group-by-group calls."""
+    if not isinstance(q, Pair) and recording(q, k, v):
+        # (with segs: f32 rows under autograd, every group on the entry points of the batch form -- autograd.Attention)
+        from . import autograd
+        return autograd.Attention.apply(q, k, v, kv_mask, n_head, segs)
     if segs is not None:
         return _attention_segs(q, k, v, kv_mask, n_head, pair, q_mask, out, *segs)
-    if not isinstance(q, Pair) and recording(q, k, v):
-        from . import autograd
-        return autograd.Attention.apply(q, k, v, kv_mask, n_head)
     fmt, (B, Tq, Cc), (_, Tk, _), pq, ldq, pk, pv, ldk, rows_k, out = _qkv_rows(q, k, v, out)
     if fmt:
         out_fmt = fmt if pair else 0
@@ -1263,12 +1264,14 @@ def _attention_segs(q, k, v, kv_mask, n_head, pair, q_mask, out, qsegs, ksegs):
     return _as_pair(out, Cc, out_fmt)
 
 
-def maxpool_mask(x, mask_in, out=None):
+def maxpool_mask(x, mask_in, out=None, segs=None):
     """MaxPool1d(3, 2, 1)(x) * mask[::2]; returns (pooled (B, T/2, C), mask_out (B, T/2) bool).
-    out: (pooled, mask_out) contiguous buffers to write instead of fresh tensors (inference path)."""
+    out: (pooled, mask_out) contiguous buffers to write instead of fresh tensors (inference path).
+    segs (autograd path): x (1, R, C) / mask_in (1, R) are a ragged row space of the groups [(first row, sequences, frames)]."""
     if recording(x):
         from . import autograd
-        return autograd.MaxPoolMask.apply(x, mask_in)
+        return autograd.MaxPoolMask.apply(x, mask_in, segs)
+    assert segs is None, "maxpool_mask(segs=...) is the autograd form; inference walks the groups (models/ragged.py)"
     B, T, Cc = x.shape
     px, rows, cols, ldx = _rows(x)
     if out is None:
@@ -1283,11 +1286,14 @@ def maxpool_mask(x, mask_in, out=None):
     return y, m_out
 
 
-def mask_head(emb, feat, out_mask, fill=-10.0):
-    """emb (B, Q, Dp), feat (B, T, Dp), out_mask (B, T) -> (B, Q, T)."""
+def mask_head(emb, feat, out_mask, fill=-10.0, segs=None):
+    """emb (B, Q, Dp), feat (B, T, Dp), out_mask (B, T) -> (B, Q, T).
+    segs (autograd path): feat (1, R, Dp) / out_mask (1, R) are a ragged row space of the groups [(first row, sequences, frames)],
+    emb their sequences in order -> one (n_i, Q, T_i) tensor per group."""
     if recording(emb, feat):
         from . import autograd
-        return autograd.MaskHead.apply(emb, feat, out_mask, fill)
+        return autograd.MaskHead.apply(emb, feat, out_mask, fill, segs)
+    assert segs is None, "mask_head(segs=...) is the autograd form; inference walks the groups (models/ragged.py)"
     B, Q, Dp = emb.shape
     T = feat.shape[1]
     pe, _, _, lde = _rows(emb)
