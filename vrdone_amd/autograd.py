@@ -549,7 +549,9 @@ def _attention_bwd(q, k, v, out, dO, kv_mask, H, lse, split_bwd, bfmt, dq, dk, d
     dev = q.device
     if _flash_attention_route(split_bwd, hd, Tq, Tk):
         # flash style (vrd_attention_bwd): the scores are recomputed tile by tile in the split of the other backward GEMMs
-        # (bf16 planes; f16x3 mode: f16 planes, dO and dS at power-of-two factors from the absolute maxima of dO and v);
+        # (bf16 planes; f16x3 mode: f16 planes, dO and dS at power-of-two factors from the absolute maxima of dO and v -- of the
+        # whole call: the dS planes are absolute, 2^-25 / s_s, so dq / dk of a sequence whose dO is 2^-12 of the call's largest are
+        # good to 1.5e-4 of their own largest entry, not to the 1e-6 of the others: vrd_attn_bwd.hip, tests/test_gpu_attn_hard.py);
         # no (B, H, Tq, Tk) matrix exists
         scratch = torch.empty(2, B, H, Tq, device=dev, dtype=torch.float32)
         so = sv = None
